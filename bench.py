@@ -358,6 +358,50 @@ def cpu_baseline(wname, w, steps=5):
     return {"value": value, "unit": unit, "cores": cores, "kind": "port", "sample": f"{what}, {steps} timed steps after {n_warm} warm-up step(s) ({dt:.1f} s)"}
 
 
+# --------------------------------------------------------------------------------------------------------------- output dump
+DUMP_MAX_ELEMS = 1 << 21        # per array: 8 MB of float32; a larger array is written as a fixed, seeded sample of this many entries
+DUMP_MAX_BYTES = 64 << 20       # all arrays of one dump together
+DUMP_SEED = 0
+
+
+def _keep(keep, name, t):
+    """pass `t` through; also store it under `name` when the step was given a dict to keep its outputs in"""
+    if keep is not None:
+        keep[name] = t
+    return t
+
+
+def _sample_index(n):
+    """None (take everything) if n fits, else DUMP_MAX_ELEMS sorted positions in [0, n): a function of n alone, so that two builds
+    sample the same entries"""
+    import torch
+    if n <= DUMP_MAX_ELEMS:
+        return None
+    g = torch.Generator().manual_seed(DUMP_SEED)
+    return torch.randint(0, n, (DUMP_MAX_ELEMS,), generator=g).sort().values
+
+
+def dump_outputs(out_dir, keep, loss, model):
+    """--dump-outputs DIR: what the last timed step handed its caller, as DIR/<name>.npy in float32 — the loss, the model outputs the
+    step kept (logits / MAE prediction and mask / encoder features and taps) and the parameters after the optimiser step (`params`:
+    all parameters in named_parameters() order, flattened and concatenated).  Arrays above DUMP_MAX_ELEMS entries are written as the
+    1-D sample at the _sample_index positions of their flattened form, smaller ones whole in their own shape."""
+    import numpy as np
+    import torch
+    arrays = {"loss": loss.detach().float().reshape(1).cpu()}
+    params = torch.cat([p.detach().float().reshape(-1) for p in model.parameters()])
+    for name, t in dict(keep, params=params).items():
+        idx = _sample_index(t.numel())
+        arrays[name] = (t.detach() if idx is None else t.detach().reshape(-1)[idx.to(t.device)]).float().cpu()
+    nbytes = sum(a.numel() * 4 for a in arrays.values())
+    if nbytes > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {nbytes} bytes, more than {DUMP_MAX_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.numpy())
+    return sorted(arrays), nbytes
+
+
 # --------------------------------------------------------------------------------------------------------------- workloads
 def setup_parallel_groups(args, w, world, rank):
     """--sp / --tp: the process groups of the reference's Hybrid-OP layout (utils/misc.init_par_groups = reference utils/misc.py:129-238;
@@ -379,7 +423,8 @@ def setup_parallel_groups(args, w, world, rank):
 
 
 def build_workload(args, w, dev, rank, par=None):
-    """-> (net-able model, step closure factory inputs): returns (model, make_step) where make_step(net, opt, sch) -> step()"""
+    """-> (net-able model, step closure factory inputs): returns (model, make_step) where make_step(net, opt, sch) -> step(keep=None);
+    a step given a dict `keep` also stores in it (by reference, no copy) the model outputs it computed, for --dump-outputs"""
     import torch
     from UCF_VIT.utils.fused_attn import FusedAttn
     B = args.batch or w["batch"]
@@ -402,8 +447,8 @@ def build_workload(args, w, dev, rank, par=None):
         y = torch.randint(0, w["classes"], (B,), generator=g).to(dev)
 
         def make_step(net, opt, sch):
-            def step():
-                loss = cross_entropy_loss(net(x, variables, seq_ps), y)
+            def step(keep=None):
+                loss = cross_entropy_loss(_keep(keep, "logits", net(x, variables, seq_ps)), y)
                 loss.backward()
                 opt.step()
                 opt.zero_grad()
@@ -424,8 +469,10 @@ def build_workload(args, w, dev, rank, par=None):
         noise = torch.rand(B, L, generator=g).to(dev)                          # fresh mask noise would be torch.rand on the device: same cost
 
         def make_step(net, opt, sch):
-            def step():
+            def step(keep=None):
                 pred, mask = net(x, variables, None, noise=noise)
+                if keep is not None:
+                    keep.update(pred=pred, mask=mask)
                 loss = patch_mse_loss(pred, x, w["patch"])                     # loss_fn "MSE": over ALL patches (base_config.yaml:29)
                 loss.backward()
                 opt.step()
@@ -462,11 +509,11 @@ def build_workload(args, w, dev, rank, par=None):
             labels_l = SD.local_slab(labels, par["spg"], 1).contiguous()
 
         def make_step(net, opt, sch):
-            def step():
+            def step(keep=None):
                 if sharded:
-                    loss = SD.sharded_dice_ce(net(x, None), labels_l, par["spg"])
+                    loss = SD.sharded_dice_ce(_keep(keep, "logits", net(x, None)), labels_l, par["spg"])
                 else:
-                    loss = HF.dice_ce(net(x, None), labels)                   # DiceCELoss(to_onehot_y, softmax, squared_pred), train_unetr_simple.py:38
+                    loss = HF.dice_ce(_keep(keep, "logits", net(x, None)), labels)   # DiceCELoss(to_onehot_y, softmax, squared_pred), train_unetr_simple.py:38
                 loss.backward()
                 opt.step()
                 opt.zero_grad()
@@ -488,8 +535,10 @@ def build_workload(args, w, dev, rank, par=None):
     def make_step(net, opt, sch):
         mod = net.module if hasattr(net, "module") else net
 
-        def step():
+        def step(keep=None):
             feats, taps = mod.forward_intermediates(x, None, None, indices=taps_at)
+            if keep is not None:
+                keep.update(features=feats, **{f"tap{i}": t for i, t in zip(taps_at, taps)})
             # synthetic objective on what the decoder consumes (final features + the three taps): four tiny element-wise reductions
             loss = feats.float().square().mean() + sum(t.float().square().mean() for t in taps)
             loss.backward()
@@ -545,7 +594,11 @@ def main():
     ap.add_argument("--sp", type=int, default=1, help="sequence-parallel group size (UNETR workloads; the token sequence is sharded)")
     ap.add_argument("--ulysses", type=int, default=0, help="all-to-all factor P_u of the 2-D Ulysses x ring layout (default gcd(heads, sp))")
     ap.add_argument("--tp", type=int, default=1, help="tensor-parallel (Hybrid-OP head / hidden shard) group size (UNETR workloads)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy, float32, at most 64 MB")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
     if args.sp < 1 or args.tp < 1 or (args.sp > 1 and args.tp > 1) or args.gpus % (args.sp * args.tp):
         raise SystemExit("bench.py: --gpus must be a multiple of --sp or --tp (sequence and tensor parallelism are not combined inside one Block)")
     if (args.sp > 1 or args.tp > 1) and WORKLOADS[args.workload]["kind"] != "unetr":
@@ -614,10 +667,12 @@ def main():
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
+    keep = {} if args.dump_outputs and rank == 0 else None
+    last = args.steps - 1
     prof.enabled = True
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        loss = step()
+    for i in range(args.steps):
+        loss = step(keep if i == last else None)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -630,6 +685,10 @@ def main():
         t = torch.tensor([dt], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if keep is not None:
+        names, nbytes = dump_outputs(args.dump_outputs, keep, loss, model)
+        keep = None
+        log(f"outputs of the last timed step written to {args.dump_outputs}: {', '.join(names)} ({nbytes / 2**20:.1f} MB)")
 
     # measured MFMA ceiling of THIS device (outside the timed region): a pure bf16 MFMA stream, ~0.3 s so the clock settles the way
     # it does inside the step (the chip lowers its clock under matrix load; the nominal 2.5 PFLOP/s assumes 2.4 GHz)

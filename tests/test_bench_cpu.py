@@ -59,6 +59,37 @@ def test_parent_stops_the_other_ranks_when_one_dies():
     assert not [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
 
 
+def test_steps_must_be_positive():
+    r = _run(["--steps", "0"], {"UCFVIT_BENCH_DRY": "1"})
+    assert r.returncode != 0 and "--steps must be at least 1" in r.stderr
+    assert not [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
+
+
+def test_dump_outputs_writes_float32_arrays_with_a_fixed_sample(tmp_path):
+    """--dump-outputs: the loss, the kept outputs (whole in their own shape when small, a fixed seeded sample of the flattened
+    tensor when large) and a sample of the concatenated parameters, float32, within the 64 MB budget; the sample positions depend
+    on the array size alone, so two runs (two builds) write the same entries"""
+    import numpy as np
+    import torch
+    import bench
+    model = torch.nn.Sequential(torch.nn.Linear(1024, 2048), torch.nn.Linear(2048, 1000))       # 4.2 M parameters: sampled
+    big = torch.randn(3000, 1000).bfloat16()
+    keep = {"logits": torch.randn(8, 5), "pred": big, "mask": torch.ones(4, 5, dtype=torch.bool)}
+    names, nbytes = bench.dump_outputs(str(tmp_path / "a"), keep, torch.tensor(1.25), model)
+    assert names == ["logits", "loss", "mask", "params", "pred"] and nbytes <= bench.DUMP_MAX_BYTES
+    z = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in names}
+    assert all(a.dtype == np.float32 for a in z.values())
+    assert z["loss"].tolist() == [1.25] and z["logits"].shape == (8, 5) and np.array_equal(z["logits"], keep["logits"].numpy())
+    assert z["mask"].shape == (4, 5) and (z["mask"] == 1).all()
+    n = bench.DUMP_MAX_ELEMS
+    assert z["pred"].shape == (n,) and np.array_equal(z["pred"], big.reshape(-1)[bench._sample_index(big.numel())].float().numpy())
+    flat = torch.cat([p.detach().reshape(-1) for p in model.parameters()])
+    assert z["params"].shape == (n,) and np.array_equal(z["params"], flat[bench._sample_index(flat.numel())].numpy())
+    bench.dump_outputs(str(tmp_path / "b"), keep, torch.tensor(1.25), model)
+    for name in names:
+        assert np.array_equal(np.load(tmp_path / "b" / (name + ".npy")), z[name]), name
+
+
 def test_work_figures_match_baseline_md():
     """BASELINE.md §4 / SURVEY §8d: 369.4 GF per image (ViT-L), 105.4 (ViT-B), 122.5 (MAE ViT-L r = 0.75), 11.8 TF per volume (UNETR encoder)"""
     import bench

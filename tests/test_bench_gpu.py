@@ -63,6 +63,20 @@ def test_bench_config5_tensor_parallel_layout_self_launch():
     assert d["config"]["parallelism"] == "tp2" and d["config"]["global_batch"] == 1
 
 
+def test_bench_dump_outputs_of_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: the last timed step's loss (the one the line reports), logits and a sample of the updated parameters as
+    float32 .npy files; `steps` of the line is the --steps given"""
+    import numpy as np
+    d = _bench(["--steps", "3", "--warmup", "1", "--workload", "vit_tiny16_256", "--batch", "32", "--no-cpu-baseline",
+                "--dump-outputs", str(tmp_path)])
+    _check(d, 1, "images/sec")
+    assert d["steps"] == 3 and d["ms_per_step"] > 0
+    z = {n: np.load(tmp_path / (n + ".npy")) for n in ("loss", "logits", "params")}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in z.values())
+    assert z["logits"].shape == (32, 2) and z["params"].ndim == 1 and z["params"].size > 0
+    assert abs(float(z["loss"][0]) - d["config"]["final_loss"]) < 1e-3
+
+
 def test_bench_mae_workload_line():
     d = _bench(["--steps", "2", "--warmup", "1", "--workload", "mae_vit_l16_224", "--batch", "64", "--cpu-steps", "1"])
     _check(d, 1, "images/sec")

@@ -238,12 +238,26 @@ def test_lr_schedule_oracle_and_product():
 def test_oracle_adamw_trajectory():
     g = load_golden("traj_vit_small.npz")
     m = R.VIT([32, 32], patch_size=8, in_chans=3, num_classes=5, embed_dim=64, depth=2, num_heads=2)
-    m.load_state_dict(det_state_dict(m, 31))
+    sd0 = det_state_dict(m, 31)
+    m.load_state_dict(sd0)
     opt = R.configure_optimizer(m, 1e-3, 0.9, 0.95, 1e-2)
     sch = R.WarmupCosineLR(opt, 2, 10, 1e-5, 1e-6)
+    lrs = []
     for i in range(5):
+        lrs.append(opt.param_groups[0]["lr"])
         loss, _ = R.train_step_class(m, opt, sch, g["x%d" % i], g["labels"][i])
         assert abs(loss.item() - g["losses"][i].item()) < 1e-5
     for k, v in m.state_dict().items():
-        if not k.startswith("token_embeds"):
-            assert rel_err(v, g["final." + k]) < 1e-5, k
+        if k.startswith("token_embeds"):
+            continue
+        ref = g["final." + k]
+        if k.endswith("attn.qkv.bias"):
+            # d(loss)/d(k-bias) is exactly zero in exact arithmetic (softmax shift invariance): its computed gradient is pure
+            # rounding noise, different on every CPU, which Adam normalises to steps of up to lr each (1 - beta1 <= sqrt(1 - beta2)).
+            # The q and v thirds are compared as everything else; the k third of both trajectories stays within those steps of its start
+            D = ref.numel() // 3
+            bound = 1.05 * sum(lrs)
+            for w_ in (v, ref):
+                assert float((w_[D:2 * D] - sd0[k][D:2 * D]).abs().max()) <= bound, k
+            v, ref = torch.cat([v[:D], v[2 * D:]]), torch.cat([ref[:D], ref[2 * D:]])
+        assert rel_err(v, ref) < 1e-5, k
