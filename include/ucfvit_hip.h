@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define UCFVIT_ABI_VERSION 12
+#define UCFVIT_ABI_VERSION 13
 
 #define UCFVIT_OK 0
 #define UCFVIT_ERR_INVALID_ARGUMENT (-1)
@@ -454,6 +454,26 @@ int ucfvit_depth_to_space2(const void* src, void* dst, int64_t B, int64_t Xi, in
                            const void* skip, int64_t Cs, void* stream);
 int ucfvit_pad_channels8(const float* src, void* dst, int64_t B, int64_t C, int64_t S, void* stream);
 int ucfvit_pad_rows8(const void* src, int src_dtype, void* dst, int64_t V, int64_t C, int64_t ld, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * UNETR decoder, align-corners trilinear resampling (csrc/resample.hip).  Reference call sites: src/UCF_VIT/simple/arch.py:887-906, 942-943,
+ * 989-991 — when the token grid times 16 is not the tile size (patch 4 / adaptive patching), dec1 goes through
+ * nn.Upsample(size=img_size, mode='trilinear', align_corners=True) before decoder2.  Channels-last bf16 [B][X][Y][Z][C], C % 8 == 0; every
+ * axis is resampled on its own, up, down or not at all (Xi -> Xo, ...), with torch's index and weight formula in fp32:
+ *   scale = (in - 1) / (out - 1) (0 when out == 1), src = scale * dst, i0 = (int) src, i1 = i0 + (i0 < in - 1), l1 = src - i0, l0 = 1 - l1.
+ *
+ * ucfvit_resample_trilinear_fwd: x dense [B][Xi][Yi][Zi][C] -> y[v ld_dst + c] over the [B][Xo][Yo][Zo] output voxels v, the 8 taps summed
+ *   in fp32 and rounded once.  ld_dst >= C, a multiple of 8 (larger: y is a channel slice of a wider channels-last buffer, pointer at the
+ *   slice's first channel).  skip (may be NULL): a dense [B][Xo][Yo][Zo][Cs] map copied behind the C channels of every row in the same pass
+ *   (Cs % 8 == 0, ld_dst >= C + Cs): the concatenation (resampled, skip) of UnetrUpBlock written as whole rows, as ucfvit_depth_to_space2.
+ * ucfvit_resample_trilinear_bwd: dx dense [B][Xi][Yi][Zi][C] = the transposed operator applied to dy[v ld_dy + c] (ld_dy >= C, a multiple
+ *   of 8: the gradient may be a channel slice of the concatenation's gradient).  Gather form: each input voxel sums the output voxels whose
+ *   stencil touches it in a fixed order, fp32, one rounding; no atomics, bitwise reproducible.
+ * ------------------------------------------------------------------------------------------------------ */
+int ucfvit_resample_trilinear_fwd(const void* x, void* y, int64_t B, int64_t Xi, int64_t Yi, int64_t Zi, int64_t Xo, int64_t Yo, int64_t Zo,
+                                  int64_t C, int64_t ld_dst, const void* skip, int64_t Cs, void* stream);
+int ucfvit_resample_trilinear_bwd(const void* dy, void* dx, int64_t B, int64_t Xi, int64_t Yi, int64_t Zi, int64_t Xo, int64_t Yo, int64_t Zo,
+                                  int64_t C, int64_t ld_dy, void* stream);
 
 #ifdef __cplusplus
 }

@@ -9,6 +9,9 @@ absent from the build container: PARITY UNPINNED against it; tests/test_conv3d.p
   tconv2x2x2(x, w)       ConvTranspose3d(k=2, s=2, bias=False): pointwise layer [V, Cin] -> [V, 8 Cout] (GEMM or 1x1x1 kernel) + depth-to-space
   conv1x1x1(x, w, b)     pointwise Conv3d: the 1x1x1 instance of the convolution kernels (tall-skinny voxel rows), the tiled GEMM of
                          nn.Linear when both channel counts reach 128
+  tconv1x1x1(x, w)       ConvTranspose3d(k=1, s=1, bias=False): the pointwise layer of UnetrUpBlock(upsample_kernel_size=1)
+  resample_trilinear(x, size)   nn.Upsample(size, mode='trilinear', align_corners=True) by csrc/resample.hip (gather-form backward)
+  tconv1x1x1_resample(x, w, size)   decoder2 of a UNETR whose token grid times 16 is not the tile size: the two above, commuted
   instnorm_act_cl        InstanceNorm3d (+ residual) + LeakyReLU on the channels-last layout
 """
 import torch
@@ -96,16 +99,18 @@ def _colsum_narrow(d2):
     return ops.colsum(d2.view(V // f, C * f)).view(f, C).sum(0)
 
 
-def _pointwise_fwd(x, w2, bias, cout_store, out_dtype=torch.bfloat16, accumulate_into=None, stats_eps=None):
-    """x [B, X, Y, Z, K] bf16 (K one of the kernels' input widths), w2 [N, K] float -> [B, X, Y, Z, cout_store] through the 1x1x1 kernel"""
+def _pointwise_fwd(x, w2, bias, cout_store, out_dtype=torch.bfloat16, accumulate_into=None, stats_eps=None, out=None):
+    """x [B, X, Y, Z, K] bf16 (K one of the kernels' input widths), w2 [N, K] float -> [B, X, Y, Z, cout_store] through the 1x1x1 kernel
+    (into `out`, a channel slice of a wider channels-last buffer, when given)"""
     n16 = _ceil_to(w2.shape[0], 16)
     if n16 != w2.shape[0]:
         w2 = torch.cat((w2, w2.new_zeros((n16 - w2.shape[0], w2.shape[1]))), 0)
         if bias is not None:
             bias = torch.cat((bias, bias.new_zeros(n16 - bias.numel())))
     packed = pack_conv_weight(w2.reshape(n16, w2.shape[1], 1, 1, 1))
+    into = {} if out is None else {"out": out}                   # (bench.py's kernel profiler wraps conv3d_fwd with its original keywords)
     return ops.conv3d_fwd(x, packed, n16, ksize=1, bias=None if bias is None else bias.float().contiguous(), cout_store=cout_store,
-                          out_dtype=out_dtype, accumulate_into=accumulate_into, stats_eps=stats_eps)
+                          out_dtype=out_dtype, accumulate_into=accumulate_into, stats_eps=stats_eps, **into)
 
 
 def _pointwise_wgrad(x, dy):
@@ -224,6 +229,83 @@ class TConv2x2x2Fn(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             dw = dw2.reshape(2, 2, 2, cout, cin).permute(4, 3, 0, 1, 2).contiguous()
         return dx, dw, dskip
+
+
+class TConv1x1x1Fn(torch.autograd.Function):
+    """ConvTranspose3d(k=1, s=1, bias=False) with weight [Cin, Cout, 1, 1, 1]: out[v][co] = sum_ci x[v][ci] w[ci][co], the pointwise layer
+    of monai's UnetrUpBlock(upsample_kernel_size=1), on the 1x1x1 convolution kernel.  With `skip` ([B, X, Y, Z, Cs]) the result is the
+    concatenation (out, skip): the kernel writes its rows into the first Cout channels of the concatenation (row stride Cout + Cs) and the
+    backward pass reads the two halves of the concatenation's gradient in place, as TConv2x2x2Fn."""
+
+    @staticmethod
+    def forward(ctx, x, w, skip):
+        cin, cout = w.shape[0], w.shape[1]
+        if tuple(w.shape[2:]) != (1, 1, 1) or x.shape[-1] != cin:
+            raise ValueError("tconv1x1x1: weight must be [Cin, Cout, 1, 1, 1] with Cin = the input's channels")
+        if not conv3_cin_supported(cin) or not conv3_cin_supported(cout) or cout % 16:
+            raise ValueError(f"tconv1x1x1: unsupported channel counts {cin} -> {cout}")   # cout is the data gradient's input width
+        w2 = w.detach().reshape(cin, cout).t()                                           # [Cout, Cin]
+        ctx.save_for_backward(x, w2)
+        ctx.cs = 0
+        if skip is None:
+            return _pointwise_fwd(x, w2, None, cout)
+        if tuple(skip.shape[:4]) != tuple(x.shape[:4]) or skip.dtype != torch.bfloat16 or skip.shape[-1] % 8:
+            raise ValueError("tconv1x1x1: skip must be a channels-last bf16 map of the input's extent")
+        ctx.cs = skip.shape[-1]
+        cat = torch.empty(tuple(x.shape[:4]) + (cout + ctx.cs,), dtype=torch.bfloat16, device=x.device)
+        _pointwise_fwd(x, w2, None, cout, out=cat[..., :cout])
+        cat[..., cout:].copy_(skip)
+        return cat
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w2 = ctx.saved_tensors
+        cout, cin = w2.shape
+        dskip = None
+        if ctx.cs:
+            if ctx.needs_input_grad[2]:
+                dskip = dy[..., cout:]
+            dy = dy[..., :cout]
+        dy = dy.contiguous()                   # the pointwise kernels read dense rows: one copy of the Cout half when it is a slice
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = _pointwise_fwd(dy, w2.t(), None, cin)
+        if ctx.needs_input_grad[1]:
+            dw = _pointwise_wgrad(x, dy).t().reshape(cin, cout, 1, 1, 1).contiguous()     # [Cout, Cin] -> the parameter's [Cin, Cout, 1, 1, 1]
+        return dx, dw, dskip
+
+
+class ResampleTrilinearFn(torch.autograd.Function):
+    """nn.Upsample(size, mode='trilinear', align_corners=True) over channels-last bf16 maps (csrc/resample.hip): fp32 taps, one rounding.
+    With `skip` ([B, *size, Cs]) the result is the concatenation (resampled, skip), written as whole rows in one pass; the backward pass
+    gathers the gradient straight out of the first C channels of the concatenation's gradient (no atomics: bitwise reproducible)."""
+
+    @staticmethod
+    def forward(ctx, x, size, skip):
+        size = tuple(int(s) for s in size)
+        if x.dim() != 5 or len(size) != 3:
+            raise ValueError("resample_trilinear: expected a channels-last map [B, X, Y, Z, C] and a 3-D size")
+        x = x.contiguous()
+        B, C = x.shape[0], x.shape[-1]
+        ctx.in_size, ctx.c, ctx.cs = tuple(x.shape[1:4]), C, 0
+        if skip is None:
+            return ops.resample_trilinear(x, size)
+        if tuple(skip.shape[:4]) != (B,) + size or skip.dtype != torch.bfloat16 or skip.shape[-1] % 8:
+            raise ValueError("resample_trilinear: skip must be a channels-last bf16 map of the output extent")
+        ctx.cs = skip.shape[-1]
+        cat = torch.empty((B,) + size + (C + ctx.cs,), dtype=torch.bfloat16, device=x.device)
+        ops.resample_trilinear(x, size, out=cat[..., :C], skip=skip.contiguous())
+        return cat
+
+    @staticmethod
+    def backward(ctx, dy):
+        dskip = None
+        if ctx.cs:
+            if ctx.needs_input_grad[2]:
+                dskip = dy[..., ctx.c:]
+            dy = dy[..., :ctx.c]
+        dx = ops.resample_trilinear_bwd(dy, ctx.in_size) if ctx.needs_input_grad[0] else None
+        return dx, None, dskip
 
 
 class Conv1x1x1Fn(torch.autograd.Function):
@@ -376,6 +458,29 @@ def conv3x3x3(x, w):
 def tconv2x2x2(x, w, skip=None):
     """skip given: returns the channel concatenation (transposed convolution, skip) — see TConv2x2x2Fn"""
     return TConv2x2x2Fn.apply(x, w, skip)
+
+
+def tconv1x1x1(x, w, skip=None):
+    """skip given: returns the channel concatenation (transposed convolution, skip) — see TConv1x1x1Fn"""
+    return TConv1x1x1Fn.apply(x, w, skip)
+
+
+def resample_trilinear(x, size, skip=None):
+    """skip given: returns the channel concatenation (resampled, skip) — see ResampleTrilinearFn"""
+    return ResampleTrilinearFn.apply(x, tuple(size), skip)
+
+
+def tconv1x1x1_resample(x, w, size, skip=None):
+    """UnetrUpBlock(upsample_kernel_size=1) of a UNETR whose token grid times 16 is not the tile size, up to its residual block: the
+    reference resamples dec1 to `size` (nn.Upsample, align_corners=True) and then applies ConvTranspose3d(k=1, s=1), and concatenates skip.
+    The transposed convolution has no bias and mixes channels per voxel, the resampling weighs voxels per channel, so in exact arithmetic
+    they commute: W interp(x) = interp(W x).  This runs them in the cheaper order — the pointwise layer at the input extent (2 Cout -> Cout
+    channels at 72^3 in the reference geometry), then the resampling of the Cout-channel result straight into the first Cout channels of
+    the concatenation, skip copied behind it in the same pass — which moves fewer bytes than resampling 2 Cout channels first (and the
+    gradient passes the same two functions in reverse).  The rounding points differ from the reference's order: here the pointwise result
+    is rounded to bf16 before it is interpolated, there the interpolated map is rounded before the pointwise layer; both are one bf16
+    rounding of an fp32 sum per stage."""
+    return resample_trilinear(tconv1x1x1(x, w), size, skip)
 
 
 def conv1x1x1(x, w, b=None, out_fp32=False):

@@ -685,9 +685,10 @@ def conv_packed_numel(cin, cout, ksize):
     return (cin // cpc) * (-(-(ksize ** 3) // tps)) * cout * 32
 
 
-def conv3d_fwd(x, w_packed, cout, ksize=3, bias=None, cout_store=None, out_dtype=torch.bfloat16, accumulate_into=None, stats_eps=None):
+def conv3d_fwd(x, w_packed, cout, ksize=3, bias=None, cout_store=None, out_dtype=torch.bfloat16, accumulate_into=None, stats_eps=None, out=None):
     """x [B, X, Y, Z, Cin] bf16, w_packed from conv.pack_conv_weight (cout rows, a multiple of 16) -> y [B, X, Y, Z, cout_store] (ksize 3:
-    stride 1, zero padding 1; ksize 1: pointwise).  bias: fp32 [cout] or None."""
+    stride 1, zero padding 1; ksize 1: pointwise).  bias: fp32 [cout] or None.  out: a bf16 channel slice of a wider channels-last buffer
+    to write y into (the first half of a concatenation)."""
     L = _l.load()
     _chk_cl(x, "conv3d.x"), _chk(w_packed, "conv3d.w_packed")
     B, X, Y, Z, cin = x.shape
@@ -698,7 +699,13 @@ def conv3d_fwd(x, w_packed, cout, ksize=3, bias=None, cout_store=None, out_dtype
         if bias.dtype != torch.float32 or bias.numel() != cout:
             raise ValueError("conv3d: bias must be fp32 [Cout]")
     cs = cout if cout_store is None else cout_store
-    if accumulate_into is not None:                          # y += result: the second data gradient of an input two layers consume
+    ldy = cs
+    if out is not None:
+        ldy = cl_row_stride(out)
+        if ldy is None or tuple(out.shape) != (B, X, Y, Z, cs) or out_dtype != torch.bfloat16 or accumulate_into is not None:
+            raise ValueError("conv3d: out must be a bf16 [B, X, Y, Z, cout_store] map, dense or a channel slice of a channels-last buffer")
+        y = out
+    elif accumulate_into is not None:                          # y += result: the second data gradient of an input two layers consume
         y = _chk(accumulate_into, "conv3d.accumulate_into")
         if tuple(y.shape) != (B, X, Y, Z, cs) or y.dtype != out_dtype:
             raise ValueError("conv3d: accumulate_into must have the output's shape and dtype")
@@ -707,13 +714,13 @@ def conv3d_fwd(x, w_packed, cout, ksize=3, bias=None, cout_store=None, out_dtype
     part, rows = None, 0
     if stats_eps is not None:
         # instance-norm statistics of the output as a by-product of the epilogue where the serving kernel has one, else one pass over y
-        if accumulate_into is not None or cs != cout or out_dtype != torch.bfloat16:
+        if accumulate_into is not None or out is not None or cs != cout or out_dtype != torch.bfloat16:
             raise ValueError("conv3d: statistics need a dense bf16 output without accumulation")
         rows = L.ucfvit_conv3d_fwd_stats_rows(B, X, Y, Z, cin, cout, ksize, 0 if bias is None else 1)
         if rows:
             buf = workspace((B * rows * 3 * cout + B * 256 * 3 * cout) * 4, x.device)       # partial rows (count, mean, M2), then the first fold stage's scratch
             part, fold_ws = buf, buf[B * rows * 3 * cout:]
-    _l.check(L.ucfvit_conv3d_fwd(x.data_ptr(), w_packed.data_ptr(), _p(bias), y.data_ptr(), B, X, Y, Z, cin, cout, ksize, cs, cs, dt(y),
+    _l.check(L.ucfvit_conv3d_fwd(x.data_ptr(), w_packed.data_ptr(), _p(bias), y.data_ptr(), B, X, Y, Z, cin, cout, ksize, ldy, cs, dt(y),
                                  0 if accumulate_into is None else 1, _p(part), _stream()), "ucfvit_conv3d_fwd")
     if stats_eps is None:
         return y
@@ -799,6 +806,48 @@ def space_to_depth2(y):
     cols = torch.empty((B * Xi * Yi * Zi, 8 * C), dtype=torch.bfloat16, device=y.device)
     _l.check(L.ucfvit_depth_to_space2(y.data_ptr(), cols.data_ptr(), B, Xi, Yi, Zi, C, ld, 0, None, 0, _stream()), "ucfvit_depth_to_space2")
     return cols
+
+
+def resample_trilinear(x, size, out=None, skip=None):
+    """align-corners trilinear resampling (nn.Upsample(size, mode='trilinear', align_corners=True)) of a dense channels-last bf16 map
+    x [B, Xi, Yi, Zi, C] (C % 8 == 0) -> [B, *size, C]; `out` may be a channel slice of a wider channels-last buffer; with `skip` (dense
+    [B, *size, Cs]) the buffer behind `out` must be C + Cs wide and receives the skip behind the C channels"""
+    L = _l.load()
+    _chk_cl(x, "resample_trilinear.x")
+    B, Xi, Yi, Zi, C = x.shape
+    Xo, Yo, Zo = (int(s) for s in size)
+    if C % 8:
+        raise ValueError(f"resample_trilinear: C must be a multiple of 8, got {C}")
+    if out is None:
+        out = torch.empty((B, Xo, Yo, Zo, C), dtype=torch.bfloat16, device=x.device)
+    ld = cl_row_stride(out)
+    if ld is None or tuple(out.shape) != (B, Xo, Yo, Zo, C):
+        raise ValueError("resample_trilinear: out must be [B, *size, C], dense or a channel slice of a dense channels-last buffer")
+    cs = 0
+    if skip is not None:
+        _chk_cl(skip, "resample_trilinear.skip")
+        cs = skip.shape[-1]
+        if tuple(skip.shape[:4]) != tuple(out.shape[:4]) or ld < C + cs:
+            raise ValueError("resample_trilinear: skip must cover the output's voxels and fit behind it in the buffer")
+    _l.check(L.ucfvit_resample_trilinear_fwd(x.data_ptr(), out.data_ptr(), B, Xi, Yi, Zi, Xo, Yo, Zo, C, ld, _p(skip), cs, _stream()),
+             "ucfvit_resample_trilinear_fwd")
+    return out
+
+
+def resample_trilinear_bwd(dy, in_size):
+    """gradient of resample_trilinear: dy [B, Xo, Yo, Zo, C] (dense or a channel slice of a dense channels-last buffer) -> dense
+    dx [B, *in_size, C]"""
+    L = _l.load()
+    ld = cl_row_stride(dy)
+    if ld is None:
+        dy = _chk_cl(dy.contiguous(), "resample_trilinear_bwd.dy")
+        ld = dy.shape[-1]
+    B, Xo, Yo, Zo, C = dy.shape
+    Xi, Yi, Zi = (int(s) for s in in_size)
+    dx = torch.empty((B, Xi, Yi, Zi, C), dtype=torch.bfloat16, device=dy.device)
+    _l.check(L.ucfvit_resample_trilinear_bwd(dy.data_ptr(), dx.data_ptr(), B, Xi, Yi, Zi, Xo, Yo, Zo, C, ld, _stream()),
+             "ucfvit_resample_trilinear_bwd")
+    return dx
 
 
 def pad_channels8(vol):

@@ -102,7 +102,8 @@ class UNETR(_TPMixin, _S.UNETR):
 
     With seq_par_size > 1 every rank embeds and encodes its contiguous shard of the token sequence: forward_intermediates returns the
     LOCAL shards [B, N / P, D] of the final features and of the taps.  The convolutional decoder then runs SHARDED as well
-    (shard_decoder=True, the default whenever the HIP decoder applies and the token grid's first axis divides by P): a token shard is an
+    (shard_decoder=True, the default whenever the HIP decoder applies, the token grid's first axis divides by P and the geometry does not
+    resample dec1 — the slab decoder has no resampling step, so patch-4 style geometries decode gathered): a token shard is an
     X-slab of the token grid, every rank decodes its slab of the volume with one-plane halo exchanges in front of the 3x3x3 layers and
     group-wide instance-norm statistics (fsdp/sharded_decoder.py), and forward() returns the LOCAL slab of the logits
     [B, classes, X / P, Y, Z] — pair it with sharded_decoder.sharded_dice_ce and sharded_decoder.local_slab(labels, ...).
@@ -197,11 +198,13 @@ class UNETR(_TPMixin, _S.UNETR):
         """True when forward() decodes only this rank's X-slab (see the class docstring)"""
         if self.seq_par_size <= 1:
             return False
-        can = self.hip_decoder() and len(self.feat_size) == 3 and self.feat_size[0] % self.seq_par_size == 0
+        can = (self.hip_decoder() and len(self.feat_size) == 3 and self.feat_size[0] % self.seq_par_size == 0
+               and not self.resamples_dec1())             # sharded_decoder.py has no resampling step: the gathered path (_unetr_head_cl) has
         if self._shard_decoder_arg is None:
             return can
         if self._shard_decoder_arg and not can:
-            raise ValueError("UNETR: shard_decoder=True needs the HIP decoder and a token grid whose first axis divides by seq_par_size")
+            raise ValueError("UNETR: shard_decoder=True needs the HIP decoder, a token grid whose first axis divides by seq_par_size and a "
+                             "geometry without the resampling of dec1 (token grid x 16 = img_size)")
         return bool(self._shard_decoder_arg)
 
     def _tokens_cl_local(self, t):

@@ -5,8 +5,7 @@ checkpoints interchange.  All token-path arithmetic (patch embedding, cls/pos as
 head, MAE masking/gather/unshuffle) runs on libucfvit_hip.so; nothing here falls back to PyTorch math.
 
 Round-1 scope: image input with adaptive_patching=False and use_varemb=False — what every BASELINE
-config uses.  The adaptive-patching and variable-aggregation front ends keep their parameters (checkpoint compatible)
-but raise NotImplementedError in forward (§8f "next" rows 1 and 4).
+config uses.
 """
 from functools import partial
 from typing import Callable, List, Optional, Tuple, Type, Union
@@ -437,9 +436,14 @@ class UNETR(VIT):
     (csrc/conv3d.hip, csrc/unetr_decoder.hip through unetr_blocks.forward_cl; layer semantics = monai's published blocks, parity unpinned).
     forward(x, variables, seq_ps=None, x_seq=None) -> [B, num_classes, *img_size]
 
+    Where the token grid times 16 is not the tile size (patch 4, adaptive patching with sqrt_len 9 on a 64^3 tile, ...) the reference
+    resamples dec1 to img_size (self.upsample: trilinear, align_corners=True) and decoder2's transposed convolution is pointwise; both
+    run on the HIP kernels too (csrc/resample.hip, unetr_blocks.UnetrUpBlock.forward_cl).
+
     ONE backend: a configuration the HIP decoder kernels do not cover (2-D, feature sizes other than 16 / 32 k, the pooling decoder
-    without skip connections, a patch size other than 16) raises in forward() unless the caller asked for torch's own convolutions
-    explicitly with the constructor argument allow_torch_decoder=True (an extension of the reference's signature; default False)."""
+    without skip connections) raises in forward() unless the caller asked for torch's own convolutions explicitly with the constructor
+    argument allow_torch_decoder=True (an extension of the reference's signature; default False).  That argument is a permission to fall
+    back, not a request: a covered configuration runs on the HIP kernels whether or not it is set."""
 
     def __init__(self, *args, **kwargs):
         self.linear_decoder = kwargs.pop('linear_decoder', '')
@@ -539,7 +543,11 @@ class UNETR(VIT):
         if self.force_torch_decoder or self.linear_decoder or not self.skip_connection:
             return False
         full = all(self.feat_size[i] * 16 == self.img_size[i] for i in range(len(self.feat_size)))
-        return full and hip_decoder_supported(2 if self.twoD else 3, self.in_chans, self.embed_dim, self.feature_size)
+        return (full or self.resamples_dec1()) and hip_decoder_supported(2 if self.twoD else 3, self.in_chans, self.embed_dim, self.feature_size)
+
+    def resamples_dec1(self):
+        """the reference's test (:989-991): dec1 is resampled to img_size and decoder2's transposed convolution is pointwise"""
+        return self.feat_size[0] * 16 != self.img_size[0]
 
     def _tokens_cl(self, t):
         """token matrix [B, N, D] -> channels-last feature map [B, *feat_size, D] in bf16: a view, no permute (the decoder kernels read a
@@ -551,7 +559,9 @@ class UNETR(VIT):
         dec3 = self.decoder5.forward_cl(self._tokens_cl(x), self.encoder4.forward_cl(self._tokens_cl(intermediates[n - 1])))
         dec2 = self.decoder4.forward_cl(dec3, self.encoder3.forward_cl(self._tokens_cl(intermediates[n - 2])))
         dec1 = self.decoder3.forward_cl(dec2, self.encoder2.forward_cl(self._tokens_cl(intermediates[n - 3])))
-        logits = self.out.forward_cl(self.decoder2.forward_cl(dec1, enc1))            # [B, X, Y, Z, classes] fp32
+        # self.upsample(dec1) of the reference: resampled to img_size inside decoder2, behind its pointwise transposed convolution
+        size = tuple(self.img_size) if self.resamples_dec1() else None
+        logits = self.out.forward_cl(self.decoder2.forward_cl(dec1, enc1, size))      # [B, X, Y, Z, classes] fp32
         return logits.permute(0, 4, 1, 2, 3)                                          # the reference's [B, classes, X, Y, Z] as a view
 
     def forward(self, x, variables, seq_ps=None, x_seq=None):
@@ -575,8 +585,8 @@ class UNETR(VIT):
     def _require_torch_decoder_opt_in(self):
         if not self.allow_torch_decoder:
             raise RuntimeError(
-                "UNETR: this configuration's convolutional decoder is not covered by the HIP convolution kernels (they need 3-D volumes, patch "
-                "size 16, the skip-connection decoder, feature_size 16 or a power-of-two multiple of 32, 1-8 input channels, an embed_dim of "
+                "UNETR: this configuration's convolutional decoder is not covered by the HIP convolution kernels (they need 3-D volumes, the "
+                "skip-connection decoder, feature_size 16 or a power-of-two multiple of 32, 1-8 input channels, an embed_dim of "
                 "8, 16 or a multiple of 32). Construct the model with allow_torch_decoder=True to run its convolutions on torch instead.")
 
 

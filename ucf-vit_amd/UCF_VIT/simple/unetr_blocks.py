@@ -6,9 +6,11 @@ and the reference ships no fixtures for it.
 
 Two execution paths over the SAME parameters (nn.Conv3d / nn.ConvTranspose3d modules are kept as the parameter containers):
   forward_cl(...)  the 3-D decoder on the HIP kernels end to end: channels-last bf16 activations [B, X, Y, Z, C],
-                   3x3x3 convolutions as implicit GEMMs on MFMA, transposed convolutions as GEMM + depth-to-space, instance norm + LeakyReLU
-                   (+ residual) fused, csrc/conv3d.hip + csrc/unetr_decoder.hip through UCF_VIT/_hip/conv.py.  UNETR uses it whenever
-                   hip_decoder_supported() holds (3-D, kernel 3 / stride 1 / upsample 2, channel counts the kernels tile).
+                   3x3x3 convolutions as implicit GEMMs on MFMA, transposed convolutions as GEMM + depth-to-space (kernel 2) or as a
+                   pointwise layer (kernel 1, followed by the align-corners trilinear resampling of csrc/resample.hip where the reference
+                   up-samples dec1), instance norm + LeakyReLU (+ residual) fused, csrc/conv3d.hip + csrc/unetr_decoder.hip +
+                   csrc/resample.hip through UCF_VIT/_hip/conv.py.  UNETR uses it whenever hip_decoder_supported() holds (3-D, kernel 3 /
+                   stride 1 / upsample 2, channel counts the kernels tile).
   forward(...)     N C (D) H W tensors: torch's own convolutions with the fused HIP instance-norm kernels between them — ONLY for models
                    built with UNETR(allow_torch_decoder=True) (2-D, unusual channel counts); without that opt-in UNETR.forward raises
                    instead of dropping to a second backend.
@@ -110,8 +112,21 @@ class UnetrUpBlock(nn.Module):
         out = self.transp_conv(inp.float())
         return self.conv_block(torch.cat((out, skip), dim=1))
 
-    def forward_cl(self, inp, skip):
-        return self.conv_block.forward_cl(HC.tconv2x2x2(inp, self.transp_conv.conv.weight, skip))      # (up-sampled, skip) concatenated in place
+    def forward_cl(self, inp, skip, size=None):
+        """size (upsample_kernel_size 1 only): the extent the reference's nn.Upsample(align_corners=True) resamples the input to before this
+        block; the resampling then runs behind the pointwise transposed convolution (_hip/conv.py:tconv1x1x1_resample)"""
+        w = self.transp_conv.conv.weight
+        k = tuple(w.shape[2:])
+        if k == (2, 2, 2) and size is None:
+            cat = HC.tconv2x2x2(inp, w, skip)                                   # (up-sampled, skip) concatenated in place
+        elif k == (1, 1, 1):
+            if size is None or tuple(size) == tuple(inp.shape[1:4]):
+                cat = HC.tconv1x1x1(inp, w, skip)
+            else:
+                cat = HC.tconv1x1x1_resample(inp, w, size, skip)                 # (resampled, skip) concatenated in place
+        else:
+            raise ValueError(f"UnetrUpBlock.forward_cl: transposed convolution kernel {k} (with resampling to {size}) is not on the HIP path")
+        return self.conv_block.forward_cl(cat)
 
 
 class UnetOutBlock(nn.Module):

@@ -2,8 +2,11 @@
 """UNETR segmentation training — entry point compatible with the reference's training_scripts/train_unetr_simple.py.
 The ViT encoder, the convolutional decoder (3x3x3 / transposed / 1x1x1 convolutions on csrc/conv3d.hip, channels-last instance-norm /
 LeakyReLU / residual chains on csrc/unetr_decoder.hip) and the Dice+CE loss (monai DiceCELoss(to_onehot_y, softmax, squared_pred) in the
-reference, :38; parity unpinned: monai is not vendored) all run on the HIP kernels.  A configuration those kernels do not cover (2-D,
-feature sizes other than 16 / 32 k, ...) needs `allow_torch_decoder: True` in model.net.init_args, else UNETR.forward raises."""
+reference, :38; parity unpinned: monai is not vendored) all run on the HIP kernels — the reference's basic_ct/unetr key set (64^3 tile,
+patch 4, adaptive patching with fixed_length 729) included: its 9^3 token grid times 16 is not the tile size, so dec1 is resampled to the
+tile (csrc/resample.hip) in front of decoder2's pointwise transposed convolution, and the config runs as it is, without extra keys.  A
+configuration those kernels do not cover (2-D, feature sizes other than 16 / 32 k, ...) needs `allow_torch_decoder: True` in
+model.net.init_args, else UNETR.forward raises."""
 import sys
 
 import torch
