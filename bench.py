@@ -2,11 +2,17 @@
 """Benchmark of the ViT training hot path on MI355X (contract: see the task statement / DESIGN.md §Measurement).
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full   (+ the measurements the headline figure does not need, see below)
     python bench.py --gpus N ...                      (starts N ranks itself, one per GPU, over RCCL)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One "step" = forward + loss + backward (+ data-parallel gradient all-reduce) + fused AdamW + zero_grad + scheduler step on one
 synthetic batch that is already resident in HBM.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line; its `roofline` comes from HIP events recorded
+around the launches of the timed steps themselves, so it costs no run of its own.  --full adds what does: the MFMA clock probe after the
+timed steps (`roofline.mfma_stream_measured`, `frac_of_mfma_stream`; bf16, rank 0) and the CPU oracle leg (`cpu_baseline`, N = 1 only,
+unless --no-cpu-baseline), which takes tens of seconds of host time.
 
 workloads (BASELINE.json configs):
   vit_l16_224            headline: ViT-L/16 224^2 classification step (train_class_simple.py:344-357), configs[2]
@@ -22,7 +28,7 @@ workloads (BASELINE.json configs):
 roofline: the dominant kernel family of the workload — the bf16 MFMA GEMM (gemm3_kernel in csrc/gemm2.hip and its staggered form gemm5_kernel in csrc/gemm_stagger.hip) for the 224^2 workloads, the
           streaming attention kernels (csrc/attention.hip) for the 8192-token encoder; `achieved` = algorithmic FLOPs of that family's
           launches in the timed region / their HIP-event-measured durations (events recorded on the launch stream).
-cpu_baseline: the CPU oracle's training loop (oracle/ucf_vit_ref.py, kind "port") on this box's host cores, rank 0, N=1 only.
+cpu_baseline: the CPU oracle's training loop (oracle/ucf_vit_ref.py, kind "port") on this box's host cores, rank 0, N=1 only, --full only.
 """
 import argparse
 import hashlib
@@ -587,8 +593,10 @@ def main():
     ap.add_argument("--workload", default="vit_l16_224", choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (default: workload default)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-steps", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements the headline figure does not need: the MFMA clock probe and the CPU oracle baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU oracle baseline")
+    ap.add_argument("--cpu-steps", type=int, default=5, help="with --full: timed steps of the CPU oracle baseline")
     # BASELINE config 5 ("hybrid-op sequence-parallel across 8 GPUs"): --gpus N = dp x sp (or dp x tp) ranks laid out like the reference's
     # init_par_groups (utils/misc.py:129-238): rank = dp_index * (tp * sp) + sp_index * tp + tp_index.  UNETR workloads only.
     ap.add_argument("--sp", type=int, default=1, help="sequence-parallel group size (UNETR workloads; the token sequence is sharded)")
@@ -690,10 +698,10 @@ def main():
         keep = None
         log(f"outputs of the last timed step written to {args.dump_outputs}: {', '.join(names)} ({nbytes / 2**20:.1f} MB)")
 
-    # measured MFMA ceiling of THIS device (outside the timed region): a pure bf16 MFMA stream, ~0.3 s so the clock settles the way
+    # --full: measured MFMA ceiling of THIS device (outside the timed region): a pure bf16 MFMA stream, ~0.3 s so the clock settles the way
     # it does inside the step (the chip lowers its clock under matrix load; the nominal 2.5 PFLOP/s assumes 2.4 GHz)
     mfma_stream = None
-    if rank == 0 and args.dtype == "bf16":
+    if args.full and rank == 0 and args.dtype == "bf16":
         from UCF_VIT._hip import ops as _ops
         for _ in range(20):
             _ops.mfma_probe()
@@ -760,7 +768,7 @@ def main():
             # context, not the contract's `peak`: what a register-only MFMA loop sustains on this device under its power management
             res["roofline"]["mfma_stream_measured"] = round(mfma_stream, 1)
             res["roofline"]["frac_of_mfma_stream"] = round(d["tflops"] / mfma_stream, 4)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb = cpu_baseline(args.workload, w, steps=args.cpu_steps)
             if cb is not None:
                 res["cpu_baseline"] = cb

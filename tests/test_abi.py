@@ -56,7 +56,7 @@ def test_error_reporting_without_gpu():
 
 
 def test_committed_bench_line_has_the_contract_keys():
-    """the newest committed bench line of the headline workload (profiles/r*_bench_vitl16_b<batch>.json, written by `python bench.py` on an MI355X)
+    """the newest committed bench line of the headline workload (profiles/r*_bench_vitl16_b<batch>.json, written by `python bench.py --full` on an MI355X)
     carries every key of the driver's contract plus the roofline / cpu_baseline objects, with consistent arithmetic; from round 2 on its
     roofline.traffic is a measured number (a PMC profile of the same source hash was in the tree when the line was produced)"""
     import glob

@@ -77,15 +77,28 @@ def test_bench_dump_outputs_of_the_last_timed_step(tmp_path):
     assert abs(float(z["loss"][0]) - d["config"]["final_loss"]) < 1e-3
 
 
+def test_bench_full_adds_the_clock_probe_and_cpu_baseline():
+    """a plain run prints the line without the measurements that take runs of their own; --full adds the MFMA clock probe and the
+    CPU oracle leg to the same line"""
+    args = ["--steps", "2", "--warmup", "1", "--workload", "vit_tiny16_256", "--batch", "32"]
+    d = _bench(args)
+    _check(d, 1, "images/sec")
+    assert "cpu_baseline" not in d and "mfma_stream_measured" not in d["roofline"] and "frac_of_mfma_stream" not in d["roofline"]
+    d = _bench(args + ["--full", "--cpu-steps", "1"])
+    _check(d, 1, "images/sec")
+    assert d["roofline"]["mfma_stream_measured"] > 0 and d["roofline"]["frac_of_mfma_stream"] > 0
+    assert d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["unit"] == "images/sec" and d["cpu_baseline"]["value"] > 0
+
+
 def test_bench_mae_workload_line():
-    d = _bench(["--steps", "2", "--warmup", "1", "--workload", "mae_vit_l16_224", "--batch", "64", "--cpu-steps", "1"])
+    d = _bench(["--steps", "2", "--warmup", "1", "--workload", "mae_vit_l16_224", "--batch", "64", "--full", "--cpu-steps", "1"])
     _check(d, 1, "images/sec")
     assert "MAE" in d["config"]["workload"] and "gemm3_kernel" in d["roofline"]["kernel"]
     assert d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["unit"] == "images/sec"
 
 
 def test_bench_unetr_volume_workload_line():
-    d = _bench(["--steps", "2", "--warmup", "1", "--workload", "unetr_enc_512x512x128", "--batch", "1", "--cpu-steps", "1"])
+    d = _bench(["--steps", "2", "--warmup", "1", "--workload", "unetr_enc_512x512x128", "--batch", "1", "--full", "--cpu-steps", "1"])
     _check(d, 1, "volumes/sec")
     assert "attention" in d["roofline"]["kernel"] or "gemm3_kernel" in d["roofline"]["kernel"]
     assert d["roofline"]["other_family"]["launches"] > 0

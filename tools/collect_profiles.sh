@@ -23,6 +23,6 @@ for WL in $WLS; do
 done
 # the un-profiled bench lines of the same build, same box
 for WL in $WLS; do
-  timeout -k 10 400 python3 $B --workload $WL > $OUT/bench_$WL.json 2>> $OUT/log.txt
+  timeout -k 10 400 python3 $B --workload $WL --full > $OUT/bench_$WL.json 2>> $OUT/log.txt
 done
 ls -R $OUT | head -60

@@ -30,7 +30,7 @@ done
   /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -Wno-unused-result tools/dma_rate.hip -o /tmp/dma_rate 2>/dev/null
   for r in 32 128 512; do timeout -k 10 120 /tmp/dma_rate $r; echo; done
 } > $OUT/dma_rate.txt
-timeout -k 10 300 python bench.py --batch 166 --no-cpu-baseline > $OUT/bench_vitl16_b166.json 2>/dev/null
-timeout -k 10 300 python bench.py --workload unetr_enc_512x512x128 > $OUT/bench_unetr_enc_b2.json 2>/dev/null
-timeout -k 10 300 python bench.py --workload vit_l16_adaptive196 --no-cpu-baseline > $OUT/bench_vitl16_adaptive196_b665.json 2>/dev/null
+timeout -k 10 300 python bench.py --batch 166 --full --no-cpu-baseline > $OUT/bench_vitl16_b166.json 2>/dev/null
+timeout -k 10 300 python bench.py --workload unetr_enc_512x512x128 --full > $OUT/bench_unetr_enc_b2.json 2>/dev/null
+timeout -k 10 300 python bench.py --workload vit_l16_adaptive196 --full --no-cpu-baseline > $OUT/bench_vitl16_adaptive196_b665.json 2>/dev/null
 ls -la $OUT
