@@ -347,3 +347,58 @@ def test_unetr_sequence_parallel_under_data_parallel_steps_like_the_unsharded_mo
     for rank, bad, same in res:
         assert not bad, f"rank {rank}: {bad}"
         assert same, "ranks diverged after the step"
+
+
+def _sharded_stats_worker(rank, world, port, q):
+    for p in (os.path.join(ROOT, "ucf-vit_amd"), ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests", "golden")):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        from UCF_VIT._hip import ops
+        from UCF_VIT.fsdp import sharded_decoder as SD
+        from UCF_VIT.fsdp.seq_parallel import _PlainGroup
+        spg = _PlainGroup(dist.group.WORLD)
+        g = torch.Generator(device="cuda:0").manual_seed(4)
+        # a volume whose channels have |mean| / sigma ~1300: bf16 steps are 8 wide at 1024, so 1024 + 8 with p = 1 % (sigma ~0.8); the two
+        # slabs get different means (the second one 8 higher in channels 8..15) so that the fold's between-slab term matters too
+        x = 1024.0 + 8.0 * (torch.rand(2, 16, 32, 16, 16, device="cuda:0", generator=g) < 0.01).float()
+        x[:, 8:, 16:] += 8.0
+        x = x.permute(0, 2, 3, 4, 1).contiguous().bfloat16()          # channels-last [B, X, Y, Z, C]
+        m_ref, r_ref = ops.instnorm_cl_stats(x, 1e-5)                    # single rank, whole volume
+        xl = SD.local_slab(x, spg, 1).contiguous()
+        mean, rstd = SD.sharded_instnorm_stats(xl, 1e-5, spg)
+        ref64 = x.double().reshape(2, -1, 16)
+        sd = ref64.var(1, unbiased=False).sqrt()
+        bad = []
+        if float((rstd.double() / r_ref.double() - 1).abs().max()) >= 1e-3:
+            bad.append(f"rstd {float((rstd.double() / r_ref.double() - 1).abs().max()):.2e}")
+        if float(((mean.double() - m_ref.double()).abs() / sd).max()) >= 1e-3:
+            bad.append("mean")
+        y = SD.sharded_instnorm_act(xl, None, 1e-5, 1.0, spg)
+        yr = SD.local_slab(ops.instnorm_cl_apply(x, m_ref, r_ref, None, 1.0), spg, 1)
+        if float((y.float() - yr.float()).abs().max()) >= 0.15:            # two bf16 steps (1 / 16) of values up to ~10 sigma
+            bad.append("y")
+        q.put((rank, bad))
+        dist.barrier()
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.gpu
+def test_sharded_instance_norm_statistics_keep_their_variance_when_the_mean_is_large():
+    """ShardedInstNormActFn's group-wide statistics (2 gloo ranks on the one GPU) against single-rank ucfvit_instnorm_cl_stats of the whole
+    volume on channels whose |mean| is ~1300 standard deviations: averaging E[x^2] over the ranks and subtracting mean^2 in fp32 loses the
+    variance there; the parallel-variance fold keeps it"""
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    procs = [ctx.Process(target=_sharded_stats_worker, args=(r, 2, 29597, q)) for r in range(2)]
+    for p in procs:
+        p.start()
+    res = [q.get(timeout=240) for _ in range(2)]
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    for rank, bad in res:
+        assert not bad, f"rank {rank}: {bad}"

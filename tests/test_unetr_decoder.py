@@ -114,3 +114,38 @@ def test_instance_norm_properties_at_volume_size():
     dy = torch.full_like(x, 2.0)
     dx, dres = ops.instnorm_bwd(dy, yl, x, mean, rstd, 0.01, True)
     assert torch.equal(dres, torch.where(yl > 0, dy, dy * 0.01))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", ["outlier_first", "large_mean"])
+def test_instance_norm_statistics_at_the_value_range_edges(case):
+    """statistics of ops.instnorm_fwd (row layout, fp32 and bf16) and ops.instnorm_cl_stats (channels-last bf16) against fp64 on rows whose
+    FIRST element lies ~300 sigma from the rest (a shift by that element alone leaves E[d^2] - E[d]^2 to cancel in fp32), and on rows with
+    |mean| / sigma >= 1000.  Bound: rstd within 1e-3 (what a bf16 output can tell apart), mean within 1e-3 sigma."""
+    from UCF_VIT._hip import ops
+    g = torch.Generator(device=DEV).manual_seed(3)
+    S, C = 1 << 20, 16
+    if case == "outlier_first":
+        x = torch.randn(2, C, S, device=DEV, generator=g)
+        x[:, :, 0] = 300.0
+    else:
+        # bf16 steps are 8 wide at 1024: a sparse two-level row (1024, 1032 with p = 1 %) has sigma ~0.8 and |mean| / sigma ~1300
+        x = 1024.0 + 8.0 * (torch.rand(2, C, S, device=DEV, generator=g) < 0.01).float()
+    for dt in (torch.float32, torch.bfloat16):
+        xd = x.to(dt)
+        if case == "large_mean" and dt == torch.float32:
+            xd = 1100.0 + torch.randn(2, C, S, device=DEV, generator=g)
+        ref = xd.double()
+        m_ref, v_ref = ref.mean(-1), ref.var(-1, unbiased=False)
+        if case == "large_mean":
+            assert float((m_ref.abs() / v_ref.sqrt()).min()) > 1000
+        else:
+            assert float(((ref[..., 0] - m_ref).abs() / v_ref.sqrt()).min()) > 250
+        r_ref = (v_ref + 1e-5).rsqrt()
+        _, mean, rstd = ops.instnorm_fwd(xd.view(2, C, 1024, S // 1024), None, 1e-5, 1.0)
+        assert float((rstd.double().view(2, C) / r_ref - 1).abs().max()) < 1e-3, dt
+        assert float(((mean.double().view(2, C) - m_ref).abs() / v_ref.sqrt()).max()) < 1e-3, dt
+        if dt == torch.bfloat16:
+            mc, rc = ops.instnorm_cl_stats(xd.permute(0, 2, 1).contiguous().view(2, 64, 128, 128, C), 1e-5)
+            assert float((rc.double() / r_ref - 1).abs().max()) < 1e-3
+            assert float(((mc.double() - m_ref).abs() / v_ref.sqrt()).max()) < 1e-3

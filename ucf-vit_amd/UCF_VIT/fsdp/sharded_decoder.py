@@ -13,8 +13,8 @@ stage up-samples by 2 per axis: rank r owns the slab x in [r X / P, (r + 1) X / 
     and is sent back and added there (the reverse exchange).  Per rank and 3x3x3 layer: 2 x B x Y x Z x C x 2 bytes each way — at
     512 x 512 x 128 / 16 channels 2 x 2.1 MB, forward and backward (DESIGN.md §7 lists every layer).
   * instance norm: the statistics run over the whole volume.  Slabs are equal, so the global mean / variance follow from the ranks'
-    (mean, variance) by one all-reduce of 2 floats per (sample, channel); the backward pass needs the two global means of dy' and
-    dy' xhat the same way (ucfvit_instnorm_cl_bwd_sums / _bwd_apply).
+    (mean, variance) by two all-reduces of 1 double per (sample, channel) (sharded_instnorm_stats); the backward pass needs the two
+    global means of dy' and dy' xhat the same way (ucfvit_instnorm_cl_bwd_sums / _bwd_apply).
   * Dice + CE: a function of per-(sample, class) sums over voxels: one all-reduce of B x 25 floats (ucfvit_dice_ce_stats / _from_stats).
 
 Parameter gradients of a sharded layer are partial sums over the rank's slab.  ShardedDiceCEFn multiplies the gradient it starts
@@ -69,7 +69,7 @@ def _exchange(send_lo, send_hi, spg):
 
 
 def _mean_over_group(t, spg):
-    """in-place mean of a small fp32 tensor over the group"""
+    """in-place mean of a small fp32 / fp64 tensor over the group"""
     g = spg.sp_group
     if t.is_cuda and _host_staged(g):
         h = t.detach().cpu()
@@ -136,17 +136,25 @@ def _interior(y):
     return v if v.is_contiguous() else v.contiguous()
 
 
+def sharded_instnorm_stats(x, eps, spg):
+    """(mean, rstd) [B, C] of the WHOLE volume from this rank's slab x.  Slabs are equal, so the volume's mean is the average of the slabs'
+    means, and its biased variance the average of var_r + (mean_r - mean)^2 (the parallel-variance formula).  Both all-reduces run in
+    float64: forming E[x^2] - mean^2 instead would cancel every bit of the variance of a channel whose |mean| is far above its spread."""
+    mean_l, rstd_l = ops.instnorm_cl_stats(x, eps)
+    mean_l = mean_l.double()
+    var_l = rstd_l.double().pow(-2) - eps                     # the slab's biased variance
+    mean = _mean_over_group(mean_l.clone(), spg)
+    var = _mean_over_group(var_l + (mean_l - mean) ** 2, spg)
+    rstd = var.clamp_min(0.0).add(eps).rsqrt()
+    return mean.float().contiguous(), rstd.float().contiguous()
+
+
 class ShardedInstNormActFn(torch.autograd.Function):
     """y = lrelu(instance_norm(x) [+ res], slope) with the statistics of the WHOLE volume (x is this rank's slab)"""
 
     @staticmethod
     def forward(ctx, x, res, eps, slope, spg):
-        mean_l, rstd_l = ops.instnorm_cl_stats(x, eps)
-        var_l = rstd_l.pow(-2) - eps                          # the slab's biased variance
-        st = torch.stack((mean_l, var_l + mean_l * mean_l))   # equal slabs: E[x], E[x^2] of the volume = the averages over the ranks
-        _mean_over_group(st, spg)
-        mean = st[0].contiguous()
-        rstd = (st[1] - mean * mean).clamp_min_(0.0).add_(eps).rsqrt_().contiguous()
+        mean, rstd = sharded_instnorm_stats(x, eps, spg)
         y = ops.instnorm_cl_apply(x, mean, rstd, res, slope)
         ctx.save_for_backward(x, y, mean, rstd)
         ctx.slope, ctx.has_res, ctx.spg = slope, res is not None, spg

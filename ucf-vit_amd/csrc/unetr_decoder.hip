@@ -33,14 +33,16 @@ __device__ __forceinline__ float block_sum(float v, float* red) {       // red: 
 template <typename T> __device__ __forceinline__ float ld(const T* p, int64_t i) { return to_f32<T>(p[i]); }
 
 // ---- instance-norm statistics: per row mean and 1 / sqrt(var + eps) (biased variance, like nn.InstanceNorm) ---------------------------
-// pass 1: partial sums of (x - shift) and (x - shift)^2 per chunk, shift = the row's first element (keeps E[x^2] - mean^2 well conditioned)
+// pass 1: per chunk the COUNT, MEAN and M2 = sum (x - mean)^2 of its elements, accumulated relative to a per-chunk shift (the chunk's
+// first element).  A shift that is far from the rest of the row (one outlier at the start) spoils the fp32 sums of that chunk only; pass 2
+// combines the chunks with the parallel-variance formula in double, so a row whose |mean| is far larger than its spread keeps its variance.
 template <typename T>
 __global__ __launch_bounds__(NT) void in_stats_partial(const T* __restrict__ x, float* __restrict__ part, int64_t S, int chunks) {
     __shared__ float red[NT / 64];
     const int64_t row = blockIdx.y;
     const T* xr = x + row * S;
-    const float shift = ld(xr, 0);
     const int64_t lo = (int64_t)blockIdx.x * CHUNK, hi = min(S, lo + CHUNK);
+    const float shift = ld(xr, lo);
     float s1 = 0.f, s2 = 0.f;
     for (int64_t i = lo + threadIdx.x; i < hi; i += NT) {
         const float v = ld(xr, i) - shift;
@@ -50,29 +52,52 @@ __global__ __launch_bounds__(NT) void in_stats_partial(const T* __restrict__ x, 
     s1 = block_sum(s1, red);
     s2 = block_sum(s2, red);
     if (threadIdx.x == 0) {
-        part[(row * chunks + blockIdx.x) * 2 + 0] = s1;
-        part[(row * chunks + blockIdx.x) * 2 + 1] = s2;
+        const float n = (float)(hi - lo);
+        float* p = part + (row * chunks + blockIdx.x) * 3;
+        p[0] = n;
+        p[1] = shift + s1 / n;
+        p[2] = fmaxf(s2 - s1 * (s1 / n), 0.f);
     }
 }
-// pass 2: one wave per row folds the chunk sums in a fixed order (double accumulation: 2048 chunks of 16384 at the full volume)
-template <typename T>
-__global__ __launch_bounds__(64) void in_stats_final(const T* __restrict__ x, const float* __restrict__ part, float* __restrict__ mean,
-                                                     float* __restrict__ rstd, int64_t S, int chunks, float eps) {
-    const int64_t row = blockIdx.x;
-    double s1 = 0.0, s2 = 0.0;
-    for (int c = threadIdx.x; c < chunks; c += 64) {
-        s1 += part[(row * chunks + c) * 2 + 0];
-        s2 += part[(row * chunks + c) * 2 + 1];
-    }
+
+// parallel-variance combination of (count, mean, M2) triples in double: n = na + nb, d = mb - ma, m = ma + d nb / n,
+// M2 = M2a + M2b + d^2 na nb / n.  Triples with count 0 drop out.
+struct Mom {
+    double n, m, m2;
+};
+__device__ __forceinline__ void mom_add(Mom& a, double nb, double mb, double m2b) {
+    if (nb <= 0.0) return;
+    const double n = a.n + nb, d = mb - a.m;
+    a.m += d * (nb / n);
+    a.m2 += m2b + d * d * (a.n * nb / n);
+    a.n = n;
+}
+// one wave: lane l has combined its share of the triples in `a`; butterfly so that every lane ends with the same combination order
+__device__ __forceinline__ Mom mom_wave_fold(Mom a) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
-        s1 += __shfl_xor(s1, o, 64);
-        s2 += __shfl_xor(s2, o, 64);
+        const double nb = __shfl_xor(a.n, o, 64), mb = __shfl_xor(a.m, o, 64), m2b = __shfl_xor(a.m2, o, 64);
+        const bool lower = (threadIdx.x & o) == 0;              // combine (lower, upper) in that order on both sides
+        Mom lo = lower ? a : Mom{nb, mb, m2b};
+        if (lower) mom_add(lo, nb, mb, m2b); else mom_add(lo, a.n, a.m, a.m2);
+        a = lo;
     }
+    return a;
+}
+
+// pass 2: one wave per row folds the chunk triples in a fixed order (2048 chunks of 16384 at the full volume)
+__global__ __launch_bounds__(64) void in_stats_final(const float* __restrict__ part, float* __restrict__ mean, float* __restrict__ rstd, int chunks,
+                                                     float eps) {
+    const int64_t row = blockIdx.x;
+    Mom a = {0.0, 0.0, 0.0};
+    for (int c = threadIdx.x; c < chunks; c += 64) {
+        const float* p = part + (row * chunks + c) * 3;
+        mom_add(a, (double)p[0], (double)p[1], (double)p[2]);
+    }
+    a = mom_wave_fold(a);
     if (threadIdx.x == 0) {
-        const double m = s1 / (double)S;
-        const double var = fmax(s2 / (double)S - m * m, 0.0);
-        mean[row] = (float)(m + (double)ld(x + row * S, 0));
+        const double var = a.n > 0.0 ? fmax(a.m2 / a.n, 0.0) : 0.0;
+        mean[row] = (float)a.m;
         rstd[row] = (float)(1.0 / sqrt(var + (double)eps));
     }
 }
@@ -314,13 +339,15 @@ __device__ __forceinline__ void cl_fold(const float (&s1)[8], const float (&s2)[
     }
 }
 
+// per chunk and channel (count, mean, M2) relative to the chunk's first voxel -> rows [B][chunks][3][C] in the layout of the convolution
+// epilogue's statistics (conv3d.hip: stats_row_write), folded by ucfvit_instnorm_cl_stats_fold
 __global__ __launch_bounds__(NT) void incl_stats_partial(const bf16* __restrict__ x, float* __restrict__ part, int64_t S, int C, int chunks) {
     __shared__ float red[NT][17];
     const int64_t b = blockIdx.y;
     const int cv = C >> 3;
     const int64_t nvec = S * cv, vlo = (int64_t)blockIdx.x * CLV, vhi = min(nvec, vlo + CLV);
     const bf16x8* xb = reinterpret_cast<const bf16x8*>(x + b * S * C);
-    const bf16x8 sh = xb[threadIdx.x % cv];                         // shift = the first voxel (keeps E[x^2] - mean^2 well conditioned)
+    const bf16x8 sh = xb[vlo + threadIdx.x % cv];                   // shift = the chunk's first voxel (vlo is a multiple of cv)
     float s1[8], s2[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) s1[e] = s2[e] = 0.f;
@@ -333,42 +360,29 @@ __global__ __launch_bounds__(NT) void incl_stats_partial(const bf16* __restrict_
             s2[e] += d * d;
         }
     }
-    cl_fold(s1, s2, red, part + (b * chunks + blockIdx.x) * 2 * C, C, cv);
-}
-__global__ __launch_bounds__(64) void incl_stats_final(const bf16* __restrict__ x, const float* __restrict__ part, float* __restrict__ mean,
-                                                       float* __restrict__ rstd, int64_t S, int C, int chunks, float eps) {
-    const int64_t b = blockIdx.x / C;
-    const int c = blockIdx.x % C;
-    double s1 = 0.0, s2 = 0.0;
-    for (int ch = threadIdx.x; ch < chunks; ch += 64) {
-        s1 += part[(b * chunks + ch) * 2 * C + c];
-        s2 += part[(b * chunks + ch) * 2 * C + C + c];
-    }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        s1 += __shfl_xor(s1, o, 64);
-        s2 += __shfl_xor(s2, o, 64);
+    for (int e = 0; e < 8; ++e) {
+        red[threadIdx.x][e] = s1[e];
+        red[threadIdx.x][8 + e] = s2[e];
     }
-    if (threadIdx.x == 0) {
-        const double m = s1 / (double)S;
-        const double var = fmax(s2 / (double)S - m * m, 0.0);
-        mean[blockIdx.x] = (float)(m + (double)(float)x[b * S * C + c]);
-        rstd[blockIdx.x] = (float)(1.0 / sqrt(var + (double)eps));
+    __syncthreads();
+    const float n = (float)((vhi - vlo) / cv);                      // voxels of the chunk
+    float* out = part + (b * chunks + blockIdx.x) * 3 * C;
+    for (int c = threadIdx.x; c < C; c += NT) {
+        const int cg = c >> 3, e = c & 7;
+        float a1 = 0.f, a2 = 0.f;
+        for (int t = cg; t < NT; t += cv) {
+            a1 += red[t][e];
+            a2 += red[t][8 + e];
+        }
+        out[c] = n;
+        out[C + c] = (float)x[(b * S + vlo / cv) * C + c] + a1 / n;
+        out[2 * C + c] = fmaxf(a2 - a1 * (a1 / n), 0.f);
     }
 }
 // ---- fold of the convolution kernels' statistics epilogue: partial rows [B][rows][3][C] of (count, mean, M2) per channel (conv3d.hip:
 // stats_row_write) combined with the parallel-variance formula in double: n = na + nb, d = mb - ma, m = ma + d nb / n,
 // M2 = M2a + M2b + d^2 na nb / n.  Rows that stored nothing carry count 0 and drop out.
-struct Mom {
-    double n, m, m2;
-};
-__device__ __forceinline__ void mom_add(Mom& a, double nb, double mb, double m2b) {
-    if (nb <= 0.0) return;
-    const double n = a.n + nb, d = mb - a.m;
-    a.m += d * (nb / n);
-    a.m2 += m2b + d * d * (a.n * nb / n);
-    a.n = n;
-}
 // first stage when there are many partial rows (a full-resolution layer writes 32768 per batch element): workgroup (g, b) combines the rows
 // [g rpg, (g + 1) rpg) -> [B][G][3][C]; a thread owns a channel, NT / C rows in flight, the threads of a channel are combined in a fixed order
 __global__ __launch_bounds__(NT) void incl_stats_fold1(const float* __restrict__ part, float* __restrict__ out, int rows, int C, int rpg) {
@@ -688,7 +702,7 @@ unsigned apply_grid(int64_t S, int64_t rows) {
 
 }  // namespace
 
-extern "C" int64_t ucfvit_instnorm_workspace(int64_t rows, int64_t S) { return (rows * chunks_of(S) * 2 + 2 * rows) * (int64_t)sizeof(float); }
+extern "C" int64_t ucfvit_instnorm_workspace(int64_t rows, int64_t S) { return (rows * chunks_of(S) * 3 + 2 * rows) * (int64_t)sizeof(float); }
 
 #define IN_DISPATCH(T_, ...)                         \
     do {                                             \
@@ -718,7 +732,7 @@ extern "C" int ucfvit_instnorm_fwd(const void* x, const void* res, void* y, floa
     float* part = (float*)workspace;
     IN_DISPATCH(T, {
         hipLaunchKernelGGL((in_stats_partial<T>), dim3(ch, (unsigned)rows), dim3(NT), 0, s, (const T*)x, part, S, ch);
-        hipLaunchKernelGGL((in_stats_final<T>), dim3((unsigned)rows), dim3(64), 0, s, (const T*)x, part, mean, rstd, S, ch, eps);
+        hipLaunchKernelGGL(in_stats_final, dim3((unsigned)rows), dim3(64), 0, s, part, mean, rstd, ch, eps);
         const dim3 g(apply_grid(S, rows), (unsigned)rows);
         if (res)
             hipLaunchKernelGGL((in_apply<T, true>), g, dim3(NT), 0, s, (const T*)x, mean, rstd, (const T*)res, (T*)y, S, slope);
@@ -839,7 +853,7 @@ static int incl_check(const char* name, const void* x, int64_t B, int64_t S, int
     return UCFVIT_OK;
 }
 extern "C" int64_t ucfvit_instnorm_cl_workspace(int64_t B, int64_t S, int64_t C) {
-    return (B * cl_chunks_of(S, C) * 2 * C + 2 * B * C) * (int64_t)sizeof(float);
+    return (B * cl_chunks_of(S, C) * 3 * C + B * 256 * 3 * C + 2 * B * C) * (int64_t)sizeof(float);    // statistics rows, then the fold's scratch
 }
 extern "C" int ucfvit_instnorm_cl_fwd(const void* x, const void* res, void* y, float* mean, float* rstd, int64_t B, int64_t S, int64_t C,
                                       float eps, float slope, void* workspace, void* stream) {
@@ -849,7 +863,7 @@ extern "C" int ucfvit_instnorm_cl_fwd(const void* x, const void* res, void* y, f
     const int ch = cl_chunks_of(S, C);
     float* part = (float*)workspace;
     hipLaunchKernelGGL(incl_stats_partial, dim3(ch, (unsigned)B), dim3(NT), 0, s, (const bf16*)x, part, S, (int)C, ch);
-    hipLaunchKernelGGL(incl_stats_final, dim3((unsigned)(B * C)), dim3(64), 0, s, (const bf16*)x, part, mean, rstd, S, (int)C, ch, eps);
+    if (int rc = ucfvit_instnorm_cl_stats_fold(part, mean, rstd, B, S, C, ch, eps, part + B * ch * 3 * C, s)) return rc;
     const dim3 g(cl_apply_grid(S, C, B), (unsigned)B);
     if (res)
         hipLaunchKernelGGL((incl_apply<true>), g, dim3(NT), 0, s, (const bf16*)x, mean, rstd, (const bf16*)res, (bf16*)y, S, (int)C, slope);
@@ -947,7 +961,7 @@ extern "C" int ucfvit_instnorm_cl_stats(const void* x, float* mean, float* rstd,
     const int ch = cl_chunks_of(S, C);
     float* part = (float*)workspace;
     hipLaunchKernelGGL(incl_stats_partial, dim3(ch, (unsigned)B), dim3(NT), 0, s, (const bf16*)x, part, S, (int)C, ch);
-    hipLaunchKernelGGL(incl_stats_final, dim3((unsigned)(B * C)), dim3(64), 0, s, (const bf16*)x, part, mean, rstd, S, (int)C, ch, eps);
+    if (int rc = ucfvit_instnorm_cl_stats_fold(part, mean, rstd, B, S, C, ch, eps, part + B * ch * 3 * C, s)) return rc;
     UCF_LAUNCH_CHECK("ucfvit_instnorm_cl_stats");
     return UCFVIT_OK;
 }
