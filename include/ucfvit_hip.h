@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define UCFVIT_ABI_VERSION 13
+#define UCFVIT_ABI_VERSION 14
 
 #define UCFVIT_OK 0
 #define UCFVIT_ERR_INVALID_ARGUMENT (-1)
@@ -349,23 +349,19 @@ int ucfvit_instnorm_bwd(const void* dy, const void* y, const void* x, const floa
                         int64_t S, float slope, void* workspace, int dtype, void* stream);
 /* Dice + cross-entropy of logits [B][n][S] (2 <= n <= 8) against int64 labels [B][S], fused forward + backward:
  *   p = softmax over the classes; dice_bc = 1 - (2 sum_v p onehot + smooth_nr) / (sum_v p^2 + sum_v onehot + smooth_dr);
- *   loss = mean_bc dice_bc + mean_bv -log p[label];  dlogits (dtype, may be NULL) = grad_scale * d loss / d logits. */
+ *   loss = mean_bc dice_bc + mean_bv -log p[label];  dlogits (dtype, may be NULL) = grad_scale * d loss / d logits.
+ * Logits element (b, class c, voxel i) at logits[b stride_b + c stride_c + i stride_s] (dlogits alike): N C (D) H W is (n S, S, 1); a
+ * channels-last tensor whose voxel rows are ld apart is (S ld, 1, ld). */
 int64_t ucfvit_dice_ce_workspace(int64_t B, int64_t S);
-int ucfvit_dice_ce(const void* logits, const int64_t* labels, float* loss, void* dlogits, int64_t B, int64_t n, int64_t S, float smooth_nr,
-                   float smooth_dr, float grad_scale, void* workspace, int dtype, void* stream);
-
-/* The same loss on strided logits: element (b, class c, voxel i) at logits[b stride_b + c stride_c + i stride_s] (dlogits alike).
- * N C (D) H W is (n S, S, 1); a channels-last tensor whose voxel rows are ld apart is (S ld, 1, ld). */
-int ucfvit_dice_ce_strided(const void* logits, const int64_t* labels, float* loss, void* dlogits, int64_t B, int64_t n, int64_t S,
-                           int64_t stride_b, int64_t stride_c, int64_t stride_s, float smooth_nr, float smooth_dr, float grad_scale,
-                           void* workspace, int dtype, void* stream);
+int ucfvit_dice_ce(const void* logits, const int64_t* labels, float* loss, void* dlogits, int64_t B, int64_t n, int64_t S, int64_t stride_b,
+                   int64_t stride_c, int64_t stride_s, float smooth_nr, float smooth_dr, float grad_scale, void* workspace, int dtype, void* stream);
 
 /* Dice + CE over a volume SHARDED across the ranks of a sequence-parallel group (X-slabs of the UNETR decoder; no reference counterpart: the
  * reference asserts seq_par_size == 1, training_scripts/train_masked_fsdp.py:220 — the loss itself is train_unetr_simple.py:38).  Every term
  * is a function of per-(batch, class) sums over voxels: ucfvit_dice_ce_stats writes this rank's sums (stats: B x ucfvit_dice_ce_stats_floats()
  * floats; workspace: ucfvit_dice_ce_workspace bytes), the caller adds them over the group, ucfvit_dice_ce_from_stats evaluates the loss of the
  * WHOLE volume from the summed stats (rewritten in place) and the gradient of the LOCAL logits (S local voxels, S_total voxels of the whole
- * volume, both per batch element).  Unsharded: S_total = S and the pair equals ucfvit_dice_ce_strided. */
+ * volume, both per batch element).  Unsharded: S_total = S gives ucfvit_dice_ce's loss up to rounding. */
 int ucfvit_dice_ce_stats_floats(void);
 int ucfvit_dice_ce_stats(const void* logits, const int64_t* labels, float* stats, int64_t B, int64_t n, int64_t S, int64_t stride_b, int64_t stride_c,
                          int64_t stride_s, void* workspace, int dtype, void* stream);
@@ -374,26 +370,24 @@ int ucfvit_dice_ce_from_stats(const void* logits, const int64_t* labels, float* 
                               float grad_scale, int dtype, void* stream);
 
 /* Channels-last instance norm (+ LeakyReLU, + residual) for the layout of the convolution kernels below: x, res, y [B][S][C] bf16,
- * mean / rstd [B][C] fp32; C a power of two in 8..2048.  Same formulas as ucfvit_instnorm_fwd / _bwd.  had_res: the forward pass added a
- * residual, so the activation mask is read from y; without one sign(y) = sign(x - mean) and y is not read at all (dres requires had_res).
- * ld_dy: voxel-row stride of dy in elements (C for a dense tensor; larger when dy is a channel slice of a concatenation's gradient). */
+ * mean / rstd [B][C] fp32; C a power of two in 8..2048.  Same formulas as ucfvit_instnorm_fwd / _bwd, one entry point per pass:
+ *   forward:  ucfvit_instnorm_cl_stats (mean / rstd of x), then ucfvit_instnorm_cl_apply (y = lrelu((x - mean) rstd [+ res], slope)).
+ *   backward: ucfvit_instnorm_cl_bwd_sums leaves the per-(batch, channel) MEANS over the voxels of dy' (the gradient behind the activation
+ *             mask) and of dy' xhat in m1 / m2 [B][C], then ucfvit_instnorm_cl_bwd_apply writes dx (and dres).  A volume sharded across
+ *             ranks averages m1 / m2 over the ranks in between (equal slabs: the mean over the whole volume).
+ * had_res: the forward pass added a residual, so the activation mask is read from y; without one sign(y) = sign(x - mean) and y is not read
+ * at all (dres requires had_res).  ld_dy: voxel-row stride of dy in elements (C for a dense tensor; larger when dy is a channel slice of a
+ * concatenation's gradient).  workspace: ucfvit_instnorm_cl_workspace bytes, for _stats and _bwd_sums; its last 2 B C floats are not
+ * touched by either, so a caller may keep m1 / m2 there.  (The forward statistics of a sharded volume combine from the ranks'
+ * ucfvit_instnorm_cl_stats by the parallel-variance formula: mean = avg(mean_r), var = avg(var_r + (mean_r - mean)^2), in double.) */
 int64_t ucfvit_instnorm_cl_workspace(int64_t B, int64_t S, int64_t C);
-int ucfvit_instnorm_cl_fwd(const void* x, const void* res, void* y, float* mean, float* rstd, int64_t B, int64_t S, int64_t C, float eps,
-                           float slope, void* workspace, void* stream);
-int ucfvit_instnorm_cl_bwd(const void* dy, const void* y, const void* x, const float* mean, const float* rstd, void* dx, void* dres, int64_t B,
-                           int64_t S, int64_t C, int64_t ld_dy, float slope, int had_res, void* workspace, void* stream);
-
-/* ucfvit_instnorm_cl_bwd in two calls, for a volume sharded across ranks: _bwd_sums leaves the per-(batch, channel) MEANS over the local voxels
- * of dy' (the gradient behind the activation mask) and of dy' xhat in m1 / m2 [B][C]; the caller averages them over the ranks (equal slabs:
- * the mean over the whole volume) and passes them to _bwd_apply.  (The forward statistics of a sharded volume combine the same way from
- * ucfvit_instnorm_cl_stats: mean = avg(mean_r), var = avg(var_r + mean_r^2) - mean^2.) */
 int ucfvit_instnorm_cl_bwd_sums(const void* dy, const void* y, const void* x, const float* mean, const float* rstd, float* m1, float* m2, int64_t B,
                                 int64_t S, int64_t C, int64_t ld_dy, float slope, int had_res, void* workspace, void* stream);
 int ucfvit_instnorm_cl_bwd_apply(const void* dy, const void* y, const void* x, const float* mean, const float* rstd, const float* m1, const float* m2,
                                  void* dx, void* dres, int64_t B, int64_t S, int64_t C, int64_t ld_dy, float slope, int had_res, void* stream);
 
 /* The tail of a residual block whose residual branch is itself normalised (monai UnetResBlock with the 1x1x1 projection):
- *   ucfvit_instnorm_cl_stats:  mean / rstd of x only (ucfvit_instnorm_cl_fwd = this + the apply pass)
+ *   ucfvit_instnorm_cl_stats:  mean / rstd of x, one per branch
  *   ucfvit_instnorm_cl_apply2: y = lrelu((x - mean) rstd + (x2 - mean2) rstd2, slope) — the normalised branch is never materialised
  *   ucfvit_instnorm_cl_bwd2:   dx, dx2 from dy, y (activation mask) and the raw inputs: one pair of passes for both normalisations
  *                              (workspace: ucfvit_instnorm_cl_bwd2_workspace bytes). */

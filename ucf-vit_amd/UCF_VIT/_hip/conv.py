@@ -438,7 +438,8 @@ def unet_res_block(inp, w1, w2, w3=None, eps=1e-5, slope=0.01):
 class InstNormActCLFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, res, eps, slope):
-        y, mean, rstd = ops.instnorm_cl_fwd(x, res, eps, slope)
+        mean, rstd = ops.instnorm_cl_stats(x, eps)
+        y = ops.instnorm_cl_apply(x, mean, rstd, res, slope)
         ctx.save_for_backward(x, y, mean, rstd)
         ctx.slope = slope
         ctx.has_res = res is not None

@@ -797,7 +797,8 @@ class DiceCEFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, labels, smooth_nr, smooth_dr):
         lb = labels if labels.is_contiguous() else labels.contiguous()
-        if logits.is_contiguous() or _is_channels_last_rows(logits):       # the HIP decoder's logits: read in place, no N C D H W copy
+        # the HIP decoder's logits (a view at offset 0 over a [B, *spatial, ld] buffer): read in place, no N C D H W copy
+        if logits.is_contiguous() or (logits.dim() >= 3 and logits.storage_offset() == 0 and ops.dice_strides(logits) is not None):
             lg = logits
         else:
             lg = logits.contiguous()
@@ -808,23 +809,16 @@ class DiceCEFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         (dl,) = ctx.saved_tensors
-        if dl.is_contiguous():
-            return dl * g.to(dl.dtype), None, None, None
-        flat = dl.as_strided((dl.shape[0] * dl.stride(0),), (1,))           # the padded channels-last buffer behind the view
-        return (flat * g.to(dl.dtype)).as_strided(dl.shape, dl.stride()), None, None, None
+        return dice_grad_times(dl, g), None, None, None
 
 
-def _is_channels_last_rows(t):
-    """[B, n, *spatial] view over a dense [B, *spatial, ld >= n] buffer"""
-    if t.dim() < 3 or t.stride(1) != 1 or t.storage_offset() != 0:
-        return False
-    ld = t.stride(-1)
-    exp = ld
-    for d in range(t.dim() - 1, 1, -1):
-        if t.stride(d) != exp:
-            return False
-        exp *= t.shape[d]
-    return ld >= t.shape[1] and t.stride(0) == exp
+def dice_grad_times(dl, g):
+    """dl * g for a logits gradient of ops.dice_ce / dice_ce_from_stats: N C (D) H W, or a view over a padded channels-last buffer, which
+    is scaled whole so that the product keeps dl's strides"""
+    if dl.is_contiguous():
+        return dl * g.to(dl.dtype)
+    flat = dl.as_strided((dl.shape[0] * dl.stride(0),), (1,))           # the padded channels-last buffer behind the view
+    return (flat * g.to(dl.dtype)).as_strided(dl.shape, dl.stride())
 
 
 # ---------------------------------------------------------------------------------------------- public helpers

@@ -574,44 +574,11 @@ def instnorm_bwd(dy, y, x, mean, rstd, slope, want_dres):
     return dx, dres
 
 
-def dice_ce(logits, labels, smooth_nr=1e-5, smooth_dr=1e-5, grad_scale=1.0, want_grad=True):
-    """logits [B, n, *spatial] (2 <= n <= 8), labels int64 [B, *spatial] (or [B, 1, *spatial]) -> (loss fp32 scalar, dlogits or None).
-    logits may be contiguous (N C D H W) or a channels-last view of a [B, *spatial, ld >= n] buffer (what the HIP decoder returns)."""
-    L = _l.load()
-    _chk(labels, "dice_ce.labels")
-    if not logits.is_cuda:
-        _chk(logits, "dice_ce.logits")
-    if labels.dtype != torch.int64:
-        raise TypeError("dice_ce: labels must be int64")
+def dice_strides(logits):
+    """(stride_b, stride_c, stride_s) of logits [B, n, *spatial] that are contiguous (N C (D) H W) or a channels-last view with contiguous
+    voxel rows (over a [B, *spatial, ld >= n] buffer); None for any other layout"""
     B, n = logits.shape[0], logits.shape[1]
     S = logits.numel() // (B * n)
-    if labels.numel() != B * S:
-        raise ValueError("dice_ce: labels must hold one class index per voxel")
-    if logits.is_contiguous():
-        sb, sc, ss = n * S, S, 1
-        dl = torch.empty_like(logits) if want_grad else None
-    else:
-        cl = logits.movedim(1, -1)                           # [B, *spatial, n]
-        ld = cl.stride(-2)
-        ok = cl.stride(-1) == 1 and ld >= n and cl.stride(0) == S * ld
-        exp = ld
-        for d in range(cl.dim() - 2, 0, -1):
-            ok = ok and cl.stride(d) == exp
-            exp *= cl.shape[d]
-        if not ok:
-            raise RuntimeError("dice_ce: logits must be contiguous or a channels-last view with contiguous voxel rows")
-        sb, sc, ss = S * ld, 1, ld
-        mk = torch.empty if ld == n else torch.zeros                 # padding columns of the rows, if any, read as zero gradient
-        dl = mk(B * S * ld, dtype=logits.dtype, device=logits.device).as_strided(logits.shape, logits.stride()) if want_grad else None
-    loss = torch.empty((), dtype=torch.float32, device=logits.device)
-    ws = workspace(L.ucfvit_dice_ce_workspace(B, S), logits.device)
-    _l.check(L.ucfvit_dice_ce_strided(logits.data_ptr(), labels.data_ptr(), loss.data_ptr(), _p(dl), B, n, S, sb, sc, ss, smooth_nr, smooth_dr,
-                                      grad_scale, ws.data_ptr(), dt(logits), _stream()), "ucfvit_dice_ce")
-    return loss, dl
-
-
-def _dice_strides(logits, B, n, S):
-    """(stride_b, stride_c, stride_s) of contiguous N C (D) H W logits or of a channels-last view with contiguous voxel rows"""
     if logits.is_contiguous():
         return n * S, S, 1
     cl = logits.movedim(1, -1)                           # [B, *spatial, n]
@@ -621,25 +588,57 @@ def _dice_strides(logits, B, n, S):
     for d in range(cl.dim() - 2, 0, -1):
         ok = ok and cl.stride(d) == exp
         exp *= cl.shape[d]
-    if not ok:
+    return (S * ld, 1, ld) if ok else None
+
+
+def _dice_labels(logits, labels, name):
+    _chk(labels, f"{name}.labels")
+    if not logits.is_cuda:
+        _chk(logits, f"{name}.logits")
+    if labels.dtype != torch.int64:
+        raise TypeError(f"{name}: labels must be int64")
+    if labels.numel() * logits.shape[1] != logits.numel():
+        raise ValueError(f"{name}: labels must hold one class index per voxel")
+
+
+def _dice_layout(logits):
+    """-> (B, n, S, (stride_b, stride_c, stride_s))"""
+    strides = dice_strides(logits)
+    if strides is None:
         raise RuntimeError("dice_ce: logits must be contiguous or a channels-last view with contiguous voxel rows")
-    return S * ld, 1, ld
+    B, n = logits.shape[0], logits.shape[1]
+    return B, n, logits.numel() // (B * n), strides
+
+
+def _dice_grad(logits, strides):
+    """dlogits with the strides of logits: N C (D) H W, or the padded channels-last buffer behind a view (padding columns zero)"""
+    if logits.is_contiguous():
+        return torch.empty_like(logits)
+    sb, _, ld = strides
+    mk = torch.empty if ld == logits.shape[1] else torch.zeros
+    return mk(logits.shape[0] * sb, dtype=logits.dtype, device=logits.device).as_strided(logits.shape, logits.stride())
+
+
+def dice_ce(logits, labels, smooth_nr=1e-5, smooth_dr=1e-5, grad_scale=1.0, want_grad=True):
+    """logits [B, n, *spatial] (2 <= n <= 8), labels int64 [B, *spatial] (or [B, 1, *spatial]) -> (loss fp32 scalar, dlogits or None).
+    logits may be contiguous (N C D H W) or a channels-last view of a [B, *spatial, ld >= n] buffer (what the HIP decoder returns)."""
+    L = _l.load()
+    _dice_labels(logits, labels, "dice_ce")
+    B, n, S, (sb, sc, ss) = _dice_layout(logits)
+    dl = _dice_grad(logits, (sb, sc, ss)) if want_grad else None
+    loss = torch.empty((), dtype=torch.float32, device=logits.device)
+    ws = workspace(L.ucfvit_dice_ce_workspace(B, S), logits.device)
+    _l.check(L.ucfvit_dice_ce(logits.data_ptr(), labels.data_ptr(), loss.data_ptr(), _p(dl), B, n, S, sb, sc, ss, smooth_nr, smooth_dr, grad_scale,
+                              ws.data_ptr(), dt(logits), _stream()), "ucfvit_dice_ce")
+    return loss, dl
 
 
 def dice_ce_stats(logits, labels):
     """this rank's per-(batch, class) sums of the Dice + CE loss over its slab of a sharded volume: fp32 [B, ucfvit_dice_ce_stats_floats()]
     (to be summed over the group and handed to dice_ce_from_stats)"""
     L = _l.load()
-    _chk(labels, "dice_ce_stats.labels")
-    if not logits.is_cuda:
-        _chk(logits, "dice_ce_stats.logits")
-    if labels.dtype != torch.int64:
-        raise TypeError("dice_ce_stats: labels must be int64")
-    B, n = logits.shape[0], logits.shape[1]
-    S = logits.numel() // (B * n)
-    if labels.numel() != B * S:
-        raise ValueError("dice_ce_stats: labels must hold one class index per local voxel")
-    sb, sc, ss = _dice_strides(logits, B, n, S)
+    _dice_labels(logits, labels, "dice_ce_stats")
+    B, n, S, (sb, sc, ss) = _dice_layout(logits)
     stats = torch.empty((B, L.ucfvit_dice_ce_stats_floats()), dtype=torch.float32, device=logits.device)
     ws = workspace(L.ucfvit_dice_ce_workspace(B, S), logits.device)
     _l.check(L.ucfvit_dice_ce_stats(logits.data_ptr(), labels.data_ptr(), stats.data_ptr(), B, n, S, sb, sc, ss, ws.data_ptr(), dt(logits), _stream()),
@@ -651,17 +650,8 @@ def dice_ce_from_stats(logits, labels, stats, S_total, smooth_nr=1e-5, smooth_dr
     """stats: the per-(batch, class) sums of the WHOLE volume (dice_ce_stats summed over the group) -> (loss of the whole volume, gradient of the
     LOCAL logits or None).  S_total: voxels of the whole volume per batch element."""
     L = _l.load()
-    B, n = logits.shape[0], logits.shape[1]
-    S = logits.numel() // (B * n)
-    sb, sc, ss = _dice_strides(logits, B, n, S)
-    if want_grad:
-        if logits.is_contiguous():
-            dl = torch.empty_like(logits)
-        else:
-            mk = torch.empty if ss == n else torch.zeros             # padding columns of the rows, if any, read as zero gradient
-            dl = mk(B * sb, dtype=logits.dtype, device=logits.device).as_strided(logits.shape, logits.stride())
-    else:
-        dl = None
+    B, n, S, (sb, sc, ss) = _dice_layout(logits)
+    dl = _dice_grad(logits, (sb, sc, ss)) if want_grad else None
     stats = stats.clone()                                # rewritten in place by the fold
     loss = torch.empty((), dtype=torch.float32, device=logits.device)
     _l.check(L.ucfvit_dice_ce_from_stats(logits.data_ptr(), labels.data_ptr(), stats.data_ptr(), loss.data_ptr(), _p(dl), B, n, S, int(S_total), sb, sc, ss,
@@ -880,31 +870,27 @@ def pad_rows8(t):
     return out
 
 
-def instnorm_cl_fwd(x, res=None, eps=1e-5, slope=0.01):
-    """channels-last: y = leaky_relu(instance_norm(x) [+ res], slope) per (batch, channel) -> (y, mean [B, C], rstd [B, C])"""
-    L = _l.load()
-    _chk_cl(x, "instnorm_cl.x")
-    if res is not None:
-        _chk_cl(res, "instnorm_cl.res")
-        if res.shape != x.shape:
-            raise ValueError("instnorm_cl: res must have the shape of x")
+def _bsc(x):
+    """(B, S, C) of a channels-last map [B, *spatial, C]: S voxels per batch element"""
     B, C = x.shape[0], x.shape[-1]
-    S = x.numel() // (B * C)
-    y = torch.empty_like(x)
-    mean = torch.empty((B, C), dtype=torch.float32, device=x.device)
-    rstd = torch.empty((B, C), dtype=torch.float32, device=x.device)
-    ws = workspace(L.ucfvit_instnorm_cl_workspace(B, S, C), x.device)
-    _l.check(L.ucfvit_instnorm_cl_fwd(x.data_ptr(), _p(res), y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), B, S, C, eps, slope, ws.data_ptr(),
-                                      _stream()), "ucfvit_instnorm_cl_fwd")
-    return y, mean, rstd
+    return B, x.numel() // (B * C), C
+
+
+def _cl_dy(dy, x, name):
+    """-> (dy, its row stride): read in place if it is a dense or channel-sliced map of x's shape (the skip half of a concatenation's
+    gradient), else a contiguous copy"""
+    ld = cl_row_stride(dy)
+    if ld is None or dy.shape != x.shape:
+        dy = _chk_cl(dy.contiguous(), name)
+        ld = dy.shape[-1]
+    return dy, ld
 
 
 def instnorm_cl_stats(x, eps=1e-5):
     """-> (mean [B, C], rstd [B, C]) of a channels-last bf16 map"""
     L = _l.load()
     _chk_cl(x, "instnorm_cl_stats.x")
-    B, C = x.shape[0], x.shape[-1]
-    S = x.numel() // (B * C)
+    B, S, C = _bsc(x)
     mean = torch.empty((B, C), dtype=torch.float32, device=x.device)
     rstd = torch.empty((B, C), dtype=torch.float32, device=x.device)
     ws = workspace(L.ucfvit_instnorm_cl_workspace(B, S, C), x.device)
@@ -920,8 +906,7 @@ def instnorm_cl_apply(x, mean, rstd, res=None, slope=0.01):
         _chk_cl(res, "instnorm_cl_apply.res")
         if res.shape != x.shape:
             raise ValueError("instnorm_cl_apply: res must have the shape of x")
-    B, C = x.shape[0], x.shape[-1]
-    S = x.numel() // (B * C)
+    B, S, C = _bsc(x)
     y = torch.empty_like(x)
     _l.check(L.ucfvit_instnorm_cl_apply(x.data_ptr(), _p(res), y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), B, S, C, slope, _stream()),
              "ucfvit_instnorm_cl_apply")
@@ -934,8 +919,7 @@ def instnorm_cl_apply2(x, mean, rstd, x2, mean2, rstd2, slope):
     _chk_cl(x, "instnorm_cl_apply2.x"), _chk_cl(x2, "instnorm_cl_apply2.x2")
     if x2.shape != x.shape:
         raise ValueError("instnorm_cl_apply2: the two branches must have one shape")
-    B, C = x.shape[0], x.shape[-1]
-    S = x.numel() // (B * C)
+    B, S, C = _bsc(x)
     y = torch.empty_like(x)
     _l.check(L.ucfvit_instnorm_cl_apply2(x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), x2.data_ptr(), mean2.data_ptr(), rstd2.data_ptr(), y.data_ptr(),
                                          B, S, C, slope, _stream()), "ucfvit_instnorm_cl_apply2")
@@ -946,12 +930,8 @@ def instnorm_cl_bwd2(dy, y, x, mean, rstd, x2, mean2, rstd2, slope):
     """backward of instnorm_cl_apply2 -> (dx, dx2); dy may be a channel slice of a wider channels-last gradient"""
     L = _l.load()
     _chk_cl(x, "instnorm_cl_bwd2.x")
-    ld = cl_row_stride(dy)
-    if ld is None or dy.shape != x.shape:
-        dy = _chk_cl(dy.contiguous(), "instnorm_cl_bwd2.dy")
-        ld = dy.shape[-1]
-    B, C = x.shape[0], x.shape[-1]
-    S = x.numel() // (B * C)
+    dy, ld = _cl_dy(dy, x, "instnorm_cl_bwd2.dy")
+    B, S, C = _bsc(x)
     dx, dx2 = torch.empty_like(x), torch.empty_like(x)
     ws = workspace(L.ucfvit_instnorm_cl_bwd2_workspace(B, S, C), x.device)
     _l.check(L.ucfvit_instnorm_cl_bwd2(dy.data_ptr(), y.data_ptr(), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), x2.data_ptr(), mean2.data_ptr(),
@@ -961,37 +941,24 @@ def instnorm_cl_bwd2(dy, y, x, mean, rstd, x2, mean2, rstd2, slope):
 
 
 def instnorm_cl_bwd(dy, y, x, mean, rstd, slope, want_dres, had_res=None):
-    """dy may be a channel slice of a wider channels-last gradient (the skip half of a concatenation's gradient): read in place"""
-    L = _l.load()
-    _chk_cl(x, "instnorm_cl_bwd.x")
-    ld = cl_row_stride(dy)
-    if ld is None or dy.shape != x.shape:
-        dy = _chk_cl(dy.contiguous(), "instnorm_cl_bwd.dy")
-        ld = dy.shape[-1]
-    B, C = x.shape[0], x.shape[-1]
-    S = x.numel() // (B * C)
-    dx = torch.empty_like(x)
-    dres = torch.empty_like(x) if want_dres else None
-    ws = workspace(L.ucfvit_instnorm_cl_workspace(B, S, C), x.device)
+    """backward of instnorm_cl_apply: instnorm_cl_bwd_sums, m1 / m2 kept in the workspace, then instnorm_cl_bwd_apply; dy may be a channel
+    slice of a wider channels-last gradient: read in place"""
     had_res = want_dres if had_res is None else had_res
-    _l.check(L.ucfvit_instnorm_cl_bwd(dy.data_ptr(), y.data_ptr(), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), dx.data_ptr(), _p(dres), B, S, C,
-                                      ld, slope, 1 if had_res else 0, ws.data_ptr(), _stream()), "ucfvit_instnorm_cl_bwd")
-    return dx, dres
+    m1, m2, dy = instnorm_cl_bwd_sums(dy, y, x, mean, rstd, slope, had_res, in_workspace=True)
+    return instnorm_cl_bwd_apply(dy, y, x, mean, rstd, m1, m2, slope, want_dres, had_res)
 
 
-def instnorm_cl_bwd_sums(dy, y, x, mean, rstd, slope, had_res):
-    """first half of instnorm_cl_bwd for a sharded volume: (m1, m2) [B, C] = the means over the LOCAL voxels of dy' and dy' xhat"""
+def instnorm_cl_bwd_sums(dy, y, x, mean, rstd, slope, had_res, in_workspace=False):
+    """first half of instnorm_cl_bwd: (m1, m2) [B, C] = the means over the voxels of x (this rank's slab of a sharded volume) of dy' and
+    dy' xhat, and dy as instnorm_cl_bwd_apply reads it.  m1 / m2 are fresh, or with in_workspace views of the workspace's last 2 B C floats,
+    which the next call on the workspace may overwrite"""
     L = _l.load()
     _chk_cl(x, "instnorm_cl_bwd_sums.x")
-    ld = cl_row_stride(dy)
-    if ld is None or dy.shape != x.shape:
-        dy = _chk_cl(dy.contiguous(), "instnorm_cl_bwd_sums.dy")
-        ld = dy.shape[-1]
-    B, C = x.shape[0], x.shape[-1]
-    S = x.numel() // (B * C)
-    m1 = torch.empty((B, C), dtype=torch.float32, device=x.device)
-    m2 = torch.empty((B, C), dtype=torch.float32, device=x.device)
-    ws = workspace(L.ucfvit_instnorm_cl_workspace(B, S, C), x.device)
+    dy, ld = _cl_dy(dy, x, "instnorm_cl_bwd_sums.dy")
+    B, S, C = _bsc(x)
+    n = L.ucfvit_instnorm_cl_workspace(B, S, C) // 4
+    ws = workspace(4 * n, x.device)
+    m1, m2 = ws[n - 2 * B * C:n].view(2, B, C) if in_workspace else torch.empty((2, B, C), dtype=torch.float32, device=x.device)
     _l.check(L.ucfvit_instnorm_cl_bwd_sums(dy.data_ptr(), y.data_ptr(), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), m1.data_ptr(), m2.data_ptr(),
                                            B, S, C, ld, slope, 1 if had_res else 0, ws.data_ptr(), _stream()), "ucfvit_instnorm_cl_bwd_sums")
     return m1, m2, dy
@@ -999,12 +966,8 @@ def instnorm_cl_bwd_sums(dy, y, x, mean, rstd, slope, had_res):
 
 def instnorm_cl_bwd_apply(dy, y, x, mean, rstd, m1, m2, slope, want_dres, had_res):
     L = _l.load()
-    ld = cl_row_stride(dy)
-    if ld is None or dy.shape != x.shape:
-        dy = _chk_cl(dy.contiguous(), "instnorm_cl_bwd_apply.dy")
-        ld = dy.shape[-1]
-    B, C = x.shape[0], x.shape[-1]
-    S = x.numel() // (B * C)
+    dy, ld = _cl_dy(dy, x, "instnorm_cl_bwd_apply.dy")
+    B, S, C = _bsc(x)
     dx = torch.empty_like(x)
     dres = torch.empty_like(x) if want_dres else None
     _l.check(L.ucfvit_instnorm_cl_bwd_apply(dy.data_ptr(), y.data_ptr(), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), m1.data_ptr(), m2.data_ptr(),

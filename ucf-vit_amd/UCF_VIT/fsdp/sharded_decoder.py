@@ -29,6 +29,7 @@ import torch
 import torch.distributed as dist
 
 from UCF_VIT._hip import conv as HC
+from UCF_VIT._hip import functional as HF
 from UCF_VIT._hip import ops
 
 
@@ -222,10 +223,7 @@ class ShardedDiceCEFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         (dl,) = ctx.saved_tensors
-        if dl.is_contiguous():
-            return dl * g.to(dl.dtype), None, None, None, None
-        flat = dl.as_strided((dl.shape[0] * dl.stride(0),), (1,))           # the padded channels-last buffer behind the view
-        return (flat * g.to(dl.dtype)).as_strided(dl.shape, dl.stride()), None, None, None, None
+        return HF.dice_grad_times(dl, g), None, None, None, None
 
 
 def sharded_dice_ce(logits_local, labels_local, spg, smooth_nr=1e-5, smooth_dr=1e-5):

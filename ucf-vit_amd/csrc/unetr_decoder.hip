@@ -770,15 +770,22 @@ extern "C" int ucfvit_instnorm_bwd(const void* dy, const void* y, const void* x,
 
 extern "C" int64_t ucfvit_dice_ce_workspace(int64_t B, int64_t S) { return (B * chunks_of(S) * DSTAT + B * DSTAT) * (int64_t)sizeof(float); }
 
+static int dice_check(const char* name, const void* logits, const int64_t* labels, int64_t B, int64_t n, int64_t S, int64_t stride_b,
+                      int64_t stride_c, int64_t stride_s, int dtype) {
+    UCF_CHECK_ARG(logits && labels, "%s: null pointer", name);
+    UCF_CHECK_ARG(B > 0 && B < 65536 && S > 0 && n >= 2 && n <= MAXC, "%s: need 2 <= classes <= %d, B in 1..65535", name, MAXC);
+    UCF_CHECK_ARG(dtype == UCFVIT_F32 || dtype == UCFVIT_BF16, "%s: bad dtype %d", name, dtype);
+    UCF_CHECK_ARG(stride_b > 0 && stride_c > 0 && stride_s > 0, "%s: strides must be positive", name);
+    return UCFVIT_OK;
+}
+
 // logits element (b, class c, voxel i) at logits[b stride_b + c stride_c + i stride_s] (dlogits alike): N C (D) H W is (n S, S, 1), a
 // channels-last tensor with row stride ld is (S ld, 1, ld)
-extern "C" int ucfvit_dice_ce_strided(const void* logits, const int64_t* labels, float* loss, void* dlogits, int64_t B, int64_t n, int64_t S,
-                                      int64_t stride_b, int64_t stride_c, int64_t stride_s, float smooth_nr, float smooth_dr, float grad_scale,
-                                      void* workspace, int dtype, void* stream) {
-    UCF_CHECK_ARG(logits && labels && loss && workspace, "ucfvit_dice_ce: null pointer");
-    UCF_CHECK_ARG(B > 0 && B < 65536 && S > 0 && n >= 2 && n <= MAXC, "ucfvit_dice_ce: need 2 <= classes <= %d, B in 1..65535", MAXC);
-    UCF_CHECK_ARG(dtype == UCFVIT_F32 || dtype == UCFVIT_BF16, "ucfvit_dice_ce: bad dtype %d", dtype);
-    UCF_CHECK_ARG(stride_b > 0 && stride_c > 0 && stride_s > 0, "ucfvit_dice_ce: strides must be positive");
+extern "C" int ucfvit_dice_ce(const void* logits, const int64_t* labels, float* loss, void* dlogits, int64_t B, int64_t n, int64_t S, int64_t stride_b,
+                              int64_t stride_c, int64_t stride_s, float smooth_nr, float smooth_dr, float grad_scale, void* workspace, int dtype,
+                              void* stream) {
+    if (int rc = dice_check("ucfvit_dice_ce", logits, labels, B, n, S, stride_b, stride_c, stride_s, dtype)) return rc;
+    UCF_CHECK_ARG(loss && workspace, "ucfvit_dice_ce: null pointer");
     hipStream_t s = (hipStream_t)stream;
     const int ch = chunks_of(S);
     float* part = (float*)workspace;
@@ -803,10 +810,8 @@ extern "C" int ucfvit_dice_ce_strided(const void* logits, const int64_t* labels,
 // value and into the gradient of the local logits (S_total = voxels of the whole volume per batch element).
 extern "C" int ucfvit_dice_ce_stats(const void* logits, const int64_t* labels, float* stats, int64_t B, int64_t n, int64_t S, int64_t stride_b,
                                     int64_t stride_c, int64_t stride_s, void* workspace, int dtype, void* stream) {
-    UCF_CHECK_ARG(logits && labels && stats && workspace, "ucfvit_dice_ce_stats: null pointer");
-    UCF_CHECK_ARG(B > 0 && B < 65536 && S > 0 && n >= 2 && n <= MAXC, "ucfvit_dice_ce_stats: need 2 <= classes <= %d, B in 1..65535", MAXC);
-    UCF_CHECK_ARG(dtype == UCFVIT_F32 || dtype == UCFVIT_BF16, "ucfvit_dice_ce_stats: bad dtype %d", dtype);
-    UCF_CHECK_ARG(stride_b > 0 && stride_c > 0 && stride_s > 0, "ucfvit_dice_ce_stats: strides must be positive");
+    if (int rc = dice_check("ucfvit_dice_ce_stats", logits, labels, B, n, S, stride_b, stride_c, stride_s, dtype)) return rc;
+    UCF_CHECK_ARG(stats && workspace, "ucfvit_dice_ce_stats: null pointer");
     hipStream_t s = (hipStream_t)stream;
     const int ch = chunks_of(S);
     float* part = (float*)workspace;
@@ -823,9 +828,9 @@ extern "C" int ucfvit_dice_ce_stats_floats(void) { return DSTAT; }
 extern "C" int ucfvit_dice_ce_from_stats(const void* logits, const int64_t* labels, float* stats, float* loss, void* dlogits, int64_t B, int64_t n,
                                          int64_t S, int64_t S_total, int64_t stride_b, int64_t stride_c, int64_t stride_s, float smooth_nr,
                                          float smooth_dr, float grad_scale, int dtype, void* stream) {
-    UCF_CHECK_ARG(logits && labels && stats && loss, "ucfvit_dice_ce_from_stats: null pointer");
-    UCF_CHECK_ARG(B > 0 && B < 65536 && S > 0 && S_total >= S && n >= 2 && n <= MAXC, "ucfvit_dice_ce_from_stats: bad sizes");
-    UCF_CHECK_ARG(dtype == UCFVIT_F32 || dtype == UCFVIT_BF16, "ucfvit_dice_ce_from_stats: bad dtype %d", dtype);
+    if (int rc = dice_check("ucfvit_dice_ce_from_stats", logits, labels, B, n, S, stride_b, stride_c, stride_s, dtype)) return rc;
+    UCF_CHECK_ARG(stats && loss, "ucfvit_dice_ce_from_stats: null pointer");
+    UCF_CHECK_ARG(S_total >= S, "ucfvit_dice_ce_from_stats: S_total < S");
     hipStream_t s = (hipStream_t)stream;
     // one "chunk" per batch element = the global sums themselves: the fold rewrites them in place and evaluates the loss
     hipLaunchKernelGGL(dice_final, dim3(1), dim3(64), 0, s, (const float*)stats, stats, loss, (int)B, (int)n, S_total, 1, smooth_nr, smooth_dr);
@@ -840,11 +845,6 @@ extern "C" int ucfvit_dice_ce_from_stats(const void* logits, const int64_t* labe
     return UCFVIT_OK;
 }
 
-extern "C" int ucfvit_dice_ce(const void* logits, const int64_t* labels, float* loss, void* dlogits, int64_t B, int64_t n, int64_t S,
-                              float smooth_nr, float smooth_dr, float grad_scale, void* workspace, int dtype, void* stream) {
-    return ucfvit_dice_ce_strided(logits, labels, loss, dlogits, B, n, S, n * S, S, 1, smooth_nr, smooth_dr, grad_scale, workspace, dtype, stream);
-}
-
 // ---- channels-last instance norm entry points: x, res, y [B][S][C] bf16; mean, rstd [B][C] fp32 ----------------------------------------------
 static int incl_check(const char* name, const void* x, int64_t B, int64_t S, int64_t C) {
     UCF_CHECK_ARG(x && B > 0 && B < 65536 && S > 0, "%s: need B in 1..65535 and S > 0", name);
@@ -852,78 +852,29 @@ static int incl_check(const char* name, const void* x, int64_t B, int64_t S, int
     UCF_CHECK_ARG(ucf_is_aligned16(x), "%s: operands must be 16-byte aligned", name);
     return UCFVIT_OK;
 }
+static int ld_dy_check(const char* name, const void* dy, int64_t C, int64_t ld_dy) {
+    UCF_CHECK_ARG(ld_dy >= C && ld_dy % 8 == 0 && ucf_is_aligned16(dy), "%s: ld_dy must be a multiple of 8 and >= C", name);
+    return UCFVIT_OK;
+}
+// statistics rows, then the fold's scratch, then m1 / m2 [2][B][C] for a caller that runs _bwd_sums and _bwd_apply back to back
 extern "C" int64_t ucfvit_instnorm_cl_workspace(int64_t B, int64_t S, int64_t C) {
-    return (B * cl_chunks_of(S, C) * 3 * C + B * 256 * 3 * C + 2 * B * C) * (int64_t)sizeof(float);    // statistics rows, then the fold's scratch
-}
-extern "C" int ucfvit_instnorm_cl_fwd(const void* x, const void* res, void* y, float* mean, float* rstd, int64_t B, int64_t S, int64_t C,
-                                      float eps, float slope, void* workspace, void* stream) {
-    if (int rc = incl_check("ucfvit_instnorm_cl_fwd", x, B, S, C)) return rc;
-    UCF_CHECK_ARG(y && mean && rstd && workspace, "ucfvit_instnorm_cl_fwd: null pointer");
-    hipStream_t s = (hipStream_t)stream;
-    const int ch = cl_chunks_of(S, C);
-    float* part = (float*)workspace;
-    hipLaunchKernelGGL(incl_stats_partial, dim3(ch, (unsigned)B), dim3(NT), 0, s, (const bf16*)x, part, S, (int)C, ch);
-    if (int rc = ucfvit_instnorm_cl_stats_fold(part, mean, rstd, B, S, C, ch, eps, part + B * ch * 3 * C, s)) return rc;
-    const dim3 g(cl_apply_grid(S, C, B), (unsigned)B);
-    if (res)
-        hipLaunchKernelGGL((incl_apply<true>), g, dim3(NT), 0, s, (const bf16*)x, mean, rstd, (const bf16*)res, (bf16*)y, S, (int)C, slope);
-    else
-        hipLaunchKernelGGL((incl_apply<false>), g, dim3(NT), 0, s, (const bf16*)x, mean, rstd, (const bf16*)x, (bf16*)y, S, (int)C, slope);
-    UCF_LAUNCH_CHECK("ucfvit_instnorm_cl_fwd");
-    return UCFVIT_OK;
-}
-extern "C" int ucfvit_instnorm_cl_bwd(const void* dy, const void* y, const void* x, const float* mean, const float* rstd, void* dx, void* dres,
-                                      int64_t B, int64_t S, int64_t C, int64_t ld_dy, float slope, int had_res, void* workspace, void* stream) {
-    if (int rc = incl_check("ucfvit_instnorm_cl_bwd", x, B, S, C)) return rc;
-    UCF_CHECK_ARG(ld_dy >= C && ld_dy % 8 == 0 && ucf_is_aligned16(dy), "ucfvit_instnorm_cl_bwd: ld_dy must be a multiple of 8 and >= C");
-    const int64_t ldg8 = ld_dy / 8;
-    UCF_CHECK_ARG(dy && y && mean && rstd && dx && workspace, "ucfvit_instnorm_cl_bwd: null pointer");
-    hipStream_t s = (hipStream_t)stream;
-    const int ch = cl_chunks_of(S, C);
-    float* part = (float*)workspace;
-    float* m1 = part + B * ch * 2 * C;
-    float* m2 = m1 + B * C;
-    UCF_CHECK_ARG(had_res || !dres, "ucfvit_instnorm_cl_bwd: dres without a residual in the forward pass");
-    if (had_res)
-        hipLaunchKernelGGL(incl_bwd_partial<true>, dim3(ch, (unsigned)B), dim3(NT), 0, s, (const bf16*)dy, (const bf16*)y, (const bf16*)x, mean, rstd,
-                           part, S, (int)C, ch, slope, ldg8);
-    else
-        hipLaunchKernelGGL(incl_bwd_partial<false>, dim3(ch, (unsigned)B), dim3(NT), 0, s, (const bf16*)dy, (const bf16*)y, (const bf16*)x, mean, rstd,
-                           part, S, (int)C, ch, slope, ldg8);
-    hipLaunchKernelGGL(incl_bwd_final, dim3((unsigned)(B * C)), dim3(64), 0, s, part, m1, m2, S, (int)C, ch);
-    const dim3 g(cl_apply_grid(S, C, B), (unsigned)B);
-#define INCL_BWD_APPLY(R_, W_)                                                                                                                  \
-    hipLaunchKernelGGL((incl_bwd_apply<R_, W_>), g, dim3(NT), 0, s, (const bf16*)dy, (const bf16*)y, (const bf16*)x, mean, rstd, m1, m2, (bf16*)dx, \
-                       (bf16*)(dres ? dres : dx), S, (int)C, slope, ldg8)
-    if (dres)
-        INCL_BWD_APPLY(true, true);
-    else if (had_res)
-        INCL_BWD_APPLY(true, false);
-    else
-        INCL_BWD_APPLY(false, false);
-#undef INCL_BWD_APPLY
-    UCF_LAUNCH_CHECK("ucfvit_instnorm_cl_bwd");
-    return UCFVIT_OK;
+    return (B * cl_chunks_of(S, C) * 3 * C + B * 256 * 3 * C + 2 * B * C) * (int64_t)sizeof(float);
 }
 
-// The backward pass in two calls, for a volume sharded across ranks (fsdp/sharded_decoder.py): _bwd_sums leaves the two per-(batch, channel)
-// MEANS over the local voxels (of dy' and of dy' xhat) in m1 / m2 [B][C]; the caller averages them over the group (equal slabs) and hands
-// them to _bwd_apply.  ucfvit_instnorm_cl_bwd = the two back to back.
+// The backward pass in two calls: _bwd_sums leaves the two per-(batch, channel) MEANS over the voxels (of dy' and of dy' xhat) in m1 / m2 [B][C],
+// _bwd_apply turns them into dx (and dres).  A volume sharded across ranks (fsdp/sharded_decoder.py) averages m1 / m2 over the group (equal
+// slabs) in between.
 extern "C" int ucfvit_instnorm_cl_bwd_sums(const void* dy, const void* y, const void* x, const float* mean, const float* rstd, float* m1, float* m2,
                                            int64_t B, int64_t S, int64_t C, int64_t ld_dy, float slope, int had_res, void* workspace, void* stream) {
     if (int rc = incl_check("ucfvit_instnorm_cl_bwd_sums", x, B, S, C)) return rc;
-    UCF_CHECK_ARG(ld_dy >= C && ld_dy % 8 == 0 && ucf_is_aligned16(dy), "ucfvit_instnorm_cl_bwd_sums: ld_dy must be a multiple of 8 and >= C");
+    if (int rc = ld_dy_check("ucfvit_instnorm_cl_bwd_sums", dy, C, ld_dy)) return rc;
     UCF_CHECK_ARG(dy && y && mean && rstd && m1 && m2 && workspace, "ucfvit_instnorm_cl_bwd_sums: null pointer");
     hipStream_t s = (hipStream_t)stream;
     const int ch = cl_chunks_of(S, C);
-    const int64_t ldg8 = ld_dy / 8;
     float* part = (float*)workspace;
-    if (had_res)
-        hipLaunchKernelGGL(incl_bwd_partial<true>, dim3(ch, (unsigned)B), dim3(NT), 0, s, (const bf16*)dy, (const bf16*)y, (const bf16*)x, mean, rstd,
-                           part, S, (int)C, ch, slope, ldg8);
-    else
-        hipLaunchKernelGGL(incl_bwd_partial<false>, dim3(ch, (unsigned)B), dim3(NT), 0, s, (const bf16*)dy, (const bf16*)y, (const bf16*)x, mean, rstd,
-                           part, S, (int)C, ch, slope, ldg8);
+    const auto partial = had_res ? incl_bwd_partial<true> : incl_bwd_partial<false>;
+    hipLaunchKernelGGL(partial, dim3(ch, (unsigned)B), dim3(NT), 0, s, (const bf16*)dy, (const bf16*)y, (const bf16*)x, mean, rstd, part, S, (int)C,
+                       ch, slope, ld_dy / 8);
     hipLaunchKernelGGL(incl_bwd_final, dim3((unsigned)(B * C)), dim3(64), 0, s, part, m1, m2, S, (int)C, ch);
     UCF_LAUNCH_CHECK("ucfvit_instnorm_cl_bwd_sums");
     return UCFVIT_OK;
@@ -932,27 +883,18 @@ extern "C" int ucfvit_instnorm_cl_bwd_apply(const void* dy, const void* y, const
                                             const float* m2, void* dx, void* dres, int64_t B, int64_t S, int64_t C, int64_t ld_dy, float slope,
                                             int had_res, void* stream) {
     if (int rc = incl_check("ucfvit_instnorm_cl_bwd_apply", x, B, S, C)) return rc;
-    UCF_CHECK_ARG(ld_dy >= C && ld_dy % 8 == 0 && ucf_is_aligned16(dy), "ucfvit_instnorm_cl_bwd_apply: ld_dy must be a multiple of 8 and >= C");
+    if (int rc = ld_dy_check("ucfvit_instnorm_cl_bwd_apply", dy, C, ld_dy)) return rc;
     UCF_CHECK_ARG(dy && y && mean && rstd && m1 && m2 && dx, "ucfvit_instnorm_cl_bwd_apply: null pointer");
     UCF_CHECK_ARG(had_res || !dres, "ucfvit_instnorm_cl_bwd_apply: dres without a residual in the forward pass");
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t ldg8 = ld_dy / 8;
-    const dim3 g(cl_apply_grid(S, C, B), (unsigned)B);
-#define INCL_BWD_APPLY(R_, W_)                                                                                                                  \
-    hipLaunchKernelGGL((incl_bwd_apply<R_, W_>), g, dim3(NT), 0, s, (const bf16*)dy, (const bf16*)y, (const bf16*)x, mean, rstd, m1, m2, (bf16*)dx, \
-                       (bf16*)(dres ? dres : dx), S, (int)C, slope, ldg8)
-    if (dres)
-        INCL_BWD_APPLY(true, true);
-    else if (had_res)
-        INCL_BWD_APPLY(true, false);
-    else
-        INCL_BWD_APPLY(false, false);
-#undef INCL_BWD_APPLY
+    // <RES: the activation mask is read from y, WRES: dres is written>
+    const auto apply = dres ? incl_bwd_apply<true, true> : had_res ? incl_bwd_apply<true, false> : incl_bwd_apply<false, false>;
+    hipLaunchKernelGGL(apply, dim3(cl_apply_grid(S, C, B), (unsigned)B), dim3(NT), 0, (hipStream_t)stream, (const bf16*)dy, (const bf16*)y,
+                       (const bf16*)x, mean, rstd, m1, m2, (bf16*)dx, (bf16*)(dres ? dres : dx), S, (int)C, slope, ld_dy / 8);
     UCF_LAUNCH_CHECK("ucfvit_instnorm_cl_bwd_apply");
     return UCFVIT_OK;
 }
 
-// statistics only (mean, rstd [B][C]); ucfvit_instnorm_cl_fwd = this + the apply pass
+// statistics only (mean, rstd [B][C]); the forward pass is this + ucfvit_instnorm_cl_apply
 extern "C" int ucfvit_instnorm_cl_stats(const void* x, float* mean, float* rstd, int64_t B, int64_t S, int64_t C, float eps, void* workspace,
                                         void* stream) {
     if (int rc = incl_check("ucfvit_instnorm_cl_stats", x, B, S, C)) return rc;
@@ -984,7 +926,7 @@ extern "C" int ucfvit_instnorm_cl_bwd2(const void* dy, const void* y, const void
                                        const float* mean2, const float* rstd2, void* dx, void* dx2, int64_t B, int64_t S, int64_t C, int64_t ld_dy,
                                        float slope, void* workspace, void* stream) {
     if (int rc = incl_check("ucfvit_instnorm_cl_bwd2", x, B, S, C)) return rc;
-    UCF_CHECK_ARG(ld_dy >= C && ld_dy % 8 == 0 && ucf_is_aligned16(dy), "ucfvit_instnorm_cl_bwd2: ld_dy must be a multiple of 8 and >= C");
+    if (int rc = ld_dy_check("ucfvit_instnorm_cl_bwd2", dy, C, ld_dy)) return rc;
     UCF_CHECK_ARG(dy && y && mean && rstd && x2 && mean2 && rstd2 && dx && dx2 && workspace, "ucfvit_instnorm_cl_bwd2: null pointer");
     hipStream_t s = (hipStream_t)stream;
     const int ch = cl_chunks_of(S, C);

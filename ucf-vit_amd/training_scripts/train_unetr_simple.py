@@ -23,7 +23,7 @@ from UCF_VIT._hip import functional as HF
 
 def dice_ce_loss(logits, label, smooth=1e-5):
     """monai DiceCELoss(to_onehot_y, softmax, squared_pred) (reference :38): DiceLoss over softmax probabilities with the squared-prediction
-    denominator, mean over batch and classes, + CrossEntropy — one fused HIP kernel pair (ucfvit_dice_ce: forward and gradient)"""
+    denominator, mean over batch and classes, + CrossEntropy — one HIP call (ucfvit_dice_ce: loss and gradient, the decoder's channels-last logits read in place)"""
     return HF.dice_ce(logits.float(), label.view(label.shape[0], *label.shape[2:]) if label.dim() == logits.dim() else label, smooth, smooth)
 
 
