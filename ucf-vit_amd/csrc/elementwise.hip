@@ -574,9 +574,10 @@ extern "C" int ucfvit_mae_mask(const float* noise, int64_t* ids_shuffle, int64_t
 
 static int rows_copy(const void* a, const int64_t* idx, void* b, int64_t B, int64_t L, int64_t R, int64_t D, int64_t idx_stride,
                      int dtype, int scatter, hipStream_t s, const char* name) {
-    UCF_CHECK_ARG(a && idx && b, "%s: null pointer", name);
     UCF_CHECK_ARG(DTYPE_OK(dtype), "%s: bad dtype %d", name, dtype);
     UCF_CHECK_ARG(B >= 0 && L > 0 && R >= 0 && R <= L && D > 0 && idx_stride >= R, "%s: bad shape", name);
+    if (B == 0 || (R == 0 && !scatter)) return UCFVIT_OK;  // nothing to write (pointers may be NULL)
+    UCF_CHECK_ARG(b && (R == 0 || (a && idx)), "%s: null pointer", name);  // R = 0: a scatter still zeroes its output
     const int64_t row_bytes = D * (dtype == UCFVIT_F32 ? 4 : 2);
     if (scatter) {
         hipError_t e = hipMemsetAsync(b, 0, (size_t)(B * L * row_bytes), s);
@@ -764,12 +765,12 @@ extern "C" int ucfvit_adamw(float* p, const void* g, float* m, float* v, void* s
 }
 
 extern "C" int ucfvit_cast(const void* src, void* dst, int64_t n, int src_dtype, int dst_dtype, float scale, void* stream) {
-    UCF_CHECK_ARG(src && dst, "ucfvit_cast: null pointer");
     UCF_CHECK_ARG(DTYPE_OK(src_dtype) && DTYPE_OK(dst_dtype), "ucfvit_cast: bad dtype");
     UCF_CHECK_ARG(n >= 0, "ucfvit_cast: negative size");
+    if (n == 0) return UCFVIT_OK;                      // empty tensor (pointers may be NULL)
+    UCF_CHECK_ARG(src && dst, "ucfvit_cast: null pointer");
     const size_t sa = src_dtype == UCFVIT_F32 ? 16 : 8, da = dst_dtype == UCFVIT_F32 ? 16 : 8;
     UCF_CHECK_ARG(((uintptr_t)src) % sa == 0 && ((uintptr_t)dst) % da == 0, "ucfvit_cast: misaligned pointer");
-    if (n == 0) return UCFVIT_OK;
     hipStream_t s = (hipStream_t)stream;
     const unsigned grid = ew_grid((n + 3) / 4);
 #define CAST(S, Dd) hipLaunchKernelGGL((cast_kernel<S, Dd>), dim3(grid), dim3(256), 0, s, (const S*)src, (Dd*)dst, n, scale)

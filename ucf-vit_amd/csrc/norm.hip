@@ -367,7 +367,7 @@ extern "C" int64_t ucfvit_colsum_workspace(int64_t M, int64_t N) { return (int64
 
 extern "C" int ucfvit_colsum(const void* x, float* out, int64_t M, int64_t N, int64_t ldx, int accumulate, void* workspace,
                              int dtype, void* stream) {
-    UCF_CHECK_ARG(x && out, "ucfvit_colsum: null pointer");
+    UCF_CHECK_ARG(out && (x || M == 0), "ucfvit_colsum: null pointer");  // M = 0: out = 0 (or unchanged when accumulating)
     UCF_CHECK_ARG(M >= 0 && N > 0 && ldx >= N, "ucfvit_colsum: bad shape");
     hipStream_t s = (hipStream_t)stream;
     const int epv = dtype == UCFVIT_F32 ? 4 : 8;
