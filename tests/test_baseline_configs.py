@@ -50,7 +50,8 @@ def _attn_ref(qkv, do, B, N, H, dh):
 def test_streaming_attention_bf16_vs_fp32_math(N, dh, B, H):
     """every dispatch of the streaming kernels in bf16 (N > 256: UNETR volumes, the vit_tiny16_256 workload; head dim 128 at any N):
     forward, log-sum-exp and all three gradients.  Tolerance 2e-2 of the largest reference magnitude (bf16 probabilities / outputs),
-    the same bound the resident kernels are held to."""
+    the same bound the resident kernels are held to.
+    The per-element bounds and the exact cases of these kernels live in tests/test_attention_ops.py."""
     from UCF_VIT._hip import ops
     gen = torch.Generator().manual_seed(N * 131 + dh)
     qkv = torch.randn(B * N, 3 * H * dh, generator=gen).bfloat16().to(DEV)

@@ -401,7 +401,8 @@ def test_attention_kernels_all_short_sequence_paths(N, dh):
     """bf16 attention forward + backward against fp32 softmax(QK^T/sqrt(dh))V on the SAME bf16 inputs, over every dispatch of the
     short-sequence kernels: fused resident forward (N <= 208) / resident forward (N <= 256) and the fused backward for 4 / 8 / 13 / 16
     blocks of 16 tokens (two blocks per wave pass: even and odd block counts, a single block, a single token), head dims 64 and 32.
-    Tolerance 2e-2 of the largest reference magnitude (bf16 probabilities and outputs)."""
+    Tolerance 2e-2 of the largest reference magnitude (bf16 probabilities and outputs).
+    The per-element bounds and the exact cases of these kernels live in tests/test_attention_ops.py."""
     from UCF_VIT._hip import ops
     B, H = 3, 2
     gen = torch.Generator().manual_seed(N * 100 + dh)
@@ -523,7 +524,8 @@ def test_adaptive_pos_embedding_fwd_bwd(dtype, B, S, D, kin, has_cls):
 @pytest.mark.parametrize("V,R,D,dh", [(3, 24, 64, 32), (5, 1000, 1024, 64), (2, 333, 768, 64), (7, 130, 256, 128), (1, 50, 192, 64)])
 def test_variable_aggregation_attention_fwd_bwd(dtype, V, R, D, dh):
     """softmax over the V variables of every token row with one shared query (building_blocks.py:336-366) against fp64 torch on the
-    same rounded inputs; D / vector width not a divisor of 256 (768) and a single variable (softmax = 1) included"""
+    same rounded inputs; D / vector width not a divisor of 256 (768) and a single variable (softmax = 1) included
+    The per-element bounds and the exact cases of these kernels live in tests/test_attention_ops.py."""
     from UCF_VIT._hip import ops
     gen = torch.Generator().manual_seed(V * 1000 + R + D)
     kv = torch.randn(V * R, 2 * D, generator=gen)

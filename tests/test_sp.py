@@ -84,7 +84,8 @@ def test_seq_parallel_block_equals_unsharded(dtype_name, tol):
 def test_cross_block_attention_and_merge(dtype_name, tol, B, Nq, Nk_blocks, H, dh):
     """the ring building blocks: attention of Nq queries against key blocks held in OTHER buffers, folded by the log-sum-exp merge,
     equals softmax(QK^T / sqrt(dh)) V over the concatenated keys; the per-block backward, given the FULL log-sum-exp and output,
-    accumulates exactly the full gradients (fp32 accumulators)."""
+    accumulates exactly the full gradients (fp32 accumulators).
+    The per-element bounds and the exact cases of these kernels live in tests/test_attention_ops.py."""
     from UCF_VIT._hip import ops
     dtype = getattr(torch, dtype_name)
     dev = "cuda"

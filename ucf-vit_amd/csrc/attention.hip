@@ -469,8 +469,8 @@ __global__ __launch_bounds__(AT_THREADS) void attn_bwd_dq_kernel(const AttnArgs<
                     Mma16<T>::mma(dp[qb], vf, dof[qb][c]);   // dPᵀ[key][q]
                 }
             }
-            // keys beyond N need no mask here: their K rows were zero-filled by tile_load, so whatever dS they get multiplies zeros in
-            // dQ += dS K (and it is finite: S = dP = 0 for them)
+            // keys beyond N: their K rows were zero-filled by tile_load, so a finite dS multiplies zeros in dQ += dS K; it is finite only
+            // while -lse < 128 (S = dP = 0, P = 2^-lse), so the ragged tile clears them below
 #pragma unroll
             for (int qb = 0; qb < QB; ++qb)
 #pragma unroll
@@ -478,6 +478,16 @@ __global__ __launch_bounds__(AT_THREADS) void attn_bwd_dq_kernel(const AttnArgs<
                     const float p = __builtin_amdgcn_exp2f(fmaf(s[qb][r], scale_log2e, -my_lse[qb]));
                     ds[qb][kb][r] = p * (dp[qb][r] - my_delta[qb]);
                 }
+        }
+        if (__builtin_expect((kt + 1) * KT > N, 0)) {      // a row whose lse is below -128 has P = inf on a padding key: inf * 0 = NaN in dQ
+            asm volatile("" ::: "memory");                 // keep this a branch, as in the forward
+#pragma unroll
+            for (int qb = 0; qb < QB; ++qb)
+#pragma unroll
+                for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (kt * KT + kb * 16 + 4 * g + r >= N) ds[qb][kb][r] = 0.f;
         }
         // dQᵀ[d][q] += Kᵀ[d][key] · dSᵀ[key][q]
         frag_t f[QB][A::NRC];
@@ -927,6 +937,7 @@ extern "C" int ucfvit_attention_fwd(const void* qkv, void* out, float* lse, int6
 
 extern "C" int ucfvit_attention_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* delta_ws,
                                     int64_t B, int64_t N, int64_t H, int64_t dh, float scale, int dtype, void* stream) {
+    if (B == 0) return UCFVIT_OK;                      // empty batch (pointers may be NULL)
     UCF_CHECK_ARG(qkv && out && dout && lse && dqkv && delta_ws, "ucfvit_attention_bwd: null pointer");
     int rc = check_attn_args("ucfvit_attention_bwd", B, N, H, dh, dtype);
     if (rc) return rc;
@@ -941,6 +952,7 @@ extern "C" int ucfvit_attention_bwd_colsum_supported(int64_t B, int64_t N, int64
 
 extern "C" int ucfvit_attention_bwd_colsum(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* delta_ws,
                                            float* colsum_partial, int64_t B, int64_t N, int64_t H, int64_t dh, float scale, int dtype, void* stream) {
+    if (B == 0) return UCFVIT_OK;                      // empty batch (pointers may be NULL)
     UCF_CHECK_ARG(qkv && out && dout && lse && dqkv && delta_ws && colsum_partial, "ucfvit_attention_bwd_colsum: null pointer");
     int rc = check_attn_args("ucfvit_attention_bwd_colsum", B, N, H, dh, dtype);
     if (rc) return rc;
