@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define UCFVIT_ABI_VERSION 14
+#define UCFVIT_ABI_VERSION 15
 
 #define UCFVIT_OK 0
 #define UCFVIT_ERR_INVALID_ARGUMENT (-1)
@@ -322,6 +322,42 @@ int ucfvit_patch_mse(const void* pred, const float* img, const float* mask, floa
 int ucfvit_adamw(float* p, const void* g, float* m, float* v, void* shadow_bf16, int64_t n, float lr, float beta1,
                  float beta2, float eps, float weight_decay, float bias_corr1, float bias_corr2, float grad_scale,
                  int grad_dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Dynamic loss scaling with on-device skipping of non-finite steps (the reference's bf16 policy: ShardedGradScaler(init_scale=8192,
+ * growth_interval=100) and its floor of 128, training_scripts/train_masked_fsdp.py:417-419,601-606; update rule = torch's
+ * _amp_update_scale_, check = torch's _amp_foreach_non_finite_check_and_unscale_ without the in-place rewrite of the gradients).
+ *
+ * All scaler state is ONE device array of UCFVIT_GS_STATE_FLOATS fp32 owned by the caller; the host never has to read it during a step:
+ *   [SCALE] loss scale   [INV_SCALE] (float)(1.0 / scale)   [FOUND_INF] 0 or 1, ORed by the check, cleared by the update
+ *   [GROWTH_TRACKER] consecutive applied steps since the scale last changed   [APPLIED_STEPS] / [SKIPPED_STEPS] counts (fp32: exact to 2^24)
+ *   [GROWTH_FACTOR] [BACKOFF_FACTOR] [GROWTH_INTERVAL] [MIN_SCALE] constants (MIN_SCALE 0: no floor); the rest is reserved (zero).
+ *
+ * grad_nonfinite:  one read-only pass; sets state[FOUND_INF] = 1 if any g[i] * mult * state[INV_SCALE] is +-Inf or NaN (the value
+ *                  adamw_scaled consumes when mult is its grad_scale).  Never clears the flag: calls over several segments OR together.
+ * adamw_scaled:    ucfvit_adamw, except that (1) every workgroup returns before touching p, m, v or the shadow when state[FOUND_INF] is set,
+ *                  (2) gradients are multiplied by grad_scale * state[INV_SCALE], (3) the bias corrections 1 - beta^t are formed on the device, in
+ *                  double from the double betas and rounded once to fp32, with t = state[APPLIED_STEPS] + 1: a skipped step does not advance t.
+ * grad_scaler_update: after the adamw_scaled launches of a step.  FOUND_INF set: scale *= BACKOFF_FACTOR, tracker = 0, SKIPPED_STEPS += 1.
+ *                  Otherwise APPLIED_STEPS += 1, tracker += 1, and when the tracker reaches GROWTH_INTERVAL it returns to 0 and scale becomes
+ *                  scale * GROWTH_FACTOR unless that is not finite.  Then scale = max(scale, MIN_SCALE), INV_SCALE is recomputed, FOUND_INF cleared.
+ * ------------------------------------------------------------------------------------------------------ */
+#define UCFVIT_GS_SCALE 0
+#define UCFVIT_GS_INV_SCALE 1
+#define UCFVIT_GS_FOUND_INF 2
+#define UCFVIT_GS_GROWTH_TRACKER 3
+#define UCFVIT_GS_APPLIED_STEPS 4
+#define UCFVIT_GS_SKIPPED_STEPS 5
+#define UCFVIT_GS_GROWTH_FACTOR 6
+#define UCFVIT_GS_BACKOFF_FACTOR 7
+#define UCFVIT_GS_GROWTH_INTERVAL 8
+#define UCFVIT_GS_MIN_SCALE 9
+#define UCFVIT_GS_STATE_FLOATS 16
+int ucfvit_grad_nonfinite(const void* g, int64_t n, int dtype, float mult, float* state, void* stream);
+int ucfvit_adamw_scaled(float* p, const void* g, float* m, float* v, void* shadow_bf16, int64_t n, float lr, double beta1,
+                        double beta2, float eps, float weight_decay, float grad_scale, int grad_dtype, const float* state,
+                        void* stream);
+int ucfvit_grad_scaler_update(float* state, void* stream);
 
 /* dtype conversion / scaling helpers (fp32 master → bf16 shadow cast; bf16 gradient transport for the DP all-reduce) */
 int ucfvit_cast(const void* src, void* dst, int64_t n, int src_dtype, int dst_dtype, float scale, void* stream);

@@ -5,13 +5,16 @@ missing or a call fails, a RuntimeError is raised with the library's own message
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int64, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_void_p
 
 F32, BF16 = 0, 1
 LAYOUT_KC, LAYOUT_KS = 0, 1
 ACT_NONE, ACT_GELU, ACT_GELU_GRAD, ACT_GELU_SAVE_DERIV, ACT_MUL_AUX = 0, 1, 2, 3, 4
 GEMM_SCHED_BYTES = 1024
-ABI_VERSION = 14
+# loss-scaler state block (UCFVIT_GS_* of include/ucfvit_hip.h)
+GS_SCALE, GS_INV_SCALE, GS_FOUND_INF, GS_GROWTH_TRACKER, GS_APPLIED_STEPS, GS_SKIPPED_STEPS = 0, 1, 2, 3, 4, 5
+GS_GROWTH_FACTOR, GS_BACKOFF_FACTOR, GS_GROWTH_INTERVAL, GS_MIN_SCALE, GS_STATE_FLOATS = 6, 7, 8, 9, 16
+ABI_VERSION = 15
 
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))  # .../ucf-vit_amd
 # UCFVIT_HIP_LIB: an alternative build of the same library (A/B measurements of kernel variants); never a non-HIP fallback
@@ -35,7 +38,7 @@ class GemmDesc(Structure):
 
 
 # name -> (restype, argtypes); must list every symbol of include/ucfvit_hip.h (tests/test_abi.py checks this)
-_P, _I64, _I, _F = c_void_p, c_int64, c_int, c_float
+_P, _I64, _I, _F, _D = c_void_p, c_int64, c_int, c_float, c_double
 SIGNATURES = {
     "ucfvit_abi_version": (c_int, []),
     "ucfvit_mfma_probe": (_I64, [_P, _I, _P]),
@@ -109,6 +112,9 @@ SIGNATURES = {
     "ucfvit_unshuffle_bwd": (c_int, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _P, _I, _P]),
     "ucfvit_patch_mse": (c_int, [_P, _P, _P, _P, _P, _I64, _I64, POINTER(c_int64), _I, _I64, _F, _P, _I, _P]),
     "ucfvit_adamw": (c_int, [_P, _P, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _F, _F, _F, _I, _P]),
+    "ucfvit_grad_nonfinite": (c_int, [_P, _I64, _I, _F, _P, _P]),
+    "ucfvit_adamw_scaled": (c_int, [_P, _P, _P, _P, _P, _I64, _F, _D, _D, _F, _F, _F, _I, _P, _P]),
+    "ucfvit_grad_scaler_update": (c_int, [_P, _P]),
     "ucfvit_cast": (c_int, [_P, _P, _I64, _I, _I, _F, _P]),
     "ucfvit_transpose_batched": (c_int, [_P, _P, _P, _I64, _I64, _P]),
 }

@@ -1069,6 +1069,32 @@ def adamw(p, g, m, v, shadow, lr, beta1, beta2, eps, weight_decay, step, grad_sc
                             weight_decay, bc1, bc2, grad_scale, dt(g), _stream()), "ucfvit_adamw")
 
 
+def _gs_state(state):
+    if state.dtype != torch.float32 or state.numel() < _l.GS_STATE_FLOATS or not state.is_contiguous():
+        raise ValueError(f"loss-scaler state must be a contiguous float32 tensor of {_l.GS_STATE_FLOATS} elements")
+    return _chk(state, "grad scaler state")
+
+
+def grad_nonfinite(g, state, mult=1.0):
+    """state[GS_FOUND_INF] |= any(g * mult * state[GS_INV_SCALE] is Inf or NaN); read-only over g, no host synchronisation"""
+    L = _l.load()
+    _chk(g, "grad_nonfinite.g")
+    _l.check(L.ucfvit_grad_nonfinite(g.data_ptr(), g.numel(), dt(g), mult, _gs_state(state).data_ptr(), _stream()), "ucfvit_grad_nonfinite")
+
+
+def adamw_scaled(p, g, m, v, shadow, lr, beta1, beta2, eps, weight_decay, state, grad_scale=1.0):
+    """adamw under a loss scaler: skipped on the device when state[GS_FOUND_INF] is set, gradients times grad_scale * state[GS_INV_SCALE],
+    bias corrections from state[GS_APPLIED_STEPS] + 1"""
+    L = _l.load()
+    _l.check(L.ucfvit_adamw_scaled(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _p(shadow), p.numel(), lr, beta1, beta2, eps,
+                                   weight_decay, grad_scale, dt(g), _gs_state(state).data_ptr(), _stream()), "ucfvit_adamw_scaled")
+
+
+def grad_scaler_update(state):
+    L = _l.load()
+    _l.check(L.ucfvit_grad_scaler_update(_gs_state(state).data_ptr(), _stream()), "ucfvit_grad_scaler_update")
+
+
 def cast(src, dst, scale=1.0):
     L = _l.load()
     _l.check(L.ucfvit_cast(src.data_ptr(), dst.data_ptr(), src.numel(), dt(src), dt(dst), scale, _stream()), "ucfvit_cast")

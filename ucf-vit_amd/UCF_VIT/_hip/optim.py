@@ -4,10 +4,15 @@ Semantics = torch.optim.AdamW (reference: utils/misc.py:58-84, two param groups)
 are consecutive slots of one HipParamStore and every one of them received its gradient in the store's flat gradient
 buffer, the whole group is ONE launch over the flat segment (which also rewrites the bf16 shadow weights in the
 same pass); otherwise it falls back to one launch per parameter.
+
+Under a HipGradScaler (grad_scaler.py) the same two paths run ucfvit_grad_nonfinite over every gradient segment of every group first and
+then ucfvit_adamw_scaled, which skips itself on the device when the check fired (step_scaled below).  The host-side step counters then
+count CALLS; the number of applied steps, which the bias corrections use, lives in the scaler's device state.
 """
 import torch
 
 from . import ops
+from .lib import GS_APPLIED_STEPS as _GS_APPLIED, GS_SKIPPED_STEPS as _GS_SKIPPED
 
 
 class HipAdamW(torch.optim.Optimizer):
@@ -19,12 +24,34 @@ class HipAdamW(torch.optim.Optimizer):
         # state_dict() then serialises only the per-parameter {step, exp_avg, exp_avg_sq} entries (views into these buffers) — the
         # torch.optim.AdamW layout the reference's checkpoints hold (train_class_simple.py:364-388) — and nothing keyed by an id()
         self._flat = {}
+        # loss-scaler binding (step_scaled): the scaler's device state, and its skipped-step count when the host counters were last equal
+        # to the applied-step count (construction or load_state_dict)
+        self._gs, self._gs_skip_base, self._gs_bound = None, None, False
 
     def load_state_dict(self, state_dict):
         """accepts a torch.optim.AdamW / HipAdamW state_dict; the flat buffers are rebuilt from the per-parameter entries on the next
         step (the loaded tensors are copied in, so a checkpoint mapped to the CPU ends up in device memory before any kernel sees it)"""
         super().load_state_dict(state_dict)
         self._flat = {}
+        self._gs_bound = False          # the next scaled step seeds the scaler's applied-step count from the loaded `step`
+
+    def state_dict(self):
+        """torch.optim.AdamW layout.  Under a loss scaler `step` is the number of APPLIED steps (calls minus the steps the device skipped):
+        one synchronisation here, none on the step path."""
+        sd = super().state_dict()
+        if self._gs is None or not self._gs_bound:
+            return sd
+        skipped = float((self._gs[_GS_SKIPPED] - self._gs_skip_base).item())
+        if skipped:
+            sd["state"] = {k: dict(v, step=v["step"] - skipped) if "step" in v else v for k, v in sd["state"].items()}
+        return sd
+
+    def _bind_scaler(self, gs):
+        """host step counters == applied steps at this point (nothing skipped yet, or a state_dict just loaded): hand that count to the
+        device, where the bias corrections are formed, and remember the scaler's skipped-step count.  Device-side writes only."""
+        steps = [int(s["step"]) for s in self.state.values() if "step" in s] + [e["step"] for e in self._flat.values()]
+        gs[_GS_APPLIED:_GS_APPLIED + 1].fill_(float(max(steps, default=0)))
+        self._gs, self._gs_skip_base, self._gs_bound = gs, gs[_GS_SKIPPED].clone(), True
 
     @staticmethod
     def _adopt_foreign_grads(group):
@@ -63,6 +90,35 @@ class HipAdamW(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        self._update(None)
+        return loss
+
+    @torch.no_grad()
+    def step_scaled(self, gs):
+        """one step under a loss scaler whose device state is `gs` (HipGradScaler.step calls this): the non-finite check over ALL gradient
+        segments of ALL groups first, then the AdamW launches, so no group updates before the flag is final.  No host synchronisation."""
+        if self._gs is not gs or not self._gs_bound:
+            self._bind_scaler(gs)
+        for group in self.param_groups:
+            if not group["params"]:
+                continue
+            self._adopt_foreign_grads(group)
+            run = self._flat_run(group)
+            if run is not None:
+                ops.grad_nonfinite(run[0].flat_g[run[1]:run[2]], gs, self.grad_scale)
+                continue
+            for p in group["params"]:
+                if p.grad is not None:
+                    ops.grad_nonfinite(p.grad if p.grad.is_contiguous() else p.grad.contiguous(), gs, self.grad_scale)
+        self._update(gs)
+
+    def _adamw(self, gs, p, g, m, v, shadow, lr, b1, b2, eps, wd, step):
+        if gs is None:
+            ops.adamw(p, g, m, v, shadow, lr, b1, b2, eps, wd, step, self.grad_scale)
+        else:
+            ops.adamw_scaled(p, g, m, v, shadow, lr, b1, b2, eps, wd, gs, self.grad_scale)
+
+    def _update(self, gs):
         for group in self.param_groups:
             if not group["params"]:
                 continue
@@ -93,12 +149,11 @@ class HipAdamW(torch.optim.Optimizer):
                                              exp_avg_sq=ent["v"][o:o + p.numel()].view(p.shape))
                 ent["step"] += 1
                 shadow = st.flat_s[lo:hi] if st.flat_s is not None else None
-                ops.adamw(st.flat_p[lo:hi], st.flat_g[lo:hi], ent["m"], ent["v"], shadow, lr, b1, b2, eps, wd, ent["step"],
-                          self.grad_scale)
+                self._adamw(gs, st.flat_p[lo:hi], st.flat_g[lo:hi], ent["m"], ent["v"], shadow, lr, b1, b2, eps, wd, ent["step"])
                 for p in group["params"]:
                     self.state[p]["step"] += 1
                 if shadow is not None:
-                    st.note_shadow_fresh()
+                    st.note_shadow_fresh()      # (also after a skipped step: the shadow still equals p, neither moved)
                 continue
             for p in group["params"]:
                 if p.grad is None:
@@ -110,9 +165,8 @@ class HipAdamW(torch.optim.Optimizer):
                     s["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                 s["step"] += 1
                 g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
-                ops.adamw(p.data, g, s["exp_avg"], s["exp_avg_sq"], None, lr, b1, b2, eps, wd, int(s["step"]), self.grad_scale)
+                self._adamw(gs, p.data, g, s["exp_avg"], s["exp_avg_sq"], None, lr, b1, b2, eps, wd, int(s["step"]))
                 p._version  # (kernel wrote p in place; bf16 shadows are re-cast lazily via the store signature)
                 slot = getattr(p, "_ucf_slot", None)
                 if slot is not None:
                     slot[0]._shadow_sig = None
-        return loss

@@ -26,6 +26,13 @@ def _tp(size, group):
     return HF.TP(group, size) if size > 1 else None
 
 
+def _mark_sharded(module, size):
+    """tensor-parallel weights differ from rank to rank: HipGradScaler refuses to take a per-rank skip decision over them"""
+    if size > 1:
+        for p in module.parameters():
+            p._ucf_sharded = "tensor"
+
+
 class Mlp(_S.Mlp):
     def __init__(self, in_features, hidden_features=None, out_features=None, act_layer=nn.GELU, norm_layer=None, bias=True,
                  drop=0.0, use_conv=False, tensor_par_size: int = 1, tensor_par_group: Optional[dist.ProcessGroup] = None):
@@ -35,6 +42,7 @@ class Mlp(_S.Mlp):
         if norm_layer is not None:
             self.norm = norm_layer(hidden_features)
         self.tensor_par_size, self.tensor_par_group = tensor_par_size, tensor_par_group
+        _mark_sharded(self, tensor_par_size)
 
     def forward(self, x):
         _no_dropout(self.drop1.p, self.training, "Mlp.drop")
@@ -61,6 +69,7 @@ class Attention(nn.Module):
         self.attn_drop = nn.Dropout(attn_drop)
         self.proj = nn.Linear(dim // tensor_par_size, dim)
         self.proj_drop = nn.Dropout(proj_drop)
+        _mark_sharded(self, tensor_par_size)
 
     def _fusable(self):
         return isinstance(self.q_norm, nn.Identity) and isinstance(self.k_norm, nn.Identity)

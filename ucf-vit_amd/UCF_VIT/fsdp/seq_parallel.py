@@ -290,6 +290,8 @@ class SeqParallelBlock(nn.Module):
         super().__init__()
         self.block = block
         self.spg = seq_par if isinstance(seq_par, SeqParallelGroups) else _PlainGroup(seq_par)
+        for p in block.parameters():
+            p._ucf_sharded = "sequence"     # gradients are per-token-shard partial sums: HipGradScaler refuses a per-rank skip decision
 
     def forward(self, x):
         b = self.block

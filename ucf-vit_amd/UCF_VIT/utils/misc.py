@@ -1,10 +1,11 @@
 """Hot-path helpers of the reference's utils/misc.py, restated for the HIP build:
 patchify / unpatchify (misc.py:14-56, MAE target layout), configure_optimizer (:58-84), configure_scheduler (:86-96),
-init_par_groups (:129-238).  File-system / dataloader helpers of the reference module are out of scope.
+init_par_groups (:129-238); configure_grad_scaler restates the scaler of training_scripts/train_masked_fsdp.py:417-419,606.  File-system / dataloader helpers of the reference module are out of scope.
 """
 import torch
 import torch.distributed as dist
 
+from .._hip.grad_scaler import HipGradScaler
 from .._hip.optim import HipAdamW
 from .._hip.params import is_no_decay
 from .lr_scheduler import LinearWarmupCosineAnnealingLR
@@ -48,6 +49,12 @@ def configure_optimizer(model, lr, beta_1, beta_2, weight_decay):
 
 def configure_scheduler(optimizer, warmup_steps, max_steps, warmup_start_lr, eta_min):
     return LinearWarmupCosineAnnealingLR(optimizer, warmup_steps, max_steps, warmup_start_lr, eta_min)
+
+
+def configure_grad_scaler(enabled):
+    """the reference's dynamic loss scaler: ShardedGradScaler(init_scale=8192, growth_interval=100), and after every update a scale
+    below 128 is raised back to 128 (train_masked_fsdp.py:417-419,606)"""
+    return HipGradScaler(init_scale=8192, growth_interval=100, min_scale=128, enabled=enabled)
 
 
 def init_par_groups(world_rank, data_par_size, tensor_par_size, seq_par_size, fsdp_size, simple_ddp_size):

@@ -139,13 +139,17 @@ class SyntheticSeqLoader:
             yield seq.to(dev, non_blocking=True), torch.cat([size, pos], dim=-1).to(dev, non_blocking=True), label.to(dev, non_blocking=True)
 
 
-def save_checkpoint(conf, epoch, model, optimizer, scheduler, loss_list, rank):
-    """alternating <name>_even.ckpt / _odd.ckpt on rank 0 (reference :364-388), same dictionary keys"""
+def save_checkpoint(conf, epoch, model, optimizer, scheduler, loss_list, rank, scaler=None):
+    """alternating <name>_even.ckpt / _odd.ckpt on rank 0 (reference :364-388), same dictionary keys; with an active loss scaler also
+    `scaler_state_dict`"""
     t = conf["trainer"]
     if rank == 0:
         os.makedirs(t["checkpoint_path"], exist_ok=True)
-        torch.save({"epoch": epoch, "model_state_dict": model.state_dict(), "optimizer_state_dict": optimizer.state_dict(),
-                    "scheduler_state_dict": scheduler.state_dict(), "loss_list": loss_list},
+        ck = {"epoch": epoch, "model_state_dict": model.state_dict(), "optimizer_state_dict": optimizer.state_dict(),
+              "scheduler_state_dict": scheduler.state_dict(), "loss_list": loss_list}
+        if scaler is not None and scaler.is_enabled():
+            ck["scaler_state_dict"] = scaler.state_dict()
+        torch.save(ck,
                    os.path.join(t["checkpoint_path"], f"{t['checkpoint_filename']}_{'even' if epoch % 2 == 0 else 'odd'}.ckpt"))
     dist.barrier()
 
@@ -185,7 +189,8 @@ def load_pretrained_mae_encoder(model, mae_state_dict):
     return copied
 
 
-def maybe_resume(conf, model, optimizer, scheduler):
+def maybe_resume(conf, model, optimizer, scheduler, scaler=None):
+    """a checkpoint written without a loss scaler resumes under one with the scaler's initial scale"""
     t = conf["trainer"]
     if not t.get("resume_from_checkpoint", False):
         return 0, []
@@ -193,6 +198,8 @@ def maybe_resume(conf, model, optimizer, scheduler):
     model.load_state_dict(ck["model_state_dict"])
     optimizer.load_state_dict(ck["optimizer_state_dict"])
     scheduler.load_state_dict(ck["scheduler_state_dict"])
+    if scaler is not None and scaler.is_enabled() and ck.get("scaler_state_dict"):
+        scaler.load_state_dict(ck["scaler_state_dict"])
     return ck["epoch"] + 1, ck["loss_list"]
 
 

@@ -10,7 +10,7 @@ from _common import (SyntheticLoader, SyntheticSeqLoader, StepTimer, init_distri
 from UCF_VIT.simple.arch import MAE
 from UCF_VIT.utils.fused_attn import FusedAttn
 from UCF_VIT.utils.metrics import patch_mse_loss, seq_mse_loss
-from UCF_VIT.utils.misc import configure_optimizer, configure_scheduler
+from UCF_VIT.utils.misc import configure_grad_scaler, configure_optimizer, configure_scheduler
 from UCF_VIT._hip.ddp import HipDataParallel
 
 
@@ -37,7 +37,10 @@ def main(device, local_rank, rank, world):
     net = HipDataParallel(model)
     optimizer = configure_optimizer(model, float(m["lr"]), float(m["beta_1"]), float(m["beta_2"]), float(m["weight_decay"]))   # PyYAML reads "1e-5" as str
     scheduler = configure_scheduler(optimizer, int(m["warmup_steps"]), int(m["max_steps"]), float(m["warmup_start_lr"]), float(m["eta_min"]))
-    epoch_start, loss_list = maybe_resume(conf, net, optimizer, scheduler)
+    # dynamic loss scaling of the reference's bf16 policy (train_masked_fsdp.py:417-419,601-606), folded into this entry point like the
+    # rest of that script's bf16 semantics; off unless the config says `model: use_grad_scaler: True`
+    scaler = configure_grad_scaler(bool(m.get("use_grad_scaler", False)))
+    epoch_start, loss_list = maybe_resume(conf, net, optimizer, scheduler, scaler)
     variables = d["dict_in_variables"][d["dataset"]]
     loss_fn = conf["trainer"].get("loss_fn", a.get("loss_fn", "MSE"))
     if margs["adaptive_patching"]:
@@ -57,15 +60,20 @@ def main(device, local_rank, rank, world):
             else:
                 loss, _, _ = training_step(data, variables, net, margs["patch_size"], margs["twoD"], loss_fn)
             epoch_loss += loss.detach()
-            loss.backward()
-            optimizer.step()
+            if scaler.is_enabled():
+                scaler.scale(loss).backward()
+                scaler.step(optimizer)
+                scaler.update()
+            else:
+                loss.backward()
+                optimizer.step()
             optimizer.zero_grad()
             scheduler.step()
             timer.tick(data.shape[0] * world)
         loss_list.append(epoch_loss)
         if rank == 0:
             print(f"epoch: {epoch} epoch_loss {epoch_loss.item():.4f} images/s {timer.rate():.1f}", flush=True)
-        save_checkpoint(conf, epoch, net, optimizer, scheduler, loss_list, rank)
+        save_checkpoint(conf, epoch, net, optimizer, scheduler, loss_list, rank, scaler)
 
 
 if __name__ == "__main__":
