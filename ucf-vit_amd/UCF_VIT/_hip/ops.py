@@ -91,8 +91,9 @@ def mfma_probe(iters=10000):
 
 # ------------------------------------------------------------------------------------------------ GEMM
 def gemm(A, B, M, N, K, a_layout, b_layout, out=None, out_dtype=None, bias=None, residual=None, act=ACT_NONE,
-         aux_in=None, aux_out=None, accumulate=False, alpha=1.0, c_colsum=None, c_colsum_accumulate=False):
+         aux_in=None, aux_out=None, accumulate=False, alpha=1.0, c_colsum=None, c_colsum_accumulate=False, split_k_workspace=True):
     """C[M,N] = epilogue(alpha * op(A)·op(B)); A, B are 2-D row-major tensors (see include/ucfvit_hip.h).
+    split_k_workspace=False withholds the split-K scratch (desc.workspace = NULL): the library then runs the problem un-split.
     c_colsum: optional fp32 [N] tensor that receives (+)= the column sums of C — as a by-product of the epilogue where the library
     has one (desc.c_colsum_partial + ucfvit_reduce_rows), else by a separate ucfvit_colsum pass over C."""
     L = _l.load()
@@ -124,7 +125,7 @@ def gemm(A, B, M, N, K, a_layout, b_layout, out=None, out_dtype=None, bias=None,
         if cs_rows > 0:
             cs_part = workspace(cs_rows * N * 4, A.device)
             d.c_colsum_partial = cs_part.data_ptr()
-    if act == ACT_NONE and bias is None and residual is None:      # only epilogue-free GEMMs (weight gradients) split K
+    if split_k_workspace and act == ACT_NONE and bias is None and residual is None:      # only epilogue-free GEMMs (weight gradients) split K
         need = L.ucfvit_gemm_workspace(ctypes.byref(d))
         if need > 0:
             ws = workspace(need, A.device)
@@ -140,7 +141,7 @@ def gemm(A, B, M, N, K, a_layout, b_layout, out=None, out_dtype=None, bias=None,
 
 
 def wgrad_grouped(items):
-    """items: list of (dy2 [M,N], x2 [M,K], out fp32 [N,K] or None, accumulate) -> list of dW tensors; ONE launch when groupable"""
+    """items: list of (dy2 [M,N], x2 [M,K], out [N,K] (fp32 or bf16) or None (fp32), accumulate) -> list of dW tensors; ONE launch when groupable"""
     L = _l.load()
     n = len(items)
     outs = []
@@ -158,7 +159,7 @@ def wgrad_grouped(items):
         d.M, d.N, d.K = N, K, Mtok
         d.lda, d.ldb, d.ldc, d.ldr, d.ldaux = dy2.stride(0), x2.stride(0), out.stride(0), 0, 0
         d.a_layout, d.b_layout = LAYOUT_KS, LAYOUT_KS
-        d.dtype, d.out_dtype = dt(dy2), F32
+        d.dtype, d.out_dtype = dt(dy2), dt(out)
         d.act, d.accumulate, d.alpha = ACT_NONE, 1 if acc else 0, 1.0
         d.workspace, d.workspace_bytes = None, 0
         d.c_colsum_partial = None
