@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define UCFVIT_ABI_VERSION 15
+#define UCFVIT_ABI_VERSION 16
 
 #define UCFVIT_OK 0
 #define UCFVIT_ERR_INVALID_ARGUMENT (-1)
@@ -122,6 +122,11 @@ int ucfvit_gemm(const ucfvit_gemm_desc* desc, void* stream);
 /* rows of desc->c_colsum_partial this problem would write (desc->c_colsum_partial itself is not read); 0: the kernel that runs this
  * problem has no such by-product and ucfvit_gemm rejects a non-NULL c_colsum_partial with UCFVIT_ERR_UNSUPPORTED. */
 int64_t ucfvit_gemm_colsum_rows(const ucfvit_gemm_desc* desc);
+/* which kernel ucfvit_gemm would run for this descriptor, as text ("v1-scalar", "v1-mfma", "g2-128", "g2-128-splitk", "g2-256",
+ * "g3-PLAIN+CS", "g3-GENERIC", "stagger-RESIDUAL", ...); reads workspace / workspace_bytes (split-K only with a sufficient workspace),
+ * c_colsum_partial ("+CS") and sched_state (keeps a launch off the staggered kernel) as ucfvit_gemm does, the descriptor's other pointers
+ * for their alignment only; host only, no HIP call; returns the length (the text is cut to cap - 1 characters), or < 0 */
+int ucfvit_gemm_route(const ucfvit_gemm_desc* desc, char* out, int64_t cap);
 /* out[n] (+)= sum_r partial[r][n]  (fp32, fixed order) — the second stage of every two-stage column sum of this library */
 int ucfvit_reduce_rows(const float* partial, float* out, int64_t rows, int64_t N, int accumulate, void* stream);
 

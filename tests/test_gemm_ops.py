@@ -44,8 +44,10 @@ C[:M,:N], aux_out[:M,:N] and the column-sum vector is untouched bit for bit.  M 
 with M, N > 0 is REFUSED loudly ("null operand pointer": a tensor without elements has a NULL data pointer, also as a view) and leaves C
 untouched: pinned.  An Inf in one row of A reaches that row of C only.
 
-Dispatch (read off ucfvit_gemm, plan2, dispatch_tile, launch3, ucfvit_gemm_stagger_try, ucfvit_gemm_grouped; _branch() restates it and is
-asserted to agree with ucfvit_gemm_colsum_rows > 0 and ucfvit_gemm_workspace > 0 on every case):
+Dispatch (read off gemm_route and its helpers in csrc/gemm_route.h, and ucfvit_gemm_grouped; _branch() restates it and is asserted to
+agree with ucfvit_gemm_colsum_rows > 0 and ucfvit_gemm_workspace > 0 on every case, and to equal the library's own answer,
+ucfvit_gemm_route, on the descriptor of every launch whose branch is named here; test_gemm_route_query_* ask it without a GPU, from
+descriptors made of fake addresses, for every entry of CASES with both tile schedules and under every UCFVIT_GEMM_STAGGER setting):
     v1-scalar     N % 4 != 0, unaligned ld, M*N < 256                          (5,2,64) (33,42,24) (33,40,20) (130,6,200)
     v1-mfma       fp32 any shape; bf16 with M, N or K < 128                     fp32 x 4 layouts (260,264,200); bf16 (100,264,256) (700,64,136) (304,384,64)
     g2-128        bf16, M,N,K >= 128, t256 < 192, no split                      4 layouts x bf16/fp32 out (696,384,136); every act (1000,520,200)
@@ -59,7 +61,8 @@ asserted to agree with ucfvit_gemm_colsum_rows > 0 and ucfvit_gemm_workspace > 0
 Not covered: ACT_MUL_AUX / GELU_GRAD with a bias on the staggered kernel (it declines them by design: the ping-pong kernel runs them);
 K = 0 with non-NULL operand pointers (ops cannot express it: a tensor without elements has a NULL data pointer).
 
-Measured on an MI355X: 217 GPU cases + 1 CPU case, 30 s (tests/test_gemm_stagger.py in the same run: 35 s, 31 s of it in its three forced
+Measured on an MI355X: 217 GPU cases + 7 CPU cases (the emulation, the route query over CASES and its five UCFVIT_GEMM_STAGGER children:
+11 s together without a GPU), 30 s (tests/test_gemm_stagger.py in the same run: 35 s, 31 s of it in its three forced
 children; the four forced children of this file take 4 - 5 s each, the three UCFVIT_GEMM_CUS children 7 s together).
   worst err / bound         C bf16   C fp32   aux_out   colsum
   v1-mfma                   0.995    0.21     0.99 (pre-activation)
@@ -372,6 +375,11 @@ def _stagger_able(c):
             and _plan2(c) is not None and _plan2(c)[0] and c.M <= 13000)
 
 
+def _forced_stagger_takes(c):
+    """of the cases above: the ones every forced setting UCFVIT_GEMM_STAGGER = 1 / 2 / 4 / 8 puts on the staggered kernel"""
+    return (c.act == NONE or (c.act == GELU_SD and not c.res) or (c.act == MUL_AUX and not c.res and not c.bias)) and not c.cs
+
+
 # ============================================================================================== operands
 def _values(g, kind, shape, scale, dtype, is_a=False):
     if kind == "int":
@@ -476,24 +484,67 @@ def _launch(c, o):
                     c_colsum=o.cs, c_colsum_accumulate=c.cs == "acc", split_k_workspace=c.ws)
 
 
-def _witness(c, o):
-    """the two ABI predicates on the very descriptor ops.gemm builds, against the restated dispatch"""
-    import ctypes
+def _desc(c, o=None):
+    """the descriptor ops.gemm builds for the case, workspace / c_colsum_partial / sched_state left NULL: from the operands o, or without a
+    GPU (o None) from fake addresses with the alignment and the leading dimensions _make gives them (never dereferenced: the queries below
+    are host code)"""
     from UCF_VIT._hip import lib as L
     d = L.GemmDesc()
-    d.A, d.B, d.C = o.A.data_ptr(), o.B.data_ptr(), o.C.data_ptr()
-    p = lambda t: None if t is None else t.data_ptr()
-    d.bias, d.residual = p(o.bias), p(o.res)
-    d.aux_in, d.aux_out = p(o.aux if c.aux_in else None), p(o.aux if c.has_aux_out else None)
+    aux_used = c.aux_in or c.has_aux_out
+    if o is not None:
+        p = lambda t: None if t is None else t.data_ptr()
+        d.A, d.B, d.C, d.bias, d.residual = o.A.data_ptr(), o.B.data_ptr(), o.C.data_ptr(), p(o.bias), p(o.res)
+        aux = p(o.aux) if aux_used else None
+        d.lda, d.ldb, d.ldc = o.A.stride(0), o.B.stride(0), o.C.stride(0)
+        d.ldr = o.res.stride(0) if o.res is not None else 0
+        d.ldaux = o.aux.stride(0) if o.aux is not None else 0
+    else:
+        es = 4 if c.f32 else 2
+        d.A, d.B, d.C = 1 << 30, 2 << 30, 3 << 30
+        d.bias = (4 << 30) + PADC * es if c.bias else None           # _make: a view PADC elements into its buffer
+        d.residual = 5 << 30 if c.res else None
+        aux = 6 << 30 if aux_used else None
+        d.lda, d.ldb, d.ldc = c.lda, c.ldb, c.N + PADC
+        d.ldr = c.N + PADC if c.res else 0
+        d.ldaux = c.N + PADC if aux_used else 0
+    d.aux_in, d.aux_out = aux if c.aux_in else None, aux if c.has_aux_out else None
     d.M, d.N, d.K = c.M, c.N, c.K
-    d.lda, d.ldb, d.ldc = o.A.stride(0), o.B.stride(0), o.C.stride(0)
-    d.ldr = o.res.stride(0) if o.res is not None else 0
-    d.ldaux = o.aux.stride(0) if o.aux is not None else 0
     d.a_layout, d.b_layout = c.la, c.lb
     d.dtype = L.F32 if c.f32 else L.BF16
     d.out_dtype = L.F32 if (c.f32 or c.out32) else L.BF16
     d.act, d.accumulate, d.alpha = c.act, 1 if c.acc else 0, c.alpha
     d.workspace, d.workspace_bytes, d.c_colsum_partial, d.sched_state = None, 0, None, None
+    return d
+
+
+def _lib_route(c, d, dyn):
+    """ucfvit_gemm_route on d with the three fields the name depends on set as ops.gemm sets them for the case: the split-K workspace
+    handed over where the case allows it and the epilogue is plain, c_colsum_partial where the column sums are asked for and the library
+    has rows for them, sched_state under the dynamic schedule (fake addresses: the query is host code)"""
+    import ctypes
+    from UCF_VIT._hip import lib as L
+    lib = L.load()
+    rows, ws = lib.ucfvit_gemm_colsum_rows(ctypes.byref(d)), lib.ucfvit_gemm_workspace(ctypes.byref(d))
+    if c.ws and ws > 0 and c.act == NONE and not c.bias and not c.res:
+        d.workspace, d.workspace_bytes = 7 << 30, ws
+    if c.cs and rows > 0:
+        d.c_colsum_partial = (8 << 30) + PADC * 4
+    if dyn:
+        d.sched_state = 9 << 30
+    buf = ctypes.create_string_buffer(64)
+    n = lib.ucfvit_gemm_route(ctypes.byref(d), buf, 64)
+    d.workspace, d.workspace_bytes, d.c_colsum_partial, d.sched_state = None, 0, None, None
+    assert 0 < n < 64, f"{c.id}: ucfvit_gemm_route returned {n}"
+    name = buf.value.decode()
+    assert len(name) == n
+    return name
+
+
+def _witness(c, o):
+    """the ABI's route queries on the very descriptor ops.gemm builds, against the restated dispatch"""
+    import ctypes
+    from UCF_VIT._hip import lib as L
+    d = _desc(c, o)
     lib = L.load()
     rows = lib.ucfvit_gemm_colsum_rows(ctypes.byref(d))
     ws = lib.ucfvit_gemm_workspace(ctypes.byref(d))
@@ -509,6 +560,8 @@ def _witness(c, o):
     got = _branch(c, dyn=bool(ops._dynamic_sched))
     if _stagger_env() < 0:
         assert got == c.branch, f"{c.id}: this case no longer covers branch {c.branch}: the dispatch now takes {got}"
+    said = _lib_route(c, d, bool(ops._dynamic_sched))
+    assert said == got, f"{c.id}: ucfvit_gemm_route says {said}, the restated dispatch {got}"
     return got
 
 
@@ -821,6 +874,7 @@ def test_gemm3_static_and_dynamic_schedule_bit_identical(c):
     """the ping-pong kernel hands out the same tiles in another order: C, aux_out and the column sums are the same bits"""
     ops = _ops()
     assert _branch(c, dyn=True) == c.branch
+    assert _lib_route(c, _desc(c), True) == c.branch and _lib_route(c, _desc(c), False) == _branch(c, dyn=False)
     stat = _run_outputs(c, "randn", 5)
     try:
         assert ops.set_dynamic_tile_schedule(True) is True
@@ -955,7 +1009,12 @@ def test_gemm_grouped_not_groupable_falls_back(odd):
             dy, x, out, acc, buf, old = sep[1]
             sep[1] = (dy[:-8], x[:-8], out, acc, buf, old)
         for (dy, x, out, acc, _, _), it in zip(sep, items):
-            # the fallback hands no split-K workspace over: the same launch as ops.gemm without one
+            # the fallback hands no split-K workspace over: the same launch as ops.gemm without one, on the branch the library names
+            c = Case("", dy.shape[1], x.shape[1], dy.shape[0], la=KS, lb=KS, out32=True, acc=acc, ws=False)
+            o = Operands()
+            o.A, o.B, o.C, o.bias, o.res, o.aux = dy, x, out, None, None, None
+            assert _lib_route(c, _desc(c, o), False) == _branch(c, dyn=False)
+            assert _branch(c, dyn=False) == ("v1-mfma" if odd == "narrow" and x.shape[1] == 64 else "g2-128")
             ops.gemm(dy, x, dy.shape[1], x.shape[1], dy.shape[0], KS, KS, out=out, accumulate=acc, split_k_workspace=False)
             assert torch.equal(out, it[2])
         for it in items:
@@ -1016,7 +1075,7 @@ def test_gemm_stagger_family(c):
     kernel with E epilogue steps, at the default only those the table names stagger-*"""
     c = replace(c, fams=("randn", "offset"))
     if _stagger_env() > 0:
-        able = (c.act == NONE or (c.act == GELU_SD and not c.res) or (c.act == MUL_AUX and not c.res and not c.bias)) and not c.cs
+        able = _forced_stagger_takes(c)
         c = replace(c, branch=_branch(c))
         assert not able or c.branch.startswith("stagger-"), f"{c.id}: the forced staggered run takes {c.branch}"
     if _t1_ok(c):
@@ -1167,6 +1226,7 @@ def test_gemm_bounds_vs_float64_emulation():
     if _stagger_env() < 0:
         for c in CASES:
             assert _branch(c) == c.branch, f"{c.id}: the restated dispatch takes {_branch(c)}"
+            assert _lib_route(c, _desc(c), c.dyn) == c.branch, f"{c.id}: ucfvit_gemm_route says {_lib_route(c, _desc(c), c.dyn)}"
     names = {c.branch for c in CASES}
     for b in ("v1-mfma", "v1-scalar", "g2-128", "g2-128-splitk", "g2-256", "g3-PLAIN", "g3-PLAIN+CS", "g3-RESIDUAL", "g3-GELU", "g3-GELU_GRAD",
               "g3-GELU_SAVE_DERIV", "g3-MUL_AUX", "g3-MUL_AUX+CS", "g3-GENERIC", "stagger-PLAIN", "stagger-RESIDUAL",
@@ -1174,8 +1234,60 @@ def test_gemm_bounds_vs_float64_emulation():
         assert b in names, f"no case for branch {b}"
 
 
+# ============================================================================================== the route query, without a GPU
+def _route_table():
+    """every entry of CASES (the 4 GiB view and the withheld workspace among them) with either tile schedule and with the split-K workspace
+    handed over or withheld: the library's route on a descriptor of fake addresses is the restated one — under the UCFVIT_GEMM_STAGGER of
+    this process; returns the names the static schedule gives"""
+    names = []
+    for c in CASES:
+        for dyn in (False, True):
+            for cc in (c, replace(c, ws=not c.ws)):
+                said, want = _lib_route(cc, _desc(cc), dyn), _branch(cc, dyn=dyn)
+                assert said == want, f"{cc.id} dyn={dyn}: ucfvit_gemm_route says {said}, the restated dispatch {want}"
+        names.append(_lib_route(c, _desc(c), False))
+    return names
+
+
+def test_gemm_route_query_every_case():
+    names = _route_table()
+    if _stagger_env() < 0:
+        assert names == [c.branch if not c.dyn else _branch(c, dyn=False) for c in CASES]
+        c = next(c for c in CASES if c.dyn)
+        assert c.branch == "g3-PLAIN+CS" and _lib_route(c, _desc(c), False) == "g3-PLAIN+CS" and _lib_route(replace(c, cs=""), _desc(c), False) == "stagger-PLAIN"
+    # the text is cut to the room given, the length returned is the whole name's
+    import ctypes
+    from UCF_VIT._hip import lib as L
+    c = next(c for c in CASES if c.branch == "g2-256")
+    buf = ctypes.create_string_buffer(b"x" * 16, 16)
+    assert L.load().ucfvit_gemm_route(ctypes.byref(_desc(c)), buf, 4) == len("g2-256") and buf.raw[:5] == b"g2-\0x"
+
+
+@pytest.mark.parametrize("steps", ["0", "1", "2", "4", "8"])
+def test_gemm_route_query_forced_stagger(steps):
+    """UCFVIT_GEMM_STAGGER is read once per process: the table again in a child under every setting the hook documents"""
+    r = _child([os.path.abspath(__file__), "routes"], {"UCFVIT_GEMM_STAGGER": steps}, 300)
+    n_st = int(r.stdout.split("stagger:")[1].split()[0])
+    n_forced = sum(1 for c in STAGGER_CASES if _forced_stagger_takes(c))
+    assert n_forced > 0
+    assert (n_st == 0) if steps == "0" else (n_st >= n_forced), r.stdout
+
+
+def _routes_payload():
+    names = _route_table()
+    ov = _stagger_env()
+    for c, name in zip(CASES, names):
+        if ov == 0:
+            assert not name.startswith("stagger-"), f"{c.id}: UCFVIT_GEMM_STAGGER=0, routed to {name}"
+        elif ov > 0 and _stagger_able(c) and _forced_stagger_takes(c):
+            assert name.startswith("stagger-"), f"{c.id}: forced to {ov} steps, routed to {name}"
+    print("stagger:", sum(n.startswith("stagger-") for n in names), "of", len(names))
+
+
 if __name__ == "__main__":
     if len(sys.argv) == 3 and sys.argv[1] == "cus":
         _cus_payload(sys.argv[2])
+    elif len(sys.argv) == 2 and sys.argv[1] == "routes":
+        _routes_payload()
     else:
-        sys.exit("usage: test_gemm_ops.py cus OUT.pt")
+        sys.exit("usage: test_gemm_ops.py cus OUT.pt | routes")

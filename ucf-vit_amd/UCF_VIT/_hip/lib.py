@@ -14,7 +14,7 @@ GEMM_SCHED_BYTES = 1024
 # loss-scaler state block (UCFVIT_GS_* of include/ucfvit_hip.h)
 GS_SCALE, GS_INV_SCALE, GS_FOUND_INF, GS_GROWTH_TRACKER, GS_APPLIED_STEPS, GS_SKIPPED_STEPS = 0, 1, 2, 3, 4, 5
 GS_GROWTH_FACTOR, GS_BACKOFF_FACTOR, GS_GROWTH_INTERVAL, GS_MIN_SCALE, GS_STATE_FLOATS = 6, 7, 8, 9, 16
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))  # .../ucf-vit_amd
 # UCFVIT_HIP_LIB: an alternative build of the same library (A/B measurements of kernel variants); never a non-HIP fallback
@@ -47,6 +47,7 @@ SIGNATURES = {
     "ucfvit_gemm_workspace": (c_int64, [POINTER(GemmDesc)]),
     "ucfvit_gemm": (c_int, [POINTER(GemmDesc), _P]),
     "ucfvit_gemm_colsum_rows": (c_int64, [POINTER(GemmDesc)]),
+    "ucfvit_gemm_route": (c_int, [POINTER(GemmDesc), c_char_p, _I64]),
     "ucfvit_reduce_rows": (c_int, [_P, _P, _I64, _I64, _I, _P]),
     "ucfvit_gemm_grouped": (c_int, [POINTER(GemmDesc), _I64, _P]),
     "ucfvit_colsum_workspace": (c_int64, [_I64, _I64]),

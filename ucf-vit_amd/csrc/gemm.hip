@@ -16,7 +16,8 @@
 //   16-byte aligned base pointers, leading dimensions and the contiguous extent of each operand multiples of 16 bytes.
 #include <stdlib.h>
 
-#include "common.h"
+#include "gemm_route.h"
+#include "gemm_tile.h"
 
 namespace {
 
@@ -44,14 +45,9 @@ template <> struct MmaT<float> {
     }
 };
 
-// ---- LDS image addressing -------------------------------------------------------------------------
-// KC image: byte offset of 16-B slot `slot` (0..7) of row `row` (0..127)
-__device__ __forceinline__ int kc_off(int row, int slot) { return row * 128 + ((slot ^ (row & 7)) << 4); }
-
-// KS image, bf16: k-row = 128 elems = 256 B; 32-B groups swizzled so the 8 k-rows a half-wave's transposed read
-// touches land on 8 distinct 32-B bank groups.
-__device__ __forceinline__ int ks_swz_bf16(int krow) { return ((krow & 3) | (((krow >> 3) & 1) << 2)) << 5; }
-__device__ __forceinline__ int ks_off_bf16(int krow, int colbyte) { return krow * 256 + (colbyte ^ ks_swz_bf16(krow)); }
+// ---- LDS image addressing (KC image and the bf16 KS swizzle: gemm_tile.h) ---------------------------
+// KS image, bf16: k-row = 128 elems = 256 B
+__device__ __forceinline__ int ks_off_bf16(int krow, int colbyte) { return krow * 256 + (colbyte ^ ks_swz(krow)); }
 // KS image, fp32: k-row = 128 elems = 512 B
 __device__ __forceinline__ int ks_off_f32(int krow, int colbyte) { return krow * 512 + (colbyte ^ (((krow >> 2) & 1) << 6)); }
 
@@ -110,9 +106,7 @@ __device__ __forceinline__ typename MmaT<T>::frag_t load_frag(const char* lds, i
     typedef typename MmaT<T>::frag_t frag_t;
     const int g = lane >> 4, i = lane & 15;
     if constexpr (LAYOUT == UCFVIT_LAYOUT_KC) {
-        // lane holds 16 B = k-elements [KCHUNK*c + EPV*g, +EPV) of row rbase+i (both dtypes: chunk = 64 B = 4 slots)
-        const int row = rbase + i;
-        return *reinterpret_cast<const frag_t*>(lds + kc_off(row, 4 * c + g));
+        return kc_frag<frag_t>(lds, rbase, c, lane);
     } else if constexpr (sizeof(T) == 2) {
         // two hardware-transposed reads: k-rows kb+{0..3} and kb+4+{0..3}, columns rbase..rbase+15;
         // lane 4q+p of each 16-lane group supplies the address of k-row q, columns 4p..4p+3.
@@ -318,25 +312,14 @@ int launch_mfma(const ucfvit_gemm_desc* d, const EpiArgs& ep, hipStream_t s) {
 }
 
 template <typename T, typename OutT>
-int dispatch_layout(const ucfvit_gemm_desc* d, const EpiArgs& ep, hipStream_t s) {
+int launch_v1(const ucfvit_gemm_desc* d, bool mfma, hipStream_t s) {
+    const EpiArgs ep = {d->bias, d->residual, d->aux_in, d->aux_out, d->ldc, d->ldr, d->ldaux, d->act, d->accumulate, d->alpha};
     const int la = d->a_layout, lb = d->b_layout;
-    constexpr int64_t EPV = 16 / sizeof(T);
-    constexpr int64_t OPV = 4;  // output vector = 4 elements
-    const int64_t a_contig = (la == UCFVIT_LAYOUT_KC) ? d->K : d->M;
-    const int64_t b_contig = (lb == UCFVIT_LAYOUT_KC) ? d->K : d->N;
-    bool ok = ucf_is_aligned16(d->A) && ucf_is_aligned16(d->B) && (d->lda % EPV == 0) && (d->ldb % EPV == 0) &&
-              (a_contig % EPV == 0) && (b_contig % EPV == 0) && (d->N % OPV == 0) && (d->ldc % OPV == 0) &&
-              (((uintptr_t)d->C) % (OPV * sizeof(OutT)) == 0) && d->M < (1ll << 31) && d->N < (1ll << 31) && d->K < (1ll << 31);
-    const size_t t4 = 4 * sizeof(T);
-    if (d->bias) ok = ok && (((uintptr_t)d->bias) % t4 == 0);
-    if (d->residual) ok = ok && (((uintptr_t)d->residual) % t4 == 0) && (d->ldr % 4 == 0);
-    if (d->aux_in) ok = ok && (((uintptr_t)d->aux_in) % t4 == 0) && (d->ldaux % 4 == 0);
-    if (d->aux_out) ok = ok && (((uintptr_t)d->aux_out) % t4 == 0) && (d->ldaux % 4 == 0);
-    if (ok && d->M * d->N >= 256) {
+    if (mfma) {
         if (la == UCFVIT_LAYOUT_KC && lb == UCFVIT_LAYOUT_KC) return launch_mfma<T, OutT, 0, 0>(d, ep, s);
         if (la == UCFVIT_LAYOUT_KC && lb == UCFVIT_LAYOUT_KS) return launch_mfma<T, OutT, 0, 1>(d, ep, s);
         if (la == UCFVIT_LAYOUT_KS && lb == UCFVIT_LAYOUT_KS) return launch_mfma<T, OutT, 1, 1>(d, ep, s);
-        if (la == UCFVIT_LAYOUT_KS && lb == UCFVIT_LAYOUT_KC) return launch_mfma<T, OutT, 1, 0>(d, ep, s);
+        return launch_mfma<T, OutT, 1, 0>(d, ep, s);
     }
     const int64_t total = d->M * d->N;
     const int64_t blocks = (total + 255) / 256;
@@ -348,10 +331,32 @@ int dispatch_layout(const ucfvit_gemm_desc* d, const EpiArgs& ep, hipStream_t s)
     return UCFVIT_OK;
 }
 
+// UCFVIT_GEMM_STAGGER — a TEST / measurement hook: 0 keeps every launch on gemm3_kernel (tests/test_hip_ops.py compares the dynamic tile
+// schedule with the static order of the SAME kernel; tools/block_gemm_bench.py A/B), 1 / 2 / 4 / 8 force the number of epilogue steps
+// (tests/test_gemm_stagger.py runs every variant).  Read once (thread-safe static).
+int stagger_override() {
+    static const int v = [] {
+        const char* e = getenv("UCFVIT_GEMM_STAGGER");
+        return e ? atoi(e) : -1;
+    }();
+    return v;
+}
+
 }  // namespace
 
-int ucfvit_gemm_v2_try(const ucfvit_gemm_desc* d, hipStream_t s);  // gemm2.hip
-
+int ucfvit_gemm_launch_v1(const ucfvit_gemm_desc* d, const GemmRoute& r, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    const bool mfma = r.kernel == GK_V1_MFMA;
+    if (d->dtype == UCFVIT_F32) {
+        UCF_CHECK_ARG(d->out_dtype == UCFVIT_F32, "ucfvit_gemm: f32 inputs require f32 output");
+        return launch_v1<float, float>(d, mfma, s);
+    } else if (d->dtype == UCFVIT_BF16) {
+        if (d->out_dtype == UCFVIT_BF16) return launch_v1<bf16, bf16>(d, mfma, s);
+        if (d->out_dtype == UCFVIT_F32) return launch_v1<bf16, float>(d, mfma, s);
+    }
+    ucfvit_set_error("ucfvit_gemm: unsupported dtype combination (%d -> %d)", d->dtype, d->out_dtype);
+    return UCFVIT_ERR_UNSUPPORTED;
+}
 
 extern "C" int ucfvit_gemm(const ucfvit_gemm_desc* d, void* stream) {
     UCF_CHECK_ARG(d != nullptr, "ucfvit_gemm: null descriptor");
@@ -366,35 +371,25 @@ extern "C" int ucfvit_gemm(const ucfvit_gemm_desc* d, void* stream) {
     UCF_CHECK_ARG(d->lda >= ((d->a_layout == 0) ? d->K : d->M), "ucfvit_gemm: lda too small");
     UCF_CHECK_ARG(d->ldb >= ((d->b_layout == 0) ? d->K : d->N), "ucfvit_gemm: ldb too small");
     UCF_CHECK_ARG(d->ldc >= d->N, "ucfvit_gemm: ldc too small");
-    if (d->M == 0 || d->N == 0) return UCFVIT_OK;
-    hipStream_t s = (hipStream_t)stream;
-    if (d->dtype == UCFVIT_BF16) {
-        const int rc = ucfvit_gemm_v2_try(d, s);   // large-tile DMA-pipelined kernel when the shape qualifies
-        if (rc == 1) return UCFVIT_OK;
-        if (rc < 0) return rc;
-    }
-    if (d->c_colsum_partial) {
+    const GemmRoute r = gemm_route(d, stagger_override());
+    if (d->c_colsum_partial && (r.colsum_rows == 0 || !ucf_is_aligned16(d->c_colsum_partial))) {
         ucfvit_set_error("ucfvit_gemm: c_colsum_partial is not available for this problem (ask ucfvit_gemm_colsum_rows first)");
         return UCFVIT_ERR_UNSUPPORTED;
     }
-    EpiArgs ep;
-    ep.bias = d->bias;
-    ep.residual = d->residual;
-    ep.aux_in = d->aux_in;
-    ep.aux_out = d->aux_out;
-    ep.ldc = d->ldc;
-    ep.ldr = d->ldr;
-    ep.ldaux = d->ldaux;
-    ep.act = d->act;
-    ep.accumulate = d->accumulate;
-    ep.alpha = d->alpha;
-    if (d->dtype == UCFVIT_F32) {
-        UCF_CHECK_ARG(d->out_dtype == UCFVIT_F32, "ucfvit_gemm: f32 inputs require f32 output");
-        return dispatch_layout<float, float>(d, ep, s);
-    } else if (d->dtype == UCFVIT_BF16) {
-        if (d->out_dtype == UCFVIT_BF16) return dispatch_layout<bf16, bf16>(d, ep, s);
-        if (d->out_dtype == UCFVIT_F32) return dispatch_layout<bf16, float>(d, ep, s);
+    switch (r.kernel) {
+        case GK_V1_SCALAR:
+        case GK_V1_MFMA: return ucfvit_gemm_launch_v1(d, r, stream);
+        case GK_STAGGER: return ucfvit_gemm_launch_stagger(d, r, stream);
+        default: return ucfvit_gemm_launch_dma(d, r, stream);
     }
-    ucfvit_set_error("ucfvit_gemm: unsupported dtype combination (%d -> %d)", d->dtype, d->out_dtype);
-    return UCFVIT_ERR_UNSUPPORTED;
+}
+
+// The three route queries: host only, no HIP call; all of them answer from the route ucfvit_gemm itself would take.
+extern "C" int64_t ucfvit_gemm_workspace(const ucfvit_gemm_desc* d) { return d ? gemm_route(d, stagger_override()).workspace_bytes : 0; }
+
+extern "C" int64_t ucfvit_gemm_colsum_rows(const ucfvit_gemm_desc* d) { return d ? gemm_route(d, stagger_override()).colsum_rows : 0; }
+
+extern "C" int ucfvit_gemm_route(const ucfvit_gemm_desc* d, char* out, int64_t cap) {
+    UCF_CHECK_ARG(d && out && cap > 0, "ucfvit_gemm_route: null descriptor or no room for the text");
+    return gemm_route_name(gemm_route(d, stagger_override()), out, cap);
 }

@@ -14,9 +14,8 @@
 //               order (deterministic) and applies accumulate.  Used when the output has too few tiles to fill 256 CUs.
 #include <stdlib.h>
 
-#include "common.h"
-
-int ucfvit_gemm_stagger_try(const ucfvit_gemm_desc* d, hipStream_t s);   // gemm_stagger.hip
+#include "gemm_route.h"
+#include "gemm_tile.h"
 
 namespace {
 
@@ -31,14 +30,8 @@ __device__ __forceinline__ void store_out16(bf16* p, const Vec16<bf16>& o) { *re
 
 constexpr int BK2 = 64;
 
-__device__ __forceinline__ int kc_off2(int row, int slot) { return row * 128 + ((slot ^ (row & 7)) << 4); }
-__device__ __forceinline__ int ks_swz2(int krow) { return ((krow & 3) | (((krow >> 3) & 1) << 2)) << 5; }
-
 template <int BR>  // BR = tile extent along the operand's row/col index (128 or 256)
-__device__ __forceinline__ int ks_off2(int krow, int colbyte) { return krow * (BR * 2) + (colbyte ^ ks_swz2(krow)); }
-
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
+__device__ __forceinline__ int ks_off2(int krow, int colbyte) { return krow * (BR * 2) + (colbyte ^ ks_swz(krow)); }
 
 // Source of the zero fill for the ragged last K-tile: lanes whose contraction index is >= K read this page instead of the
 // operand (a DMA lane cannot be predicated off without leaving stale LDS bytes).
@@ -66,7 +59,7 @@ __device__ __forceinline__ void issue_tile(const bf16* __restrict__ base, int64_
             constexpr int KPP = 1024 / RB;      // k-rows per piece
             const int krow = idx * KPP + (lane * 16) / RB;
             const int pbyte = (lane * 16) % RB;
-            const int col = (pbyte ^ ks_swz2(krow)) >> 1;
+            const int col = (pbyte ^ ks_swz(krow)) >> 1;
             int gc = r0 + col;
             gc = gc <= R - 8 ? gc : R - 8;
             src = base + (int64_t)(k0 + krow) * ld + gc;
@@ -80,7 +73,7 @@ template <int LAYOUT, int BR>
 __device__ __forceinline__ bf16x8 load_frag2(const char* lds, int rbase, int c, int lane) {
     const int g = lane >> 4, i = lane & 15;
     if constexpr (LAYOUT == UCFVIT_LAYOUT_KC) {
-        return *reinterpret_cast<const bf16x8*>(lds + kc_off2(rbase + i, 4 * c + g));
+        return kc_frag<bf16x8>(lds, rbase, c, lane);
     } else {
         const int kb = 32 * c + 8 * g, q = i >> 2, p = i & 3;
         const int colbyte = (rbase + 4 * p) * 2;
@@ -176,18 +169,6 @@ __device__ __forceinline__ void sched_leave(unsigned* sched, int tid) {
             sched[SCHED_EXIT_WORD] = 0u;
         }
     }
-}
-
-// logical tile index -> (m0, n0): bands of 8 N-tiles, walking down M inside a band (neighbouring tiles share operand panels)
-__device__ __forceinline__ void tile_origin(int t, int tiles_m, int tiles_n, int BM, int BN, int& m0, int& n0) {
-    // 12 N-tiles (the qkv projection: N = 3072) as three bands of 4 rather than 8 + 4: every XCD block is 8 x 4 tiles
-    const int BAND = (tiles_n > 8 && tiles_n % 8 != 0 && tiles_n % 4 == 0) ? 4 : 8;
-    const int band_tiles = BAND * tiles_m;
-    const int band = t / band_tiles;
-    const int band_w = min(BAND, tiles_n - band * BAND);
-    const int in_band = t - band * band_tiles;
-    m0 = (in_band / band_w) * BM;
-    n0 = (band * BAND + in_band % band_w) * BN;
 }
 
 // XCD-blocked work schedule.  Hardware hands workgroup w to XCD w % 8 and every XCD has a private L2, so operand panels are
@@ -431,41 +412,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm2_kernel(const bf16* __restri
 // issuing waves, then the barrier) at the end of interval 4t+3, i.e. 3-4 intervals after it was issued and right before its
 // first reader (G0 in interval 4t+4).  A pipeline buffer is overwritten only >= 1 interval after its last ds_read.
 // =====================================================================================================================
-// Per-lane 32-bit byte offsets (row clamp + source-side swizzle folded in) of this wave's 4 DMA pieces of an operand K-tile;
-// the K position is a wave-uniform byte offset added to the (SGPR) base pointer at issue time.
-template <int LAYOUT, int BR>
-__device__ __forceinline__ void half_offsets(unsigned (&off)[4], int64_t ld, int r0, int R, int grp, int w4, int lane) {
-    constexpr int NP = BR / 8, PER = NP / 8;
-    static_assert(PER == 4, "256-wide operand tiles only");
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-        const int idx = grp * (NP / 2) + w4 * PER + i;
-        if (LAYOUT == UCFVIT_LAYOUT_KC) {
-            const int row = idx * 8 + (lane >> 3);
-            const int gslot = (lane & 7) ^ (row & 7);
-            int gr = r0 + row;
-            gr = gr < R ? gr : R - 1;
-            off[i] = (unsigned)(((int64_t)gr * ld + gslot * 8) * 2);
-        } else {
-            constexpr int RB = BR * 2, KPP = 1024 / RB;
-            const int krow = idx * KPP + (lane * 16) / RB;
-            const int pbyte = (lane * 16) % RB;
-            const int col = (pbyte ^ ks_swz2(krow)) >> 1;
-            int gc = r0 + col;
-            gc = gc <= R - 8 ? gc : R - 8;
-            off[i] = (unsigned)(((int64_t)krow * ld + gc) * 2);
-        }
-    }
-}
-template <int BR>
-__device__ __forceinline__ void issue_half(const char* __restrict__ base_k, const unsigned (&off)[4], char* lds, int grp, int w4) {
-    constexpr int NP = BR / 8, PER = NP / 8;
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-        const int idx = grp * (NP / 2) + w4 * PER + i;
-        __builtin_amdgcn_global_load_lds((gptr_t)(base_k + off[i]), (lptr_t)(lds + idx * 1024), 16, 0, 0);
-    }
-}
+// (half_offsets / issue_half, the per-lane offsets and the issue of this wave's 4 DMA pieces of an operand K-tile: gemm_tile.h)
 // ragged last K-tile: lanes beyond the valid contraction extent `krem` read the zero page
 template <int LAYOUT, int BR>
 __device__ __forceinline__ void issue_half_tail(const char* __restrict__ base_k, const unsigned (&off)[4], char* lds, int grp, int w4, int lane,
@@ -491,14 +438,7 @@ template <int LAYOUT> __device__ __forceinline__ int64_t k_byte_off(int k0, int6
     return LAYOUT == UCFVIT_LAYOUT_KC ? (int64_t)k0 * 2 : (int64_t)k0 * ld * 2;
 }
 
-#define PP_BARRIER()                              \
-    do {                                          \
-        __builtin_amdgcn_sched_barrier(0);        \
-        asm volatile("" ::: "memory");            \
-        __builtin_amdgcn_s_barrier();             \
-        asm volatile("" ::: "memory");            \
-        __builtin_amdgcn_sched_barrier(0);        \
-    } while (0)
+#define PP_BARRIER() TILE_BARRIER((void)0)
 #define PP_WAIT_B() /* all but the 4 youngest (the A pieces just issued) */ \
     do {                                                   \
         __builtin_amdgcn_sched_barrier(0);                 \
@@ -533,8 +473,7 @@ template <int NP> struct GroupsT {
 // cannot see the asm waits that retire the LDS-DMA, drains vmcnt(0) — loads AND the strips' stores, which share the counter — at
 // every use of a loaded value (124 drains per tile).  A specialised epilogue is straight-line: its one C-shaped input is fetched
 // PD strips ahead with counted waits, its stores are never waited for.  (A cache-warming DMA touch of that input during the K loop
-// was worth 5 % before this and nothing after it; removed.)
-enum { EPI_GENERIC = 0, EPI_PLAIN = 1, EPI_RESIDUAL = 2, EPI_GELU = 3, EPI_GELU_GRAD = 4, EPI_GELU_SAVE_DERIV = 5, EPI_MUL_AUX = 6 };
+// was worth 5 % before this and nothing after it; removed.)  EPI_*: gemm_route.h.
 
 typedef GroupsT<GROUP_MAX> Groups3;
 
@@ -1005,57 +944,11 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ slab, OutT* __res
     }
 }
 
-static bool generic_epilogue_only();
-static bool pp_enabled();
-
-struct Plan2 {
-    int big;     // 1: 256x256 tile, 0: 128x128
-    int splits;
-    int k_per_split;
-};
-
-inline bool plan2(const ucfvit_gemm_desc* d, Plan2* p) {
-    if (d->dtype != UCFVIT_BF16) return false;
-    if (d->K < 128) return false;
-    // ragged last K-tile is zero-filled by the DMA issue; 16-byte vectors along K need K % 8 == 0 only for KC operands
-    if ((d->a_layout == UCFVIT_LAYOUT_KC || d->b_layout == UCFVIT_LAYOUT_KC) && d->K % 8 != 0) return false;
-    if (d->M < 128 || d->N < 128) return false;
-    const int64_t t256 = ((d->M + 255) / 256) * ((d->N + 255) / 256);
-    const int64_t t128 = ((d->M + 127) / 128) * ((d->N + 127) / 128);
-    const int64_t ktiles_all = (d->K + BK2 - 1) / BK2;
-    const bool plain_epi = !d->bias && !d->residual && !d->aux_in && !d->aux_out && d->act == UCFVIT_ACT_NONE;
-    p->splits = 1;
-    if (t256 >= 192) {
-        p->big = 1;
-    } else {
-        p->big = 0;
-        if (plain_epi && t128 < 384) {
-            constexpr int target = 384;
-            // split-K so that every XCD owns whole 8 x 8-tile blocks (64 resident workgroups = 2 per CU) of ONE K-slice and
-            // all 8 XCDs are busy in every round: nb64 * s block-slices must be a multiple of 8 (see Sched2)
-            const int64_t tm = (d->M + 127) / 128, tn = (d->N + 127) / 128;
-            const int nb64 = (int)(((tm + 7) / 8) * ((tn + 7) / 8));
-            int g8 = 8;
-            while (nb64 % g8) g8 >>= 1;                     // gcd(nb64, 8)
-            int s = 8 / g8;
-            if (nb64 * s > target / 8) s = 1;                // too many rounds of slab traffic: plain persistent walk
-            const int kmax = (int)(ktiles_all / 8);          // at least 8 K-tiles per slice
-            if (s > kmax) s = kmax;
-            if (s < 1) s = 1;
-            p->splits = s;
-        }
-    }
-    const int64_t ktiles = (d->K + BK2 - 1) / BK2;
-    p->k_per_split = (int)(((ktiles + p->splits - 1) / p->splits) * BK2);
-    p->splits = (int)((d->K + p->k_per_split - 1) / p->k_per_split);
-    return true;
-}
-
 // block shape for the XCD-blocked schedule: `cap` = resident workgroups of one XCD (32 CUs x 1 or 2)
 inline Sched2 make_sched2(int tiles_m, int tiles_n, int splits, int k_per_split, int cap) {
     const int64_t work = (int64_t)tiles_m * tiles_n * splits;
     int T = (int)((work + 7) / 8);                        // tile-slices per XCD if everything fits one round
-    if (T > cap || splits > 1) T = cap;                   // split-K plans are made for full blocks (plan2)
+    if (T > cap || splits > 1) T = cap;                   // split-K plans are made for full blocks (gemm_plan)
     if (T < 1) T = 1;
     int bm = cap == 64 ? 8 : 4;
     if (bm > tiles_m) bm = tiles_m;
@@ -1081,7 +974,7 @@ inline Sched2 make_sched2(int tiles_m, int tiles_n, int splits, int k_per_split,
 }
 
 template <int LA, int LB, int BM, int BN, int WM, int WN, typename OutT>
-int launch2(const ucfvit_gemm_desc* d, const Plan2& p, Epi2 ep, hipStream_t s) {
+int launch2(const ucfvit_gemm_desc* d, const GemmRoute& p, const Epi2& ep, hipStream_t s) {
     const int tiles_m = (int)((d->M + BM - 1) / BM), tiles_n = (int)((d->N + BN - 1) / BN);
     constexpr size_t smem = 2 * (size_t)(BM + BN) * 128;
     auto kern = gemm2_kernel<LA, LB, BM, BN, WM, WN, OutT>;
@@ -1159,167 +1052,69 @@ inline void fill_problem(Problem3& P, const ucfvit_gemm_desc* d, int tile_start)
     P.accumulate = d->accumulate;
 }
 
+// gemm3_kernel for one problem: the epilogue the route names ((KC, KC) with a bf16 output only; everything else is generic)
 template <int LA, int LB, typename OutT>
-int launch3(const ucfvit_gemm_desc* d, const Plan2& p, Epi2 ep, hipStream_t s) {
+int launch3(const ucfvit_gemm_desc* d, const GemmRoute& r, const Epi2& ep, hipStream_t s) {
     GroupsT<1> gt;
     memset(&gt, 0, sizeof(gt));
     fill_problem(gt.p[0], d, 0);
     gt.n = 1;
     gt.total_tiles = gt.p[0].tiles_m * gt.p[0].tiles_n;
+    const int K = (int)d->K;
     if constexpr (LA == UCFVIT_LAYOUT_KC && LB == UCFVIT_LAYOUT_KC && sizeof(OutT) == 2) {
-        // straight-line epilogues for the shapes of the training step (see EPI_* above); everything else is generic
-        if (!generic_epilogue_only() && p.splits == 1 && !ep.slab && !d->accumulate && d->N >= 8) {
-            const int K_ = (int)d->K;
-            // the epilogue hidden under the partner group's K loop (gemm_stagger.hip) where that kernel applies
-            const int rs = ucfvit_gemm_stagger_try(d, s);
-            if (rs == 1) return UCFVIT_OK;
-            if (rs < 0) return rs;
-            if (ep.act == UCFVIT_ACT_NONE && !ep.residual && !ep.aux_out) {
-                if (ep.cs_partial) return launch3g<LA, LB, OutT, EPI_PLAIN, true, 1>(gt, K_, ep, 1, p.k_per_split, s);
-                return launch3g<LA, LB, OutT, EPI_PLAIN, false, 1>(gt, K_, ep, 1, p.k_per_split, s);
-            }
-            if (ep.act == UCFVIT_ACT_NONE && ep.residual && !ep.aux_out)
-                return launch3g<LA, LB, OutT, EPI_RESIDUAL, false, 1>(gt, K_, ep, 1, p.k_per_split, s);
-            if (ep.act == UCFVIT_ACT_GELU && !ep.residual)
-                return launch3g<LA, LB, OutT, EPI_GELU, false, 1>(gt, K_, ep, 1, p.k_per_split, s);
-            if (ep.act == UCFVIT_ACT_GELU_GRAD && !ep.residual && !ep.aux_out)
-                return launch3g<LA, LB, OutT, EPI_GELU_GRAD, false, 1>(gt, K_, ep, 1, p.k_per_split, s);
-            if (ep.act == UCFVIT_ACT_GELU_SAVE_DERIV && !ep.residual)
-                return launch3g<LA, LB, OutT, EPI_GELU_SAVE_DERIV, false, 1>(gt, K_, ep, 1, p.k_per_split, s);
-            if (ep.act == UCFVIT_ACT_MUL_AUX && !ep.residual && !ep.aux_out) {
-                if (ep.cs_partial) return launch3g<LA, LB, OutT, EPI_MUL_AUX, true, 1>(gt, K_, ep, 1, p.k_per_split, s);
-                return launch3g<LA, LB, OutT, EPI_MUL_AUX, false, 1>(gt, K_, ep, 1, p.k_per_split, s);
-            }
+#define G3(EPI_, CS_) launch3g<LA, LB, OutT, EPI_, CS_, 1>(gt, K, ep, 1, r.k_per_split, s)
+        switch (r.epi) {
+            case EPI_PLAIN: return r.cs ? G3(EPI_PLAIN, true) : G3(EPI_PLAIN, false);
+            case EPI_RESIDUAL: return G3(EPI_RESIDUAL, false);
+            case EPI_GELU: return G3(EPI_GELU, false);
+            case EPI_GELU_GRAD: return G3(EPI_GELU_GRAD, false);
+            case EPI_GELU_SAVE_DERIV: return G3(EPI_GELU_SAVE_DERIV, false);
+            case EPI_MUL_AUX: return r.cs ? G3(EPI_MUL_AUX, true) : G3(EPI_MUL_AUX, false);
         }
+#undef G3
     }
-    return launch3g<LA, LB, OutT, EPI_GENERIC, false, 1>(gt, (int)d->K, ep, p.splits, p.k_per_split, s);
+    return launch3g<LA, LB, OutT, EPI_GENERIC, false, 1>(gt, K, ep, r.splits, r.k_per_split, s);
 }
 
-static bool generic_epilogue_only() { return false; }
-static bool pp_enabled() { return true; }
-
 template <int LA, int LB, typename OutT>
-int dispatch_tile(const ucfvit_gemm_desc* d, const Plan2& p, const Epi2& ep, hipStream_t s) {
-    const int64_t a_bytes = ((d->a_layout == UCFVIT_LAYOUT_KC ? d->M : d->K) * d->lda) * 2;
-    const int64_t b_bytes = ((d->b_layout == UCFVIT_LAYOUT_KC ? d->N : d->K) * d->ldb) * 2;
-    if (p.big && pp_enabled() && a_bytes < (1ll << 32) && b_bytes < (1ll << 32)) return launch3<LA, LB, OutT>(d, p, ep, s);
-    if (p.big) return launch2<LA, LB, 256, 256, 2, 4, OutT>(d, p, ep, s);
-    return launch2<LA, LB, 128, 128, 2, 2, OutT>(d, p, ep, s);
+int launch_tile(const ucfvit_gemm_desc* d, const GemmRoute& r, const Epi2& ep, hipStream_t s) {
+    if (r.kernel == GK_G3) return launch3<LA, LB, OutT>(d, r, ep, s);
+    if (r.kernel == GK_G2_256) return launch2<LA, LB, 256, 256, 2, 4, OutT>(d, r, ep, s);
+    return launch2<LA, LB, 128, 128, 2, 2, OutT>(d, r, ep, s);
 }
 
 template <typename OutT>
-int dispatch_layout2(const ucfvit_gemm_desc* d, const Plan2& p, const Epi2& ep, hipStream_t s) {
+int launch_layout(const ucfvit_gemm_desc* d, const GemmRoute& r, const Epi2& ep, hipStream_t s) {
     const int la = d->a_layout, lb = d->b_layout;
-    if (la == 0 && lb == 0) return dispatch_tile<0, 0, OutT>(d, p, ep, s);
-    if (la == 0 && lb == 1) return dispatch_tile<0, 1, OutT>(d, p, ep, s);
-    if (la == 1 && lb == 1) return dispatch_tile<1, 1, OutT>(d, p, ep, s);
-    return dispatch_tile<1, 0, OutT>(d, p, ep, s);
+    if (la == 0 && lb == 0) return launch_tile<0, 0, OutT>(d, r, ep, s);
+    if (la == 0 && lb == 1) return launch_tile<0, 1, OutT>(d, r, ep, s);
+    if (la == 1 && lb == 1) return launch_tile<1, 1, OutT>(d, r, ep, s);
+    return launch_tile<1, 0, OutT>(d, r, ep, s);
 }
 
 }  // namespace
 
-// shape / alignment requirements of the DMA + vector-epilogue path (shared by ucfvit_gemm_v2_try and the by-product predicates)
-static bool v2_operands_ok(const ucfvit_gemm_desc* d) {
-    const int64_t a_contig = (d->a_layout == UCFVIT_LAYOUT_KC) ? d->K : d->M;
-    const int64_t b_contig = (d->b_layout == UCFVIT_LAYOUT_KC) ? d->K : d->N;
-    bool ok = ucf_is_aligned16(d->A) && ucf_is_aligned16(d->B) && d->lda % 8 == 0 && d->ldb % 8 == 0 && a_contig % 8 == 0 &&
-              b_contig % 8 == 0 && d->N % 8 == 0 && d->ldc % 8 == 0 && ((uintptr_t)d->C) % 16 == 0 && d->M < (1ll << 31) &&
-              d->N < (1ll << 31) && d->K < (1ll << 31);
-    if (d->bias) ok = ok && ((uintptr_t)d->bias) % 8 == 0;
-    if (d->residual) ok = ok && ((uintptr_t)d->residual) % 16 == 0 && d->ldr % 8 == 0;
-    if (d->aux_in) ok = ok && ((uintptr_t)d->aux_in) % 16 == 0 && d->ldaux % 8 == 0;
-    if (d->aux_out) ok = ok && ((uintptr_t)d->aux_out) % 16 == 0 && d->ldaux % 8 == 0;
-    return ok;
+// GK_G2_128 / GK_G2_256 / GK_G3 of a route (bf16 operands that meet the DMA path's rules, bf16 or fp32 output)
+int ucfvit_gemm_launch_dma(const ucfvit_gemm_desc* d, const GemmRoute& r, void* stream) {
+    const Epi2 ep = {(const bf16*)d->bias, (const bf16*)d->residual, (const bf16*)d->aux_in, (bf16*)d->aux_out, d->ldc, d->ldr, d->ldaux,
+                     d->act, d->accumulate, d->alpha,
+                     /* slab */ r.splits > 1 ? (float*)d->workspace : nullptr, /* cs_partial */ r.cs ? d->c_colsum_partial : nullptr,
+                     /* sched */ (unsigned*)d->sched_state};
+    hipStream_t s = (hipStream_t)stream;
+    return d->out_dtype == UCFVIT_BF16 ? launch_layout<bf16>(d, r, ep, s) : launch_layout<float>(d, r, ep, s);
 }
-
-// the output column sums (desc->c_colsum_partial) exist in the specialised MUL_AUX and plain epilogues of the 256x256 ping-pong kernel: the
-// data-gradient GEMM through the activation (C = dh of the MLP) and the plain data gradients (C = dO of the attention projection: the V
-// third of the qkv bias gradient), two 128-row blocks per output tile row
-static int64_t colsum_rows_for(const ucfvit_gemm_desc* d) {
-    Plan2 p;
-    if (!d || !plan2(d, &p) || !v2_operands_ok(d)) return 0;
-    const int64_t a_bytes = d->M * d->lda * 2, b_bytes = d->N * d->ldb * 2;
-    const bool path = p.big && p.splits == 1 && pp_enabled() && !generic_epilogue_only() && a_bytes < (1ll << 32) && b_bytes < (1ll << 32) &&
-                      d->a_layout == UCFVIT_LAYOUT_KC && d->b_layout == UCFVIT_LAYOUT_KC && d->out_dtype == UCFVIT_BF16 && !d->accumulate &&
-                      d->N >= 8 && !d->residual && !d->aux_out &&
-                      (d->act == UCFVIT_ACT_MUL_AUX || (d->act == UCFVIT_ACT_NONE && !d->aux_in));
-    return path ? 2 * ((d->M + 255) / 256) : 0;
-}
-
-extern "C" int64_t ucfvit_gemm_colsum_rows(const ucfvit_gemm_desc* d) { return colsum_rows_for(d); }
-
-// bytes of fp32 workspace ucfvit_gemm wants for this problem (0 if none)
-extern "C" int64_t ucfvit_gemm_workspace(const ucfvit_gemm_desc* d) {
-    Plan2 p;
-    if (!d || !plan2(d, &p) || p.splits <= 1) return 0;
-    return (int64_t)p.splits * d->M * d->N * (int64_t)sizeof(float);
-}
-
-// returns 1 if the v2 kernel handled the problem, 0 if the caller should use the v1 path, <0 on error
-int ucfvit_gemm_v2_try(const ucfvit_gemm_desc* d, hipStream_t s) {
-    Plan2 p;
-    if (!plan2(d, &p)) return 0;
-    if (!v2_operands_ok(d)) return 0;
-    Epi2 ep;
-    ep.bias = (const bf16*)d->bias;
-    ep.residual = (const bf16*)d->residual;
-    ep.aux_in = (const bf16*)d->aux_in;
-    ep.aux_out = (bf16*)d->aux_out;
-    ep.ldc = d->ldc;
-    ep.ldr = d->ldr;
-    ep.ldaux = d->ldaux;
-    ep.act = d->act;
-    ep.accumulate = d->accumulate;
-    ep.alpha = d->alpha;
-    ep.slab = nullptr;
-    ep.cs_partial = nullptr;
-    ep.sched = (unsigned*)d->sched_state;
-    if (d->c_colsum_partial) {
-        if (colsum_rows_for(d) == 0 || !ucf_is_aligned16(d->c_colsum_partial)) {
-            ucfvit_set_error("ucfvit_gemm: c_colsum_partial is not available for this problem (ask ucfvit_gemm_colsum_rows first)");
-            return UCFVIT_ERR_UNSUPPORTED;
-        }
-        ep.cs_partial = d->c_colsum_partial;
-    }
-    if (p.splits > 1) {
-        const int64_t need = (int64_t)p.splits * d->M * d->N * (int64_t)sizeof(float);
-        if (!d->workspace || d->workspace_bytes < need || !ucf_is_aligned16(d->workspace)) {
-            // no (or too small a) workspace: run un-split
-            p.splits = 1;
-            p.k_per_split = (int)d->K;
-        } else {
-            ep.slab = (float*)d->workspace;
-        }
-    }
-    int rc;
-    if (d->out_dtype == UCFVIT_BF16)
-        rc = dispatch_layout2<bf16>(d, p, ep, s);
-    else if (d->out_dtype == UCFVIT_F32)
-        rc = dispatch_layout2<float>(d, p, ep, s);
-    else
-        return 0;
-    return rc == UCFVIT_OK ? 1 : rc;
-}
-
 
 // Grouped launch: n <= 32 epilogue-free GEMMs with identical K, layouts and dtypes (the weight gradients of 1..8 Blocks) run
 // as ONE persistent ping-pong launch over the union of their 256x256 tiles — no split-K, no partial-sum slabs.
 extern "C" int ucfvit_gemm_grouped(const ucfvit_gemm_desc* descs, int64_t n, void* stream) {
     UCF_CHECK_ARG(descs && n >= 1 && n <= GROUP_MAX, "ucfvit_gemm_grouped: need 1..%d descriptors", GROUP_MAX);
     const ucfvit_gemm_desc& d0 = descs[0];
-    bool fast = d0.dtype == UCFVIT_BF16 && pp_enabled() && d0.K >= 128;
+    bool fast = true;
     for (int64_t i = 0; i < n && fast; ++i) {
         const ucfvit_gemm_desc& d = descs[i];
-        const int64_t a_contig = (d.a_layout == UCFVIT_LAYOUT_KC) ? d.K : d.M;
-        const int64_t b_contig = (d.b_layout == UCFVIT_LAYOUT_KC) ? d.K : d.N;
-        const int64_t a_bytes = ((d.a_layout == UCFVIT_LAYOUT_KC ? d.M : d.K) * d.lda) * 2;
-        const int64_t b_bytes = ((d.b_layout == UCFVIT_LAYOUT_KC ? d.N : d.K) * d.ldb) * 2;
         fast = d.K == d0.K && d.dtype == d0.dtype && d.out_dtype == d0.out_dtype && d.a_layout == d0.a_layout && d.b_layout == d0.b_layout &&
                !d.bias && !d.residual && !d.aux_in && !d.aux_out && d.act == UCFVIT_ACT_NONE && d.alpha == 1.0f && d.A && d.B && d.C &&
-               d.M >= 128 && d.N >= 128 && ucf_is_aligned16(d.A) && ucf_is_aligned16(d.B) && ucf_is_aligned16(d.C) && d.lda % 8 == 0 &&
-               d.ldb % 8 == 0 && d.ldc % 8 == 0 && a_contig % 8 == 0 && b_contig % 8 == 0 && d.N % 8 == 0 && a_bytes < (1ll << 32) &&
-               b_bytes < (1ll << 32) &&
-               !((d.a_layout == UCFVIT_LAYOUT_KC || d.b_layout == UCFVIT_LAYOUT_KC) && d.K % 8 != 0);
+               gemm_dma_shape_ok(&d) && gemm_dma_operands_ok(&d) && gemm_ab_fit_u32(&d);
     }
     hipStream_t s = (hipStream_t)stream;
     if (!fast) {   // not groupable: run them one by one through the ordinary dispatcher

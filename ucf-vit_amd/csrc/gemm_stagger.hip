@@ -25,7 +25,8 @@
 // that nobody needs at the very end of the tile list are issued anyway), so every wait is an exact count.
 #include <stdlib.h>
 
-#include "common.h"
+#include "gemm_route.h"
+#include "gemm_tile.h"
 
 #ifndef S5_ST_MOD
 #define S5_ST_MOD " nt"      // C / aux are written once: non-temporal, so the dirty lines leave L2 gradually (see gemm2.hip:store_out16)
@@ -33,36 +34,9 @@
 
 namespace {
 
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 typedef __attribute__((ext_vector_type(4))) int i32x4;
 
-__device__ __forceinline__ int s5_kc_off(int row, int slot) { return row * 128 + ((slot ^ (row & 7)) << 4); }
-
-// per-lane byte offsets of this wave's 4 DMA pieces (1 KiB each: 8 rows x 128 B) of its group's half of a 256-row KC operand K-tile
-__device__ __forceinline__ void s5_offsets(unsigned (&off)[4], int64_t ld, int r0, int R, int grp, int w4, int lane) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int idx = grp * 16 + w4 * 4 + i;
-        const int row = idx * 8 + (lane >> 3);
-        const int gslot = (lane & 7) ^ (row & 7);
-        int gr = r0 + row;
-        gr = gr < R ? gr : R - 1;
-        off[i] = (unsigned)(((int64_t)gr * ld + gslot * 8) * 2);
-    }
-}
-__device__ __forceinline__ void s5_issue(const char* __restrict__ base_k, const unsigned (&off)[4], char* lds, int grp, int w4) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int idx = grp * 16 + w4 * 4 + i;
-        __builtin_amdgcn_global_load_lds((gptr_t)(base_k + off[i]), (lptr_t)(lds + idx * 1024), 16, 0, 0);
-    }
-}
-__device__ __forceinline__ bf16x8 s5_frag(const char* lds, int rbase, int c, int lane) {
-    const int g = lane >> 4, i = lane & 15;
-    return *reinterpret_cast<const bf16x8*>(lds + s5_kc_off(rbase + i, 4 * c + g));
-}
-
+// (the operand images, the tile order and the DMA issue are gemm3_kernel's: gemm_tile.h; both operands are KC here)
 __device__ __forceinline__ i32x4 s5_rsrc(const void* p, unsigned bytes) {
     const uint64_t a = (uint64_t)p;
     i32x4 r;
@@ -98,15 +72,7 @@ __device__ int g_s5_stamp_n[2];
 #else
 #define S5_STAMP_HERE() do { } while (0)
 #endif
-#define s5_barrier()                          \
-    do {                                      \
-        __builtin_amdgcn_sched_barrier(0);    \
-        asm volatile("" ::: "memory");        \
-        __builtin_amdgcn_s_barrier();         \
-        asm volatile("" ::: "memory");        \
-        S5_STAMP_HERE();                      \
-        __builtin_amdgcn_sched_barrier(0);    \
-    } while (0)
+#define s5_barrier() TILE_BARRIER(S5_STAMP_HERE())
 
 template <int I> struct IC {
     static constexpr int value = I;
@@ -118,7 +84,7 @@ template <int B, int E_, typename F> __device__ __forceinline__ void s5_for(F&& 
     }
 }
 
-enum { S5_PLAIN = 1, S5_RESIDUAL = 2, S5_GELU_SAVE_DERIV = 5, S5_MUL_AUX = 6 };
+// EPI below: EPI_PLAIN, EPI_RESIDUAL, EPI_GELU_SAVE_DERIV or EPI_MUL_AUX (gemm_route.h)
 
 // The vector-memory operations one wave issues during an epilogue phase of E K-steps (4 E barrier intervals), in order, and the number
 // issued so far at every point that waits for one of them.  Interval u = 4 j + r:
@@ -131,15 +97,15 @@ enum { S5_PLAIN = 1, S5_RESIDUAL = 2, S5_GELU_SAVE_DERIV = 5, S5_MUL_AUX = 6 };
 // behind that step's closing vmcnt(0): the phase opens without a memory round trip.
 template <int EPI, int E> struct EpiLog {
     static constexpr int U = 4 * E;
-    static constexpr bool HAS_IN = EPI == S5_RESIDUAL || EPI == S5_MUL_AUX;
-    static constexpr int NS = EPI == S5_GELU_SAVE_DERIV ? 2 : 1;
+    static constexpr bool HAS_IN = EPI == EPI_RESIDUAL || EPI == EPI_MUL_AUX;
+    static constexpr int NS = EPI == EPI_GELU_SAVE_DERIV ? 2 : 1;
     static constexpr int PD = 2;
     // Who feeds the draining group's half of the B stream?  OWN_B: the draining group itself, 4 pieces in the first interval of every one
     // of its steps.  Its wait for the pieces of step j sits behind its stores of step j - 1 (vmcnt retires in order): harmless when those
     // are old by then — one step (E == 1: no older stores at all) or long arithmetic slices (the GELU epilogue: a slice per interval, four
     // intervals before the wait) — and a stall for the short slices of the other epilogues at E > 1, where the partner group, which is in
     // its K loop, issues both halves instead.
-    static constexpr bool OWN_B = E == 1 || EPI == S5_GELU_SAVE_DERIV;
+    static constexpr bool OWN_B = E == 1 || EPI == EPI_GELU_SAVE_DERIV;
     int idxL[16] = {}, idxDmaB[E] = {}, idxDmaAll[E] = {};
     int nWL[16] = {}, nWB[E] = {}, nWD[E] = {};
     static constexpr int slot_of(int q) { return q * U / 16; }
@@ -177,9 +143,9 @@ struct StaggerArgs {
     const char* A;
     const char* B;
     bf16* C;
-    const bf16* bias;      // [N], or the zero page (bias_bytes says how much of it may be read)
-    const bf16* in;        // residual (S5_RESIDUAL) / aux_in (S5_MUL_AUX), [M][ldin]
-    bf16* aux_out;         // gelu' (S5_GELU_SAVE_DERIV), [M][ldaux]
+    const bf16* bias;      // [N], or any device address with bias_bytes = 0 (bias_bytes says how much of it may be read)
+    const bf16* in;        // residual (EPI_RESIDUAL) / aux_in (EPI_MUL_AUX), [M][ldin]
+    bf16* aux_out;         // gelu' (EPI_GELU_SAVE_DERIV), [M][ldaux]
     float* cs_partial;     // [2 tiles_m][N] column sums (CS)
     int M, N, K;
     int64_t lda, ldb;
@@ -188,19 +154,6 @@ struct StaggerArgs {
     float alpha;
     int tiles_m, tiles_n, total_tiles;
 };
-
-__device__ __attribute__((aligned(16))) unsigned char g_s5_zero_page[1024];
-
-// logical tile index -> (m0, n0): bands of 8 (or 4) N-tiles, walking down M inside a band — the order of gemm3_kernel
-__device__ __forceinline__ void s5_tile_origin(int t, int tiles_m, int tiles_n, int& m0, int& n0) {
-    const int BAND = (tiles_n > 8 && tiles_n % 8 != 0 && tiles_n % 4 == 0) ? 4 : 8;
-    const int band_tiles = BAND * tiles_m;
-    const int band = t / band_tiles;
-    const int band_w = min(BAND, tiles_n - band * BAND);
-    const int in_band = t - band * band_tiles;
-    m0 = (in_band / band_w) * 256;
-    n0 = (band * BAND + in_band % band_w) * 256;
-}
 
 // first half of an epilogue pass (see gemm5_kernel: `pass`): stage strip Q / 2 (even Q), read rows (Q & 1) * 8 + prow back transposed.
 // (A free function, not a lambda: hipcc does not capture the operands of an asm statement inside a generic lambda that is instantiated
@@ -236,7 +189,7 @@ __global__ __launch_bounds__(512) void gemm5_kernel(StaggerArgs a) {
     const int T = (nwg - bid + G - 1) / G;                     // tiles of this workgroup (the launch keeps G <= nwg)
     auto tile_mn = [&](int c, int& m0_, int& n0_) {
         const int cnt = min(G, nwg - c * G);
-        s5_tile_origin(c * G + xcd_remap(bid, cnt), a.tiles_m, a.tiles_n, m0_, n0_);
+        tile_origin(c * G + xcd_remap(bid, cnt), a.tiles_m, a.tiles_n, BM, BN, m0_, n0_);
     };
 
     // epilogue staging rows of this wave (wave w4 of whichever group is draining: the two groups never drain at the same time)
@@ -254,18 +207,18 @@ __global__ __launch_bounds__(512) void gemm5_kernel(StaggerArgs a) {
         const_cast<bf16*>(HAS_IN ? a.in : (const bf16*)a.C), 0, HAS_IN ? (int)((int64_t)a.M * a.ldin * 2) : 0, 0x00020000);
     char* const inring = smem + 2 * BUF + 4 * STAGE + w4 * ((PD + 1) * 1024);
     const unsigned in_r = (unsigned)(uintptr_t)LDS_PTR(char, inring) + lane * 16;
-    const i32x4 rAux = s5_rsrc(EPI == S5_GELU_SAVE_DERIV ? (const void*)a.aux_out : (const void*)a.C,
-                               EPI == S5_GELU_SAVE_DERIV ? (unsigned)((int64_t)a.M * a.ldaux * 2) : 0u);
+    const i32x4 rAux = s5_rsrc(EPI == EPI_GELU_SAVE_DERIV ? (const void*)a.aux_out : (const void*)a.C,
+                               EPI == EPI_GELU_SAVE_DERIV ? (unsigned)((int64_t)a.M * a.ldaux * 2) : 0u);
 
     unsigned offA[4], offB[4], offB2[4];      // offB2: the partner group's half of the B K-tile (issued while the partner drains)
     int m0, n0;
     tile_mn(0, m0, n0);
-    s5_offsets(offB, a.ldb, n0, a.N, grp, w4, lane);
-    s5_offsets(offB2, a.ldb, n0, a.N, grp ^ 1, w4, lane);
-    s5_offsets(offA, a.lda, m0, a.M, grp, w4, lane);
+    half_offsets<UCFVIT_LAYOUT_KC, 256>(offB, a.ldb, n0, a.N, grp, w4, lane);
+    half_offsets<UCFVIT_LAYOUT_KC, 256>(offB2, a.ldb, n0, a.N, grp ^ 1, w4, lane);
+    half_offsets<UCFVIT_LAYOUT_KC, 256>(offA, a.lda, m0, a.M, grp, w4, lane);
     // prologue: stream step 0 = B K-tile 0 of the first panel (both halves), G0's A rows of K-tile 0 (G1's first K-step is step E)
-    s5_issue(a.B, offB, smem + A_BYTES, grp, w4);
-    if (grp == 0) s5_issue(a.A, offA, smem, grp, w4);
+    issue_half<256>(a.B, offB, smem + A_BYTES, grp, w4);
+    if (grp == 0) issue_half<256>(a.A, offA, smem, grp, w4);
     s5_wait_vm<0>();
     s5_barrier();
 
@@ -284,8 +237,8 @@ __global__ __launch_bounds__(512) void gemm5_kernel(StaggerArgs a) {
 
 #define S5_READ(bufA_, bufB_, c_)                                                                  \
     do {                                                                                           \
-        _Pragma("unroll") for (int j = 0; j < FN; ++j) fb[j] = s5_frag(bufB_, wn + 16 * j, c_, lane); \
-        _Pragma("unroll") for (int i = 0; i < FM; ++i) fa[i] = s5_frag(bufA_, wm + 16 * i, c_, lane); \
+        _Pragma("unroll") for (int j = 0; j < FN; ++j) fb[j] = kc_frag<bf16x8>(bufB_, wn + 16 * j, c_, lane); \
+        _Pragma("unroll") for (int i = 0; i < FM; ++i) fa[i] = kc_frag<bf16x8>(bufA_, wm + 16 * i, c_, lane); \
     } while (0)
 #define S5_COMPUTE()                                                                               \
     do {                                                                                           \
@@ -324,7 +277,7 @@ __global__ __launch_bounds__(512) void gemm5_kernel(StaggerArgs a) {
         }
         const f32x4 lo = plo[q & 1], hi = phi[q & 1];
         float v[8];
-        if constexpr (EPI == S5_MUL_AUX) {       // (data gradients carry no bias)
+        if constexpr (EPI == EPI_MUL_AUX) {       // (data gradients carry no bias)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 v[r] = lo[r] * a.alpha;
@@ -341,7 +294,7 @@ __global__ __launch_bounds__(512) void gemm5_kernel(StaggerArgs a) {
         const int m = em + 16 * i + 8 * ps;
         const bool inside = m < a.M && nok;
         const unsigned rowoff = (unsigned)(16 * i + 8 * ps);
-        if constexpr (EPI == S5_GELU_SAVE_DERIV) {
+        if constexpr (EPI == EPI_GELU_SAVE_DERIV) {
             float df[8];
             gelu_and_grad_fast8(v, df);
             Vec16<bf16> o;
@@ -349,11 +302,11 @@ __global__ __launch_bounds__(512) void gemm5_kernel(StaggerArgs a) {
             for (int r = 0; r < 8; ++r) o.set(r, df[r]);
             const unsigned vo = inside ? voAux + rowoff * (unsigned)(a.ldaux * 2) : S5_OOB;
             asm volatile("buffer_store_dwordx4 %0, %1, %2, 0 offen" S5_ST_MOD "\n\ts_nop 1" ::"v"(o.v), "v"(vo), "s"(rAux) : "memory");
-        } else if constexpr (EPI == S5_MUL_AUX || EPI == S5_RESIDUAL) {
+        } else if constexpr (EPI == EPI_MUL_AUX || EPI == EPI_RESIDUAL) {
             const bf16x8 h = __builtin_bit_cast(bf16x8, hin);
 #pragma unroll
             for (int r = 0; r < 8; ++r) {
-                if constexpr (EPI == S5_MUL_AUX) v[r] *= (float)h[r];
+                if constexpr (EPI == EPI_MUL_AUX) v[r] *= (float)h[r];
                 else v[r] += (float)h[r];
             }
         }
@@ -375,8 +328,8 @@ __global__ __launch_bounds__(512) void gemm5_kernel(StaggerArgs a) {
         s5_for<0, 4>([&](auto rc) __attribute__((always_inline)) {
             constexpr int r = decltype(rc)::value, u = 4 * J + r;
             if constexpr (r == 0) {
-                if constexpr (EpiLog<EPI, E>::OWN_B) s5_issue(bnext, offB, nb + A_BYTES, grp, w4);
-                if constexpr (J == E - 1) s5_issue(anext, offA, nb, grp, w4);
+                if constexpr (EpiLog<EPI, E>::OWN_B) issue_half<256>(bnext, offB, nb + A_BYTES, grp, w4);
+                if constexpr (J == E - 1) issue_half<256>(anext, offA, nb, grp, w4);
             }
             if constexpr (CS && u == 0) {
 #pragma unroll
@@ -427,7 +380,7 @@ __global__ __launch_bounds__(512) void gemm5_kernel(StaggerArgs a) {
         voC = (unsigned)(((int64_t)em * a.ldc + ncol) * 2);
         voIn = (unsigned)(((int64_t)em * a.ldin + ncol) * 2);
         voAux = (unsigned)(((int64_t)em * a.ldaux + ncol) * 2);
-        if constexpr (EPI != S5_MUL_AUX) {
+        if constexpr (EPI != EPI_MUL_AUX) {
             const unsigned vb = nok ? (unsigned)(ncol * 2) : S5_OOB;
             asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=v"(biasw) : "v"(vb), "s"(rBias) : "memory");
         }
@@ -470,8 +423,8 @@ __global__ __launch_bounds__(512) void gemm5_kernel(StaggerArgs a) {
                     const bool g0_last = grp == 0 && p == nk - 1;
                     const int kn = p == nk - 1 ? 0 : p + 1;            // the B panel is streamed cyclically
                     if (g0_last) epi_setup();
-                    s5_issue(a.B + kn * 128, offB, nb + A_BYTES, grp, w4);
-                    if (!g0_last) s5_issue(a.A + kn * 128, offA, nb, grp, w4);
+                    issue_half<256>(a.B + kn * 128, offB, nb + A_BYTES, grp, w4);
+                    if (!g0_last) issue_half<256>(a.A + kn * 128, offA, nb, grp, w4);
                     S5_READ(bufA, bufB, 0);
                     s5_barrier();
                     S5_COMPUTE();
@@ -499,12 +452,12 @@ __global__ __launch_bounds__(512) void gemm5_kernel(StaggerArgs a) {
             const bool knext = nxt_tile && (grp == 0 ? pn < nk : pn >= E);
             // ---- operands of the next stream step
             if (wrap && next_ok) {
-                s5_offsets(offB, a.ldb, nn0, a.N, grp, w4, lane);
-                s5_offsets(offB2, a.ldb, nn0, a.N, grp ^ 1, w4, lane);
+                half_offsets<UCFVIT_LAYOUT_KC, 256>(offB, a.ldb, nn0, a.N, grp, w4, lane);
+                half_offsets<UCFVIT_LAYOUT_KC, 256>(offB2, a.ldb, nn0, a.N, grp ^ 1, w4, lane);
             }
             const int kb = pn < nk ? pn : pn - nk;
             const char* bnext = a.B + (nxt_tile ? kb * 128 : 0);
-            if (knext && (grp == 0 ? pn == 0 : pn == E)) s5_offsets(offA, a.lda, wrap ? nm0 : m0, a.M, grp, w4, lane);
+            if (knext && (grp == 0 ? pn == 0 : pn == E)) half_offsets<UCFVIT_LAYOUT_KC, 256>(offA, a.lda, wrap ? nm0 : m0, a.M, grp, w4, lane);
             const char* anext = a.A + (knext ? kb * 128 : 0);
             if (kmode) {
                 if (grp == 0 ? p == 0 : (p == E && !(nk > E))) {
@@ -514,13 +467,13 @@ __global__ __launch_bounds__(512) void gemm5_kernel(StaggerArgs a) {
                         for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
                 }
                 if (grp == 0 ? p == nk - 1 : p == nk + E - 1) epi_setup();
-                s5_issue(bnext, offB, nb + A_BYTES, grp, w4);
+                issue_half<256>(bnext, offB, nb + A_BYTES, grp, w4);
                 if constexpr (!EpiLog<EPI, E>::OWN_B) {
-                    if (grp == 0 ? p < E : p >= nk) s5_issue(bnext, offB2, nb + A_BYTES, grp ^ 1, w4);     // the partner drains: its half too
+                    if (grp == 0 ? p < E : p >= nk) issue_half<256>(bnext, offB2, nb + A_BYTES, grp ^ 1, w4);     // the partner drains: its half too
                 } else {
-                    if (grp == 0 && c == 0 && p < E) s5_issue(bnext, offB2, nb + A_BYTES, grp ^ 1, w4);    // (G1 has not started yet)
+                    if (grp == 0 && c == 0 && p < E) issue_half<256>(bnext, offB2, nb + A_BYTES, grp ^ 1, w4);    // (G1 has not started yet)
                 }
-                if (knext) s5_issue(anext, offA, nb, grp, w4);
+                if (knext) issue_half<256>(anext, offA, nb, grp, w4);
                 S5_READ(bufA, bufB, 0);
                 s5_barrier();
                 S5_COMPUTE();
@@ -551,7 +504,7 @@ __global__ __launch_bounds__(512) void gemm5_kernel(StaggerArgs a) {
                 }
             } else if (grp == 1) {
                 // G1 before its first tile (G0 feeds the whole B stream): in the last of these steps it fetches its first A K-tile
-                if (knext) s5_issue(anext, offA, nb, grp, w4);
+                if (knext) issue_half<256>(anext, offA, nb, grp, w4);
                 s5_barrier();
                 s5_barrier();
                 s5_barrier();
@@ -594,17 +547,6 @@ template <int EPI, bool CS, int E> int s5_launch(const StaggerArgs& a, hipStream
     return UCFVIT_OK;
 }
 
-// UCFVIT_GEMM_STAGGER — a TEST / measurement hook: 0 keeps every launch on gemm3_kernel (tests/test_hip_ops.py compares the dynamic tile
-// schedule with the static order of the SAME kernel; tools/block_gemm_bench.py A/B), 1 / 2 / 4 / 8 force the number of epilogue steps
-// (tests/test_gemm_stagger.py runs every variant).  Read once (thread-safe static).
-int s5_steps_override() {
-    static const int v = [] {
-        const char* e = getenv("UCFVIT_GEMM_STAGGER");
-        return e ? atoi(e) : -1;
-    }();
-    return v;
-}
-
 }  // namespace
 
 #ifdef S5_STAMP
@@ -619,43 +561,18 @@ extern "C" int ucfvit_debug_stagger_stamps(unsigned long long* out, int* counts,
 }
 #endif
 
-// returns 1 when the staggered kernel ran the problem, 0 when the caller should use gemm3_kernel, < 0 on error.
-// The caller (gemm2.hip: launch3) has already checked the DMA path's alignment rules and that the 256x256 tile applies.
-int ucfvit_gemm_stagger_try(const ucfvit_gemm_desc* d, hipStream_t s) {
-    const int ov = s5_steps_override();
-    if (ov == 0) return 0;
-    if (d->dtype != UCFVIT_BF16 || d->out_dtype != UCFVIT_BF16 || d->a_layout != UCFVIT_LAYOUT_KC || d->b_layout != UCFVIT_LAYOUT_KC) return 0;
-    if (d->accumulate || d->sched_state || d->K % 64 != 0 || d->N % 8 != 0) return 0;
-    const int64_t lim = (1ll << 31) - 1;
-    if (d->M * d->ldc * 2 > lim || d->M * d->lda * 2 >= (1ll << 32) || d->N * d->ldb * 2 >= (1ll << 32)) return 0;
-    int epi;
-    if (d->act == UCFVIT_ACT_NONE && !d->residual && !d->aux_out && !d->aux_in) epi = S5_PLAIN;
-    else if (d->act == UCFVIT_ACT_NONE && d->residual && !d->aux_out && !d->aux_in) epi = S5_RESIDUAL;
-    else if (d->act == UCFVIT_ACT_GELU_SAVE_DERIV && !d->residual && d->aux_out) epi = S5_GELU_SAVE_DERIV;
-    else if (d->act == UCFVIT_ACT_MUL_AUX && !d->residual && !d->aux_out && d->aux_in) epi = S5_MUL_AUX;
-    else return 0;
-    if (d->c_colsum_partial && epi != S5_MUL_AUX) return 0;
-    if (epi == S5_MUL_AUX && d->bias) return 0;             // (data gradients carry no bias: that epilogue has no bias registers)
-    if (epi == S5_RESIDUAL && d->M * d->ldr * 2 > lim) return 0;
-    if ((epi == S5_MUL_AUX || epi == S5_GELU_SAVE_DERIV) && d->M * d->ldaux * 2 > lim) return 0;
-    const int nk = (int)(d->K / 64);
+// GK_STAGGER of a route: gemm5_kernel with the route's epilogue and number of epilogue steps
+int ucfvit_gemm_launch_stagger(const ucfvit_gemm_desc* d, const GemmRoute& r, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    const int epi = r.epi;
     StaggerArgs a;
     a.A = (const char*)d->A;
     a.B = (const char*)d->B;
     a.C = (bf16*)d->C;
-    if (d->bias) {
-        a.bias = (const bf16*)d->bias;
-        a.bias_bytes = (unsigned)(d->N * 2);
-    } else {
-        static void* const zp = [] {               // looked up once (thread-safe static); nullptr: this launch stays on gemm3_kernel
-            void* q = nullptr;
-            return hipGetSymbolAddress(&q, HIP_SYMBOL(g_s5_zero_page)) == hipSuccess ? q : nullptr;
-        }();
-        if (!zp) return 0;
-        a.bias = (const bf16*)zp;
-        a.bias_bytes = 0;                                   // every lane out of range: the bias reads as zero
-    }
-    a.in = (const bf16*)(epi == S5_RESIDUAL ? d->residual : d->aux_in);
+    // no bias: a buffer of 0 bytes, every lane out of range, the bias reads as zero whatever the address (C: a valid one)
+    a.bias = (const bf16*)(d->bias ? d->bias : d->C);
+    a.bias_bytes = d->bias ? (unsigned)(d->N * 2) : 0u;
+    a.in = (const bf16*)(epi == EPI_RESIDUAL ? d->residual : d->aux_in);
     a.aux_out = (bf16*)d->aux_out;
     a.cs_partial = d->c_colsum_partial;
     a.M = (int)d->M;
@@ -664,35 +581,19 @@ int ucfvit_gemm_stagger_try(const ucfvit_gemm_desc* d, hipStream_t s) {
     a.lda = d->lda;
     a.ldb = d->ldb;
     a.ldc = (int)d->ldc;
-    a.ldin = (int)(epi == S5_RESIDUAL ? d->ldr : d->ldaux);
+    a.ldin = (int)(epi == EPI_RESIDUAL ? d->ldr : d->ldaux);
     a.ldaux = (int)d->ldaux;
     a.alpha = d->alpha;
     a.tiles_m = (int)((d->M + 255) / 256);
     a.tiles_n = (int)((d->N + 255) / 256);
     a.total_tiles = a.tiles_m * a.tiles_n;
-    const bool cs = d->c_colsum_partial != nullptr;
-    // Epilogue steps.  Measured (tools/block_gemm_bench.py, ViT-L shapes at M = 131005; profiles/r03_a_*): a K-step with only ONE group
-    // computing costs about what a paired K-step costs (the step is paced by the DMA round trip, not by the MFMAs), so the fewer such steps
-    // the better: E = 1 wins everywhere it applies, larger E loses.  The residual epilogue only pays for itself behind a long K loop, and
-    // the column-sum variant of the multiply epilogue does not fit the register budget at E = 1: both stay on gemm3_kernel.
-    // Which launches: per-shape A/B at the shapes of all five workloads (profiles/r03_c_stagger_shapes.txt): the staggered kernel wins
-    // 3-7 % at K >= 1536, 0-6 % at K = 1024 and LOSES 4-10 % at K = 768 / 512 (the cyclic re-read of a B K-tile and the two unpaired steps
-    // per tile weigh 1 / nk): K >= 1024 only.
-    int E = 1;                                       // (fc1 forward with the GELU epilogue, E = 1 / 2 / 4 / 8: 1251 / 1262 / 1317 / 1652 us)
-    if (ov > 0) E = ov;
-    else if (nk < 16) return 0;
-    else if (epi == S5_RESIDUAL && nk < 32) return 0;
-    else if (cs) return 0;
-    if (nk < 2 * E) E = nk >= 8 ? 4 : (nk >= 4 ? 2 : (nk >= 2 ? 1 : 0));
-    if (E == 0 || (cs && E == 1)) return 0;
-    int rc;
+    const int E = r.stagger_steps;
 #define S5_GO(EPI_, CS_)                                                               \
     (E == 1 ? s5_launch<EPI_, CS_, 1>(a, s) : E == 2 ? s5_launch<EPI_, CS_, 2>(a, s) : \
      E == 4 ? s5_launch<EPI_, CS_, 4>(a, s) : s5_launch<EPI_, CS_, 8>(a, s))
-    if (epi == S5_PLAIN) rc = S5_GO(S5_PLAIN, false);
-    else if (epi == S5_RESIDUAL) rc = S5_GO(S5_RESIDUAL, false);
-    else if (epi == S5_GELU_SAVE_DERIV) rc = S5_GO(S5_GELU_SAVE_DERIV, false);
-    else rc = cs ? S5_GO(S5_MUL_AUX, true) : S5_GO(S5_MUL_AUX, false);
+    if (epi == EPI_PLAIN) return S5_GO(EPI_PLAIN, false);
+    if (epi == EPI_RESIDUAL) return S5_GO(EPI_RESIDUAL, false);
+    if (epi == EPI_GELU_SAVE_DERIV) return S5_GO(EPI_GELU_SAVE_DERIV, false);
+    return r.cs ? S5_GO(EPI_MUL_AUX, true) : S5_GO(EPI_MUL_AUX, false);
 #undef S5_GO
-    return rc == UCFVIT_OK ? 1 : rc;
 }
