@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define UCFVIT_ABI_VERSION 16
+#define UCFVIT_ABI_VERSION 17
 
 #define UCFVIT_OK 0
 #define UCFVIT_ERR_INVALID_ARGUMENT (-1)
@@ -157,6 +157,13 @@ int64_t ucfvit_layernorm_bwd_workspace(int64_t rows, int64_t D);
 int ucfvit_layernorm_bwd(const void* dy, const void* x, const void* gamma, const float* mean, const float* rstd,
                          const void* dres, void* dx, float* dgamma, float* dbeta, int64_t rows, int64_t D, int accumulate,
                          float* dx_colsum, int dx_colsum_accumulate, void* workspace, int dtype, void* stream);
+/* The same backward with a residual-branch gradient that exists for one row in every `dres_period` only: row r receives
+ * dres[r / dres_period] (dres: [ceil(rows / dres_period)][D] dtype) when r % dres_period == 0 and +0 otherwise, i.e. exactly what
+ * ucfvit_layernorm_bwd computes for that dres expanded to [rows][D] with zeros, bit for bit, without the expanded array existing.
+ * (The class-token rows of a [B][N][D] residual stream: dres_period = N.)  dres_period = 1 is ucfvit_layernorm_bwd; rows < 2^31. */
+int ucfvit_layernorm_bwd_rows(const void* dy, const void* x, const void* gamma, const float* mean, const float* rstd,
+                              const void* dres, int64_t dres_period, void* dx, float* dgamma, float* dbeta, int64_t rows, int64_t D,
+                              int accumulate, float* dx_colsum, int dx_colsum_accumulate, void* workspace, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Fused multi-head self-attention core, softmax(q·kᵀ·scale)·v, non-causal, no mask, dropout 0:
@@ -185,6 +192,20 @@ int ucfvit_attention_bwd_colsum_supported(int64_t B, int64_t N, int64_t H, int64
 int ucfvit_attention_bwd_colsum(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv,
                                 float* delta_ws, float* colsum_partial, int64_t B, int64_t N, int64_t H, int64_t dh, float scale,
                                 int dtype, void* stream);
+
+/* The same attention for ONE query row per batch element (a model whose head reads only the class token needs nothing else of its
+ * last Block's attention output).  qkv as above, all N keys / values are read; the query is token `qrow` of every batch element.
+ *   fwd: out [B][H*dh] dtype (compact: one row per batch element), lse fp32 [B][H], log2 domain.
+ *   bwd: dout / out are the compact [B][H*dh] rows; dqkv (qkv's layout) is written whole: the K and V thirds of every token, the Q
+ *        third of token `qrow`, zeros in the Q third of every other token.
+ *        colsum_partial (optional) fp32 [B][2][H][dh]: row b = dq of batch element b (fp32, before rounding), then H dh zeros — the
+ *        same contract as ucfvit_attention_bwd_colsum (the V third of the bias gradient is the column sum of the compact dout).
+ * fp32 and bf16, dh in {32, 64, 128}, N <= 8192; one pass over K and V, plain VALU arithmetic (HBM-bound). */
+int ucfvit_attention_rows_fwd(const void* qkv, void* out, float* lse, int64_t B, int64_t N, int64_t H, int64_t dh, int64_t qrow,
+                              float scale, int dtype, void* stream);
+int ucfvit_attention_rows_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv,
+                              float* colsum_partial, int64_t B, int64_t N, int64_t H, int64_t dh, int64_t qrow, float scale,
+                              int dtype, void* stream);
 
 /* Attention of a QUERY block against ANOTHER token block's keys / values: the building block of ring sequence parallelism (no reference
  * counterpart: the reference constructs seq_par_group and asserts seq_par_size == 1, training_scripts/train_masked_fsdp.py:220).

@@ -55,7 +55,7 @@ class WgradQueue:
 
     def __init__(self):
         self.items, self.owners = [], []
-        self.tiles = 0
+        self.tiles, self.tiles_by_rows = 0, {}
         self.deferrable = True
         self.callback_armed = False
         self.listeners = []          # called after every flush (HipDataParallel launches the buckets that were waiting for it)
@@ -81,7 +81,12 @@ class WgradQueue:
         self.items.append((dy2, x2, o2, acc))
         # (o2 is a separate view object: holding `out` itself would raise its use count and make AccumulateGrad clone it)
         self.owners.append((weight, o2) if (out is not None and not acc) else None)
-        self.tiles += ((dy2.shape[1] + 255) // 256) * ((x2.shape[1] + 255) // 256)
+        # one grouped launch takes problems of ONE reduction length (token rows): a tail Block's compact gradients (B rows) wait next to
+        # the dense ones (B N rows) and ops.wgrad_grouped sends them as a launch of their own; the round count below is that of the
+        # fullest launch
+        rows = dy2.shape[0]
+        self.tiles_by_rows[rows] = self.tiles_by_rows.get(rows, 0) + ((dy2.shape[1] + 255) // 256) * ((x2.shape[1] + 255) // 256)
+        self.tiles = max(self.tiles_by_rows.values())
         return ret
 
     def end_block(self):
@@ -111,7 +116,7 @@ class WgradQueue:
 
     def flush(self):
         items, owners = self.items, self.owners
-        self.items, self.owners, self.tiles, self.deferrable = [], [], 0, True
+        self.items, self.owners, self.tiles, self.tiles_by_rows, self.deferrable = [], [], 0, {}, True
         for i in range(0, len(items), self.MAX_PROBLEMS):
             ops.wgrad_grouped(items[i:i + self.MAX_PROBLEMS])
         for ow in owners:
@@ -188,14 +193,14 @@ def _bgrad(bias, dy2):
     return None if acc else r
 
 
-def _ln_bwd(dy2, x2, gamma_c, mean, rstd, weight, bias, dres=None, dx_colsum=None, dx_colsum_accumulate=False):
+def _ln_bwd(dy2, x2, gamma_c, mean, rstd, weight, bias, dres=None, dx_colsum=None, dx_colsum_accumulate=False, dres_period=1):
     ow, aw = grad_target(weight)
     ob, ab = grad_target(bias)
     if aw != ab or (ow is None) != (ob is None):  # mixed states: take the simple route
         ow = ob = None
         aw = ab = False
     dx, dg, db = ops.layernorm_bwd(dy2, x2, gamma_c, mean, rstd, dres=dres, dgamma=ow, dbeta=ob, accumulate=aw, dx_colsum=dx_colsum,
-                                   dx_colsum_accumulate=dx_colsum_accumulate)
+                                   dx_colsum_accumulate=dx_colsum_accumulate, dres_period=dres_period)
     return dx, (None if aw else dg), (None if ab else db)
 
 
@@ -540,6 +545,99 @@ class BlockFn(torch.autograd.Function):
             _publish_stream_colsum(wq, dx, cs0)
         wq.end_block()                                   # the Block's 4 weight gradients: grouped launch now, or with the next Blocks'
         return (_ret_grad(dx.view(B, N, -1), in_dtype), g_n1w, g_n1b) + ga + (g_n2w, g_n2b) + gm + (None, None, None, None, None)
+
+
+TAIL_ROWS = os.environ.get("UCFVIT_TAIL_ROWS", "1") != "0"     # A/B switch: 0 = the last Block runs dense like every other
+TAIL_ROWS_MAX_TOKENS = 8192                                    # AR_MAX_N of csrc/attention_rows.hip
+
+
+class TailBlockFn(torch.autograd.Function):
+    """BlockFn for the LAST Block of a model whose head reads only the class token (token 0 of every sequence; the final norm is
+    row-wise): [B, N, D] -> the Block's output for those B rows, [B, D].  Everything up to the keys and values is needed for every
+    token (LayerNorm 1, the qkv GEMM); from the attention on only the class rows are computed: one query per head
+    (ops.attention_rows_fwd), then proj / LayerNorm 2 / fc1 / fc2 as M = B GEMMs, the proj residual read in place from the strided
+    class rows of x (ldr = N D).  Backward: the same compact chain, weight gradients queued with B reduction rows; the gradient turns
+    dense again at dK / dV (ops.attention_rows_bwd) and the class rows' residual gradient joins the dense dx inside the LayerNorm-1
+    backward (dres_period = N), rounded once like the dense Block's."""
+
+    @staticmethod
+    def _run_forward(x2, B, N, num_heads, eps, c, params):
+        n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b = params
+        D = x2.shape[1]
+        dh = D // num_heads
+        ln1, mean1, rstd1 = ops.layernorm_fwd(x2, c(n1w), c(n1b), eps)
+        qkv = ops.linear_fwd(ln1, c(qkvw), c(qkvb))
+        o, lse = ops.attention_rows_fwd(qkv, B, N, num_heads, dh, dh ** -0.5, 0)
+        x1 = ops.linear_fwd(o, c(projw), c(projb), residual=x2.view(B, N, D)[:, 0])   # class rows of the stream: a [B, D] view, row stride N D
+        ln2, mean2, rstd2 = ops.layernorm_fwd(x1, c(n2w), c(n2b), eps)
+        y, (h, a) = _mlp_fwd(ln2, c(f1w), c(f1b), c(f2w), c(f2b), x1)
+        return y, (mean1, rstd1, ln1, qkv, o, lse, x1, mean2, rstd2, ln2, h, a)
+
+    @staticmethod
+    def forward(ctx, x, n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b, num_heads, eps, cdtype, recompute=False):
+        """recompute: as in BlockFn, only the Block's input is kept and backward re-runs the forward launches (bit-identical)"""
+        xin = _as(x, cdtype)
+        B, N, D = xin.shape
+        x2 = xin.view(B * N, D)
+        c = lambda p: compute_param(p, cdtype)
+        params = (n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b)
+        y, saved = TailBlockFn._run_forward(x2, B, N, num_heads, eps, c, params)
+        if recompute:
+            ctx.save_for_backward(x2, *params)
+        else:
+            ctx.save_for_backward(x2, *saved, *params)
+        ctx.meta = (B, N, num_heads, cdtype, x.dtype)
+        ctx.recompute, ctx.eps = recompute, eps
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        B, N, H, cdtype, in_dtype = ctx.meta
+        c = lambda p: compute_param(p, cdtype)
+        if ctx.recompute:
+            x2, *params = ctx.saved_tensors
+            _, saved = TailBlockFn._run_forward(x2, B, N, H, ctx.eps, c, tuple(params))
+            (mean1, rstd1, ln1, qkv, o, lse, x1, mean2, rstd2, ln2, h, a) = saved
+            n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b = params
+        else:
+            (x2, mean1, rstd1, ln1, qkv, o, lse, x1, mean2, rstd2, ln2, h, a,
+             n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b) = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        D = x2.shape[1]
+        dh = D // H
+        dy2 = _as(dy, cdtype).reshape(B, D)
+        wq = _queue_for(qkvw)
+        dln2, gm = _mlp_bwd(dy2, ln2, (h, a), c(f1w), c(f2w), f1w, f1b, f2w, f2b, need[9:13], None, wq, dy2_colsum=_take_stream_colsum(wq, dy2))
+        pb_out, pb_acc, g_projb = None, False, None
+        if projb is not None and need[6]:
+            pb_out, pb_acc = grad_target(projb)
+            if pb_out is None:
+                pb_out = torch.empty(projb.shape, dtype=torch.float32, device=dy2.device)
+            g_projb = None if pb_acc else pb_out
+        dx1, g_n2w, g_n2b = _ln_bwd(dln2, x1, c(n2w), mean2, rstd2, n2w, n2b, dres=dy2, dx_colsum=pb_out, dx_colsum_accumulate=pb_acc)
+        g_projw = _wgrad(projw, dx1, o, wq) if need[5] else None
+        want_b = qkvb is not None and need[4]
+        if want_b:
+            # Q third: dq of every image, summed; K third: 0 exactly; V third: the column sums of the compact dO (see _attn_bwd)
+            gb, acc = grad_target(qkvb)
+            if gb is None:
+                gb, acc = torch.empty(3 * D, dtype=torch.float32, device=dy2.device), False
+            do = _dgrad(dx1, projw, c(projw), c_colsum=gb[2 * D:], c_colsum_accumulate=acc)
+            dqkv, part = ops.attention_rows_bwd(qkv, o, do, lse, B, N, H, dh, dh ** -0.5, 0, want_colsum=True)
+            ops.reduce_rows(part, gb[:2 * D], accumulate=acc)
+            g_qkvb = None if acc else gb
+        else:
+            do = _dgrad(dx1, projw, c(projw))
+            dqkv = ops.attention_rows_bwd(qkv, o, do, lse, B, N, H, dh, dh ** -0.5, 0)
+            g_qkvb = None
+        g_qkvw = _wgrad(qkvw, dqkv, ln1, wq) if need[3] else None
+        dln1 = _dgrad(dqkv, qkvw, c(qkvw))
+        cs0 = torch.empty(D, dtype=torch.float32, device=dy2.device) if _BIAS_FROM_EPILOGUE else None
+        dx, g_n1w, g_n1b = _ln_bwd(dln1, x2, c(n1w), mean1, rstd1, n1w, n1b, dres=dx1, dx_colsum=cs0, dres_period=N)
+        if cs0 is not None and in_dtype == cdtype:
+            _publish_stream_colsum(wq, dx, cs0)           # the fc2 bias gradient of the Block before this one
+        wq.end_block()
+        return (_ret_grad(dx.view(B, N, D), in_dtype), g_n1w, g_n1b, g_qkvw, g_qkvb, g_projw, g_projb, g_n2w, g_n2b) + gm + (None, None, None, None)
 
 
 class PatchEmbedFn(torch.autograd.Function):

@@ -141,7 +141,17 @@ def gemm(A, B, M, N, K, a_layout, b_layout, out=None, out_dtype=None, bias=None,
 
 
 def wgrad_grouped(items):
-    """items: list of (dy2 [M,N], x2 [M,K], out [N,K] (fp32 or bf16) or None (fp32), accumulate) -> list of dW tensors; ONE launch when groupable"""
+    """items: list of (dy2 [M,N], x2 [M,K], out [N,K] (fp32 or bf16) or None (fp32), accumulate) -> list of dW tensors; ONE launch when groupable.
+    The library groups problems of one reduction length M: items of several lengths (the compact gradients of a tail Block among dense
+    ones) go out as one launch per length."""
+    rows = {it[0].shape[0] for it in items}
+    if len(rows) > 1:
+        outs = [None] * len(items)
+        for r in sorted(rows, reverse=True):
+            idx = [i for i, it in enumerate(items) if it[0].shape[0] == r]
+            for i, o in zip(idx, wgrad_grouped([items[i] for i in idx])):
+                outs[i] = o
+        return outs
     L = _l.load()
     n = len(items)
     outs = []
@@ -232,21 +242,26 @@ def layernorm_fwd(x2, gamma, beta, eps):
 
 
 def layernorm_bwd(dy2, x2, gamma, mean, rstd, dres=None, dgamma=None, dbeta=None, accumulate=False, dx_colsum=None,
-                  dx_colsum_accumulate=False):
-    """-> dx, dgamma, dbeta; dx_colsum: optional fp32 [D] that receives (+)= the column sums of dx (a bias gradient, see the header)"""
+                  dx_colsum_accumulate=False, dres_period=1):
+    """-> dx, dgamma, dbeta; dx_colsum: optional fp32 [D] that receives (+)= the column sums of dx (a bias gradient, see the header).
+    dres_period = P > 1: dres is compact, [ceil(rows / P), D], and belongs to rows 0, P, 2 P, ... (every other row adds +0)"""
     L = _l.load()
     _chk(dy2, "layernorm_bwd.dy")
     rows, D = x2.shape
+    if dres is not None:
+        _chk(dres, "layernorm_bwd.dres")
+        if dres_period < 1 or tuple(dres.shape) != (-(-rows // dres_period), D) or dres.dtype != x2.dtype:
+            raise ValueError("layernorm_bwd: dres must be [ceil(rows / dres_period), D] of x's dtype")
     dx = torch.empty_like(x2)
     if dgamma is None:
         dgamma = torch.empty(D, dtype=torch.float32, device=x2.device)
     if dbeta is None:
         dbeta = torch.empty(D, dtype=torch.float32, device=x2.device)
     ws = workspace(L.ucfvit_layernorm_bwd_workspace(rows, D), x2.device)
-    _l.check(L.ucfvit_layernorm_bwd(dy2.data_ptr(), x2.data_ptr(), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _p(dres),
-                                    dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), rows, D, 1 if accumulate else 0,
-                                    _p(dx_colsum), 1 if dx_colsum_accumulate else 0, ws.data_ptr(), dt(x2), _stream()),
-             "ucfvit_layernorm_bwd")
+    _l.check(L.ucfvit_layernorm_bwd_rows(dy2.data_ptr(), x2.data_ptr(), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _p(dres),
+                                         int(dres_period), dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), rows, D, 1 if accumulate else 0,
+                                         _p(dx_colsum), 1 if dx_colsum_accumulate else 0, ws.data_ptr(), dt(x2), _stream()),
+             "ucfvit_layernorm_bwd_rows")
     return dx, dgamma, dbeta
 
 
@@ -282,6 +297,31 @@ def attention_bwd(qkv, out, dout, lse, B, N, H, dh, scale, want_colsum=False):
     _l.check(L.ucfvit_attention_bwd(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(), dqkv.data_ptr(), delta.data_ptr(),
                                     B, N, H, dh, scale, dt(qkv), _stream()), "ucfvit_attention_bwd")
     return (dqkv, None) if want_colsum else dqkv
+
+
+def attention_rows_fwd(qkv, B, N, H, dh, scale, qrow=0):
+    """one query (token `qrow`) per batch element against all N keys: qkv [B*N, 3*H*dh] -> out [B, H*dh] (compact), lse [B, H]"""
+    L = _l.load()
+    _chk(qkv, "attention_rows.qkv")
+    out = torch.empty((B, H * dh), dtype=qkv.dtype, device=qkv.device)
+    lse = torch.empty((B, H), dtype=torch.float32, device=qkv.device)
+    _l.check(L.ucfvit_attention_rows_fwd(qkv.data_ptr(), out.data_ptr(), lse.data_ptr(), B, N, H, dh, int(qrow), scale, dt(qkv), _stream()),
+             "ucfvit_attention_rows_fwd")
+    return out, lse
+
+
+def attention_rows_bwd(qkv, out, dout, lse, B, N, H, dh, scale, qrow=0, want_colsum=False):
+    """out / dout: compact [B, H*dh] -> dqkv [B*N, 3*H*dh] (Q third: token `qrow` only, zeros elsewhere), or (dqkv, partial fp32 [B, 2 H dh])
+    with want_colsum (partial: dq of every batch element, then zeros; see attention_bwd)"""
+    L = _l.load()
+    _chk(out, "attention_rows_bwd.out"), _chk(dout, "attention_rows_bwd.dout"), _chk(qkv, "attention_rows_bwd.qkv")
+    if tuple(out.shape) != (B, H * dh) or tuple(dout.shape) != (B, H * dh) or dout.dtype != qkv.dtype or out.dtype != qkv.dtype:
+        raise ValueError("attention_rows_bwd: out and dout must be [B, H*dh] of qkv's dtype")
+    dqkv = torch.empty_like(qkv)
+    part = torch.empty((B, 2 * H * dh), dtype=torch.float32, device=qkv.device) if want_colsum else None
+    _l.check(L.ucfvit_attention_rows_bwd(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(), dqkv.data_ptr(), _p(part), B, N, H, dh,
+                                         int(qrow), scale, dt(qkv), _stream()), "ucfvit_attention_rows_bwd")
+    return (dqkv, part) if want_colsum else dqkv
 
 
 def attention_cross_fwd(q, k, v, B, Nq, Nk, H, dh, scale):

@@ -307,8 +307,33 @@ class VIT(nn.Module):
             raise NotImplementedError("drop_rate > 0 is not on the HIP hot path")
         return self.head(x)
 
+    def tail_rows_applies(self) -> bool:
+        """forward() may run the last Block for the class-token rows only (HF.TailBlockFn): pooling takes token 0 of every sequence
+        directly behind the row-wise final norm, so nothing else of that Block's output is read.  Not for subclasses (their heads read
+        every token; the tensor-parallel models); forward_features() and forward_intermediates() always return all tokens.  A
+        checkpointed last Block keeps its recompute inside the tail, so checkpointed and plain runs stay bit-identical.
+        UCFVIT_TAIL_ROWS=0 switches it off."""
+        if not HF.TAIL_ROWS or type(self) is not VIT or self.num_prefix_tokens != 1 or self.head is None or len(self.blocks) == 0:
+            return False
+        if getattr(self, "tensor_par_size", 1) > 1 or type(self.norm) is not LayerNorm or type(self.patch_drop) is not nn.Identity:
+            return False
+        blk = self.blocks[-1]
+        return type(blk) is Block and blk._fusable()
+
     def forward(self, x: torch.Tensor, variables, seq_ps=None) -> torch.Tensor:
-        return self.forward_head(self.forward_features(x, variables, seq_ps))
+        if not self.tail_rows_applies():
+            return self.forward_head(self.forward_features(x, variables, seq_ps))
+        self._prepare()
+        x = self._pos_embed(self._embed_tokens(x, variables), seq_ps)
+        for blk in self.blocks[:-1]:
+            x = blk(x)
+        if x.dim() == 3 and x.shape[1] <= HF.TAIL_ROWS_MAX_TOKENS:
+            x = self.norm(self.blocks[-1].forward_class_rows(x))            # [B, D]: the rows pool() would take
+        else:
+            x = self.pool(self.norm(self.blocks[-1](x)))
+        if self.head_drop.p > 0.0 and self.training:
+            raise NotImplementedError("drop_rate > 0 is not on the HIP hot path")
+        return self.head(x)
 
 
 class SAP(VIT):

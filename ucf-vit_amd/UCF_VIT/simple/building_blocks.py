@@ -255,6 +255,19 @@ class Block(nn.Module):
         x = x + self.drop_path2(self.ls2(self.mlp(self.norm2(x))))
         return x
 
+    def forward_class_rows(self, x: torch.Tensor) -> torch.Tensor:
+        """forward(x)[:, 0] computed without the other rows (HF.TailBlockFn); the caller checked _fusable()"""
+        for d in (self.drop_path1, self.drop_path2):
+            if isinstance(d, DropPath):
+                _no_dropout(d.drop_prob, self.training, "drop_path")
+        a, m = self.attn, self.mlp
+        _no_dropout(a.attn_drop.p, self.training, "attn_drop")
+        _no_dropout(a.proj_drop.p, self.training, "proj_drop")
+        _no_dropout(m.drop1.p, self.training, "Mlp.drop")
+        return HF.TailBlockFn.apply(x, self.norm1.weight, self.norm1.bias, a.qkv.weight, a.qkv.bias, a.proj.weight, a.proj.bias,
+                                    self.norm2.weight, self.norm2.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias,
+                                    a.num_heads, self.norm1.eps, _cd(self), self.activation_checkpointing and torch.is_grad_enabled())
+
 
 class MyUnetBlock(nn.Module):
     """Transposed-conv upsampling stage of the skip-less UNETR decoder (reference :241-284; monai get_conv_layer(conv_only,

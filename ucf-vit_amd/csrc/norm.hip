@@ -68,11 +68,14 @@ __global__ __launch_bounds__(LN_THREADS) void ln_fwd_kernel(const T* __restrict_
 // backward: dx = rstd * (g - mean(g) - xhat * mean(g*xhat)), g = dy*gamma ; per-workgroup partial dgamma/dbeta
 // DXS: also the column sums of dx (+ dres) = the bias gradient of the Linear layer that produced LayerNorm's input's residual
 // partner (proj / fc2 of the Block before): third row of the per-workgroup partials
-template <typename T, int NV, bool DXS>
+// PERIODIC: dres holds one row for every `period` rows (row r takes dres[r / period] when r % period == 0, +0 otherwise: the sum is
+// formed and rounded exactly as with the expanded array)
+template <typename T, int NV, bool DXS, bool PERIODIC>
 __global__ __launch_bounds__(LN_THREADS) void ln_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ x,
                                                             const T* __restrict__ gamma, const float* __restrict__ mean,
                                                             const float* __restrict__ rstd, const T* __restrict__ dres,
-                                                            T* __restrict__ dx, float* __restrict__ partial, int64_t rows, int D) {
+                                                            T* __restrict__ dx, float* __restrict__ partial, int64_t rows, int D,
+                                                            int period) {
     constexpr int EPV = Vec16<T>::N;
     __shared__ float red[4][64 * 8 + 8];  // cross-wave reduction staging, one 16-B vector slot (as fp32 x EPV) at a time
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -115,12 +118,24 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_kernel(const T* __restrict_
             }
         }
         const float c1 = wave_sum(s1) / (float)D, c2 = wave_sum(s2) / (float)D;
+        int64_t rrow = row;          // the row of dres
+        bool has_r = true;
+        if constexpr (PERIODIC) {
+            const unsigned qr = (unsigned)row / (unsigned)period;
+            has_r = (unsigned)row == qr * (unsigned)period;
+            rrow = qr;
+        }
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const int v = lane + 64 * i;
             if (v < nvec) {
                 Vec16<T> o, rv;
-                if (dres) rv = *reinterpret_cast<const Vec16<T>*>(dres + row * D + v * EPV);
+                if (dres) {
+                    if (has_r) rv = *reinterpret_cast<const Vec16<T>*>(dres + rrow * D + v * EPV);
+                    else
+#pragma unroll
+                        for (int e = 0; e < EPV; ++e) rv.set(e, 0.f);
+                }
 #pragma unroll
                 for (int e = 0; e < EPV; ++e) {
                     const float xh = (xv[i].get(e) - mu) * rs;
@@ -296,28 +311,34 @@ int ln_fwd_t(const void* x, const void* gamma, const void* beta, void* y, float*
 }
 
 template <typename T>
-int ln_bwd_t(const void* dy, const void* x, const void* gamma, const float* mean, const float* rstd, const void* dres, void* dx, float* dgamma,
-             float* dbeta, int64_t rows, int64_t D, int accumulate, float* dx_colsum, int dx_colsum_accumulate, void* ws, hipStream_t s) {
+int ln_bwd_t(const void* dy, const void* x, const void* gamma, const float* mean, const float* rstd, const void* dres, int64_t period, void* dx,
+             float* dgamma, float* dbeta, int64_t rows, int64_t D, int accumulate, float* dx_colsum, int dx_colsum_accumulate, void* ws, hipStream_t s) {
     const int nv = ln_nv<T>(D);
     UCF_CHECK_ARG(nv > 0 && nv <= 4, "ucfvit_layernorm_bwd: D=%lld must be a multiple of %d and <= %d", (long long)D,
                   (int)(16 / sizeof(T)), (int)(256 * 16 / sizeof(T)));
     const int g = ln_grid(rows);
     const dim3 grid(g), block(LN_THREADS);
+#define LN_BWD_K(NVV, DXS_, PER_)                                                                                                \
+    hipLaunchKernelGGL((ln_bwd_kernel<T, NVV, DXS_, PER_>), grid, block, 0, s, (const T*)dy, (const T*)x, (const T*)gamma, mean, rstd, \
+                       (const T*)dres, (T*)dx, (float*)ws, rows, (int)D, (int)period)
 #define LN_BWD(NVV)                                                                                                            \
     do {                                                                                                                       \
-        if (dx_colsum)                                                                                                         \
-            hipLaunchKernelGGL((ln_bwd_kernel<T, NVV, true>), grid, block, 0, s, (const T*)dy, (const T*)x, (const T*)gamma, mean, rstd, \
-                               (const T*)dres, (T*)dx, (float*)ws, rows, (int)D);                                             \
-        else                                                                                                                   \
-            hipLaunchKernelGGL((ln_bwd_kernel<T, NVV, false>), grid, block, 0, s, (const T*)dy, (const T*)x, (const T*)gamma, mean, rstd, \
-                               (const T*)dres, (T*)dx, (float*)ws, rows, (int)D);                                             \
+        if (dx_colsum) {                                                                                                       \
+            if (periodic) LN_BWD_K(NVV, true, true);                                                                           \
+            else LN_BWD_K(NVV, true, false);                                                                                   \
+        } else {                                                                                                               \
+            if (periodic) LN_BWD_K(NVV, false, true);                                                                          \
+            else LN_BWD_K(NVV, false, false);                                                                                  \
+        }                                                                                                                      \
     } while (0)
+    const bool periodic = dres && period > 1;
     switch (nv) {
         case 1: LN_BWD(1); break;
         case 2: LN_BWD(2); break;
         default: LN_BWD(4); break;
     }
 #undef LN_BWD
+#undef LN_BWD_K
     UCF_LAUNCH_CHECK("ucfvit_layernorm_bwd");
     const int W = (dx_colsum ? 3 : 2) * (int)D;
     hipLaunchKernelGGL(reduce_partials_kernel, dim3((W + RP_COLS - 1) / RP_COLS), dim3(256), 0, s, (const float*)ws, dgamma, dbeta, g, (int)D,
@@ -346,21 +367,29 @@ extern "C" int64_t ucfvit_layernorm_bwd_workspace(int64_t rows, int64_t D) {
     return (int64_t)ln_grid(rows) * 3 * D * (int64_t)sizeof(float);      // dgamma, dbeta and (optional) dx column-sum partials
 }
 
-extern "C" int ucfvit_layernorm_bwd(const void* dy, const void* x, const void* gamma, const float* mean, const float* rstd,
-                                    const void* dres, void* dx, float* dgamma, float* dbeta, int64_t rows, int64_t D, int accumulate,
-                                    float* dx_colsum, int dx_colsum_accumulate, void* workspace, int dtype, void* stream) {
+extern "C" int ucfvit_layernorm_bwd_rows(const void* dy, const void* x, const void* gamma, const float* mean, const float* rstd,
+                                         const void* dres, int64_t dres_period, void* dx, float* dgamma, float* dbeta, int64_t rows, int64_t D,
+                                         int accumulate, float* dx_colsum, int dx_colsum_accumulate, void* workspace, int dtype, void* stream) {
     UCF_CHECK_ARG(dy && x && gamma && mean && rstd && dx && dgamma && dbeta && workspace, "ucfvit_layernorm_bwd: null pointer");
     UCF_CHECK_ARG(rows > 0 && D > 0, "ucfvit_layernorm_bwd: bad shape");
+    UCF_CHECK_ARG(dres_period >= 1 && (dres_period == 1 || rows < (1ll << 31)), "ucfvit_layernorm_bwd_rows: need dres_period >= 1 and rows < 2^31");
     UCF_CHECK_ARG(ucf_is_aligned16(x) && ucf_is_aligned16(dy) && ucf_is_aligned16(dx) && ucf_is_aligned16(gamma) && ucf_is_aligned16(dres),
                   "ucfvit_layernorm_bwd: pointers must be 16-byte aligned");
     if (dtype == UCFVIT_F32)
-        return ln_bwd_t<float>(dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, rows, D, accumulate, dx_colsum, dx_colsum_accumulate, workspace,
-                               (hipStream_t)stream);
+        return ln_bwd_t<float>(dy, x, gamma, mean, rstd, dres, dres_period, dx, dgamma, dbeta, rows, D, accumulate, dx_colsum, dx_colsum_accumulate,
+                               workspace, (hipStream_t)stream);
     if (dtype == UCFVIT_BF16)
-        return ln_bwd_t<bf16>(dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, rows, D, accumulate, dx_colsum, dx_colsum_accumulate, workspace,
-                              (hipStream_t)stream);
+        return ln_bwd_t<bf16>(dy, x, gamma, mean, rstd, dres, dres_period, dx, dgamma, dbeta, rows, D, accumulate, dx_colsum, dx_colsum_accumulate,
+                              workspace, (hipStream_t)stream);
     ucfvit_set_error("ucfvit_layernorm_bwd: bad dtype %d", dtype);
     return UCFVIT_ERR_UNSUPPORTED;
+}
+
+extern "C" int ucfvit_layernorm_bwd(const void* dy, const void* x, const void* gamma, const float* mean, const float* rstd,
+                                    const void* dres, void* dx, float* dgamma, float* dbeta, int64_t rows, int64_t D, int accumulate,
+                                    float* dx_colsum, int dx_colsum_accumulate, void* workspace, int dtype, void* stream) {
+    return ucfvit_layernorm_bwd_rows(dy, x, gamma, mean, rstd, dres, 1, dx, dgamma, dbeta, rows, D, accumulate, dx_colsum, dx_colsum_accumulate,
+                                     workspace, dtype, stream);
 }
 
 extern "C" int64_t ucfvit_colsum_workspace(int64_t M, int64_t N) { return (int64_t)colsum_chunks(M) * N * (int64_t)sizeof(float); }
