@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define UCFVIT_ABI_VERSION 17
+#define UCFVIT_ABI_VERSION 18
 
 #define UCFVIT_OK 0
 #define UCFVIT_ERR_INVALID_ARGUMENT (-1)
@@ -172,6 +172,9 @@ int ucfvit_layernorm_bwd_rows(const void* dy, const void* x, const void* gamma, 
  * out : [B][N][H*dh] dtype     — already in the layout `proj` consumes
  * lse : [B][H][N] fp32, log2-domain log-sum-exp of the scaled scores (saved for backward)
  * bwd : dqkv has qkv's layout; delta_ws is fp32 [B][H][N] scratch.  dh ∈ {32, 64, 128}.
+ * Dispatch: attn_route() in csrc/attn_route.h decides once per call between the kernels that keep a head's whole sequence in LDS
+ * (csrc/attention_short.hip: bf16, dh 32 / 64, N <= 256) and the streaming kernels (csrc/attention.hip: everything else); both families
+ * take their MFMA fragments through csrc/attn_tile.h.  ucfvit_attention_route names the decision.
  * ------------------------------------------------------------------------------------------------------ */
 int ucfvit_attention_fwd(const void* qkv, void* out, float* lse, int64_t B, int64_t N, int64_t H, int64_t dh,
                          float scale, int dtype, void* stream);
@@ -192,6 +195,12 @@ int ucfvit_attention_bwd_colsum_supported(int64_t B, int64_t N, int64_t H, int64
 int ucfvit_attention_bwd_colsum(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv,
                                 float* delta_ws, float* colsum_partial, int64_t B, int64_t N, int64_t H, int64_t dh, float scale,
                                 int dtype, void* stream);
+/* which kernels ucfvit_attention_fwd (backward = 0) or ucfvit_attention_bwd / _bwd_colsum (backward = 1) would run for this shape, as
+ * text: "short-nb4", "short-nb8", "s3-nb13", "short-nb16" (forward) or "fused-nb4" .. "fused-nb16" (backward), NB being the 16-row blocks
+ * the kernel is built for, followed by "-exact" (N fills them: only the last key block is masked) or "-masked"; otherwise "stream-bf16" /
+ * "stream-fp32".  ucfvit_attention_bwd_colsum_supported is 1 exactly for the "fused-" names.  Host only, no HIP call; returns the length
+ * (the text is cut to cap - 1 characters), or < 0 for a shape the attention entry points refuse */
+int ucfvit_attention_route(int64_t B, int64_t N, int64_t H, int64_t dh, int dtype, int backward, char* out, int64_t cap);
 
 /* The same attention for ONE query row per batch element (a model whose head reads only the class token needs nothing else of its
  * last Block's attention output).  qkv as above, all N keys / values are read; the query is token `qrow` of every batch element.

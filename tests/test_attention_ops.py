@@ -41,7 +41,7 @@ test_forward_bound_vs_float64_emulation needs no GPU: a float64 emulation of the
 operand family while the wrong references fall outside.
 
 Measured on an MI355X:
-  141 GPU cases + 1 CPU case, 5.5 s of test time (9 s wall with start-up; tests/test_baseline_configs.py: 15 s / 18 s in the same run).
+  141 GPU cases + 3 CPU cases (two of them the route query, 0.01 s), 5.5 s of test time (9 s wall with start-up; tests/test_baseline_configs.py: 15 s / 18 s in the same run).
   worst err / bound        o      lse    dQ     dK     dV     colsum
   short (bf16)             0.79   0.06   0.80   0.91   0.89   0.69
   streaming bf16           0.44   0.27   0.82   0.90   0.88   -
@@ -114,15 +114,20 @@ def _c32(scale):
     return s32, s32 * LOG2E
 
 
-# ============================================================================================== dispatch (read off the host code)
-# ucfvit_attention_fwd: bf16, dh in {32, 64}, N <= 256 -> attention_short.hip, nb = ceil(N / 16):
-#     nb <= 4  attn_s_fwd_kernel NB 4      EXACT (nb == 4): N 49, 50, 64          masked: N 1, 15, 16, 17
-#     nb <= 8  attn_s_fwd_kernel NB 8      EXACT (nb == 8): N 128                 masked: N 65
-#     nb <= 13 attn_s3_fwd_kernel NB 13    EXACT (nb == 13): N 196, 197, 208      masked: N 129
-#     nb <= 16 attn_s_fwd_kernel NB 16     EXACT (nb == 16): N 255, 256           masked: N 209
-#   ucfvit_attention_bwd / _bwd_colsum, same condition -> attn_g_bwd_kernel NB 4 / 8 / 13 / 16, EXACT / masked exactly as above.
+# ============================================================================================== dispatch
+# attn_route() in csrc/attn_route.h; test_attention_route_query holds the library's own answer, ucfvit_attention_route, to this table.
+# bf16, dh in SHORT_DH, N <= 256 -> attention_short.hip, NB = the first bucket that holds ceil(N / 16) blocks:
+#   forward: the kernel named here (short: attn_s_fwd_kernel, s3: attn_s3_fwd_kernel), ucfvit_attention_bwd / _bwd_colsum: attn_g_bwd_kernel
+#   of the same NB; EXACT where N fills the bucket's last block, else the masked instantiation
+SHORT_DH = (32, 64)
+SHORT_ROUTES = {  # NB: (forward kernel, N that run EXACT, N that run masked)
+    4: ("short", (49, 50, 64), (1, 15, 16, 17)),
+    8: ("short", (128,), (65,)),
+    13: ("s3", (196, 197, 208), (129,)),
+    16: ("short", (255, 256), (209,)),
+}
 #   everything else -> attention.hip streaming kernels attn_fwd_kernel / attn_delta_kernel / attn_bwd_dq_kernel / attn_bwd_dkv_kernel:
-#     bf16 (Geo: QB 2, NBUF 2, 128 queries per workgroup, 64-key tiles): N > 256 at dh 32 / 64, any N at dh 128
+#     bf16 (Geo: QB 2, NBUF 2, 128 queries per workgroup, 64-key tiles): N > 256 at dh 32 / 64, any N at dh 128, B H >= 2^31
 #     fp32 (Geo: QB 1, NBUF 1, 64 queries per workgroup): every N and dh
 SHORT_N = [1, 15, 16, 17, 64, 65, 128, 129, 197, 208, 209, 255, 256]
 
@@ -157,6 +162,70 @@ BIG_CASES = [(BF, 2048, 32), (BF, 2048, 128), (BF, 8192, 64), (BF, 8192, 128)]
 
 def _cid(c):
     return f"{'bf16' if c[0] == BF else 'fp32'}-N{c[1]}-dh{c[2]}"
+
+
+# ============================================================================================== the route query, without a GPU
+def _table_route(dtype, N, dh, backward):
+    """the name SHORT_ROUTES gives (dtype, N, dh); a short-sequence N the table does not list is an error of the table"""
+    if dtype != BF:
+        return "stream-fp32"
+    if dh in SHORT_DH:
+        for nb, (fwd, exact, masked) in SHORT_ROUTES.items():
+            if N in exact or N in masked:
+                return f"{'fused' if backward else fwd}-nb{nb}-{'exact' if N in exact else 'masked'}"
+        assert N > 256, f"N = {N} is missing from SHORT_ROUTES"
+    return "stream-bf16"
+
+
+def _lib_route(dtype, N, dh, backward, B=2, H=3, cap=64):
+    import ctypes
+    from UCF_VIT._hip import lib as L
+    buf = ctypes.create_string_buffer(cap)
+    n = L.load().ucfvit_attention_route(B, N, H, dh, L.BF16 if dtype == BF else L.F32, int(backward), buf, cap)
+    assert 0 < n < cap, f"ucfvit_attention_route returned {n}"
+    assert len(buf.value) == n
+    return buf.value.decode()
+
+
+def test_attention_route_query():
+    """no GPU: for every case of the GPU tests, forward and backward, the library routes as SHORT_ROUTES says, _kind() names the same family,
+    and the column sums exist exactly where the backward is the fused kernel; a grid.x of 2^31 workgroups or more streams"""
+    from UCF_VIT._hip import lib as L
+    lib = L.load()
+    cases = SELF_CASES + BIG_CASES + [(BF, N, dh) for N in _short_ns() for dh in SHORT_DH]
+    family = {"short": "short", "s3": "short", "fused": "short", "stream-bf16": "stream", "stream-fp32": "fp32"}
+    seen = set()
+    for dtype, N, dh in cases:
+        for backward in (False, True):
+            said = _lib_route(dtype, N, dh, backward)
+            assert said == _table_route(dtype, N, dh, backward), f"{_cid((dtype, N, dh))} backward={backward}: ucfvit_attention_route says {said}"
+            head = said if said.startswith("stream") else said.split("-")[0]
+            assert family[head] == _kind(dtype, N, dh)[0], f"{_cid((dtype, N, dh))}: _kind says {_kind(dtype, N, dh)[0]}, the library {said}"
+            seen.add(said)
+        sup = lib.ucfvit_attention_bwd_colsum_supported(2, N, 3, dh, L.BF16 if dtype == BF else L.F32)
+        assert sup == int(_lib_route(dtype, N, dh, True).startswith("fused-")), f"{_cid((dtype, N, dh))}: bwd_colsum_supported = {sup}"
+    for nb, (fwd, _, _) in SHORT_ROUTES.items():          # every instantiation the table names is asked for
+        for tail in ("exact", "masked"):
+            assert f"{fwd}-nb{nb}-{tail}" in seen and f"fused-nb{nb}-{tail}" in seen
+    assert {"stream-bf16", "stream-fp32"} <= seen
+    for backward in (False, True):
+        assert _lib_route(BF, 197, 64, backward, B=65535, H=65535) == "stream-bf16"
+    assert lib.ucfvit_attention_bwd_colsum_supported(65535, 197, 65535, 64, L.BF16) == 0
+
+
+def test_attention_route_query_cuts_the_text_to_the_room_given():
+    """the length returned is the whole name's, the text is cut to cap - 1 characters and terminated; a refused shape is an error"""
+    import ctypes
+    from UCF_VIT._hip import lib as L
+    lib = L.load()
+    name = b"fused-nb13-exact"
+    for cap, want in ((4, b"fus\0x"), (1, b"\0xxxx"), (len(name), name[:-1] + b"\0x"), (len(name) + 1, name + b"\0x")):
+        buf = ctypes.create_string_buffer(b"x" * 32, 32)
+        assert lib.ucfvit_attention_route(2, 197, 3, 64, L.BF16, 1, buf, cap) == len(name)
+        assert buf.raw[:len(want)] == want, (cap, buf.raw)
+    buf = ctypes.create_string_buffer(b"x" * 32, 32)
+    assert lib.ucfvit_attention_route(2, 197, 3, 64, L.BF16, 1, buf, 0) == len(name) and buf.raw == b"x" * 32
+    assert lib.ucfvit_attention_route(2, 197, 3, 48, L.BF16, 0, buf, 32) < 0 and b"head dim" in lib.ucfvit_last_error()
 
 
 # ============================================================================================== float64 references and bounds

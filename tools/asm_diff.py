@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Is the device code of the GEMM translation units the same in two source trees?
+"""Is the device code of the named translation units the same in two source trees?
 
-    python tools/gemm_asm_diff.py OLD_TREE NEW_TREE [--units gemm gemm2 gemm_stagger] [--keep DIR]
+    python tools/asm_diff.py OLD_TREE NEW_TREE --units gemm gemm2 gemm_stagger [--keep DIR]
 
 Compiles ucf-vit_amd/csrc/<unit>.hip of both trees to gfx950 assembly (device side only, the flags of the Makefile) and compares,
 kernel by kernel, the instruction stream and the .amdhsa_* resource directives (VGPR / AGPR / SGPR counts, LDS size, scratch size).
@@ -54,10 +54,10 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("old_tree")
     ap.add_argument("new_tree")
-    ap.add_argument("--units", nargs="+", default=["gemm", "gemm2", "gemm_stagger"])
+    ap.add_argument("--units", nargs="+", required=True, help="names of ucf-vit_amd/csrc/<unit>.hip")
     ap.add_argument("--keep", help="directory that receives the .s files (default: a temporary one)")
     a = ap.parse_args()
-    tmp = a.keep or tempfile.mkdtemp(prefix="gemm_asm_")
+    tmp = a.keep or tempfile.mkdtemp(prefix="asm_diff_")
     os.makedirs(tmp, exist_ok=True)
     jobs = [(t, u, os.path.join(tmp, f"{side}_{u}.s")) for side, t in (("old", a.old_tree), ("new", a.new_tree)) for u in a.units]
     with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 1, 8)) as ex:

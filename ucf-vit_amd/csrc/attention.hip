@@ -16,42 +16,13 @@
 
 #include <type_traits>
 
-#include "common.h"
-
-// attention_short.hip: whole-sequence-in-LDS kernels for N <= 256 (return 1 = handled, 0 = not applicable, <0 = error)
-int ucfvit_attention_short_fwd(const void* qkv, void* out, float* lse, int64_t B, int64_t N, int64_t H, int64_t dh, float scale, int dtype,
-                               hipStream_t s);
-int ucfvit_attention_fused_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* cs_partial, int64_t B, int64_t N,
-                               int64_t H, int64_t dh, float scale, int dtype, hipStream_t s);
-int ucfvit_attention_fused_bwd_applies(int64_t B, int64_t N, int64_t H, int64_t dh, int dtype);
-
+#include "attn_route.h"
+#include "attn_tile.h"
 
 namespace {
 
 constexpr int AT_THREADS = 256;  // 4 waves x 16 lane-columns = 64 queries (or keys) per workgroup
 constexpr int KT = 64;           // rows per LDS tile
-
-template <typename T> struct Mma16;
-template <> struct Mma16<bf16> {
-    typedef bf16x8 frag_t;
-    static __device__ __forceinline__ void mma(f32x4& acc, const frag_t& a, const frag_t& b) {
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
-    }
-    static __device__ __forceinline__ frag_t ones() {
-        frag_t r;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) r[j] = (bf16)1.0f;
-        return r;
-    }
-};
-template <> struct Mma16<float> {
-    typedef f32x4 frag_t;
-    static __device__ __forceinline__ void mma(f32x4& acc, const frag_t& a, const frag_t& b) {
-#pragma unroll
-        for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], b[s], acc, 0, 0, 0);
-    }
-    static __device__ __forceinline__ frag_t ones() { return f32x4{1.f, 1.f, 1.f, 1.f}; }
-};
 
 template <typename T, int DH> struct AT {
     static constexpr int EPV = 16 / sizeof(T);
@@ -65,15 +36,6 @@ template <typename T, int DH> struct AT {
     static constexpr int TILE_BYTES = KT * RB;
     typedef typename Mma16<T>::frag_t frag_t;
 };
-
-template <int SPR> __device__ __forceinline__ int slot_swz(int row) {
-    if (SPR == 4) return (0x1230 >> (((row >> 2) & 3) * 4)) & 3;  // {0,3,2,1}[(row>>2)&3]
-    if (SPR == 8) return row & 7;
-    return row & 15;
-}
-template <typename T, int DH> __device__ __forceinline__ int tile_off(int row, int slot) {
-    return row * AT<T, DH>::RB + ((slot ^ slot_swz<AT<T, DH>::SPR>(row)) << 4);
-}
 
 template <typename T, int DH> struct TileStage {
     u32x4 v[AT<T, DH>::PPT];
@@ -100,61 +62,6 @@ template <typename T, int DH> __device__ __forceinline__ void tile_store(const T
     }
 }
 
-// "row" fragment: 16 B of row (rb*16 + lane&15) at head-dim chunk c: elements d = (4c + g)*EPV .. +EPV
-template <typename T, int DH>
-__device__ __forceinline__ typename AT<T, DH>::frag_t frag_row(const char* lds, int rb, int c, int lane) {
-    const int row = rb * 16 + (lane & 15), g = lane >> 4;
-    return *reinterpret_cast<const typename AT<T, DH>::frag_t*>(lds + tile_off<T, DH>(row, 4 * c + g));
-}
-// "transposed" fragment for a contraction over tile rows: lane (lane&15 = i) gets column d = db*16 + i of the rows
-// of row-chunk rc in ACCUMULATOR order: bf16: rows 32rc + 16*(j>>2) + 4g + (j&3), j=0..7 ; fp32: rows 16rc + 4g + s.
-template <typename T, int DH>
-__device__ __forceinline__ typename AT<T, DH>::frag_t frag_tr(const char* lds, int rc, int db, int lane) {
-    typedef typename AT<T, DH>::frag_t frag_t;
-    const int g = lane >> 4, i = lane & 15;
-    if constexpr (sizeof(T) == 2) {
-        const int q = i >> 2, p = i & 3;
-        const int slot = 2 * db + (p >> 1), sub = (p & 1) * 8;
-        const int r_lo = 32 * rc + 4 * g + q, r_hi = r_lo + 16;
-        const char* a_lo = lds + tile_off<T, DH>(r_lo, slot) + sub;
-        const char* a_hi = lds + tile_off<T, DH>(r_hi, slot) + sub;
-        short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(short4v, a_lo));
-        short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(short4v, a_hi));
-        short8v r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        return __builtin_bit_cast(frag_t, r);
-    } else {
-        const int slot = 4 * db + (i >> 2), sub = (i & 3) * 4;
-        f32x4 r;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) r[s] = *reinterpret_cast<const float*>(lds + tile_off<T, DH>(16 * rc + 4 * g + s, slot) + sub);
-        return __builtin_bit_cast(frag_t, r);
-    }
-}
-// accumulator blocks -> operand fragment for row-chunk rc (bf16: two 16-row blocks packed; fp32: one block as is)
-template <typename T> __device__ __forceinline__ typename Mma16<T>::frag_t frag_from_acc(const f32x4* acc, int rc) {
-    typedef typename Mma16<T>::frag_t frag_t;
-    if constexpr (sizeof(T) == 2) {
-        bf16x8 r;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            r[j] = (bf16)acc[2 * rc][j];
-            r[4 + j] = (bf16)acc[2 * rc + 1][j];
-        }
-        return __builtin_bit_cast(frag_t, r);
-    } else {
-        return __builtin_bit_cast(frag_t, acc[rc]);
-    }
-}
-// 16 B of a global row as an operand fragment (zero beyond R)
-template <typename T, int DH>
-__device__ __forceinline__ typename AT<T, DH>::frag_t frag_global(const T* __restrict__ base, int64_t row_stride, int row, int R, int c, int lane) {
-    typedef typename AT<T, DH>::frag_t frag_t;
-    const int g = lane >> 4;
-    u32x4 z = {0u, 0u, 0u, 0u};
-    u32x4 v = (row < R) ? *reinterpret_cast<const u32x4*>(base + (int64_t)row * row_stride + (4 * c + g) * AT<T, DH>::EPV) : z;
-    return __builtin_bit_cast(frag_t, v);
-}
-
 // max(a, b, c) as ONE instruction: hipcc puts a canonicalising v_max_f32 x, x, x in front of every fmaxf of an MFMA result
 // (32 extra VALU instructions per key tile of the forward kernel, which is bound by its VALU work)
 __device__ __forceinline__ float max3f(float a, float b, float c) {
@@ -162,15 +69,6 @@ __device__ __forceinline__ float max3f(float a, float b, float c) {
     asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
     return r;
 }
-__device__ __forceinline__ float group_max(float v) {  // over the 4 lane groups that share lane&15
-    v = fmaxf(v, __shfl_xor(v, 16, 64));
-    return fmaxf(v, __shfl_xor(v, 32, 64));
-}
-__device__ __forceinline__ float group_sum(float v) {
-    v += __shfl_xor(v, 16, 64);
-    return v + __shfl_xor(v, 32, 64);
-}
-
 // Operands of the streaming kernels: every matrix is [batch][token][head][DH] with its own token / batch stride (in elements), so the same
 // kernels serve self-attention on the packed qkv GEMM output (q = qkv, k = qkv + D, v = qkv + 2D, token stride 3D) and attention of a
 // query block against ANOTHER token block's keys / values (ring sequence parallelism: UCF_VIT/fsdp/seq_parallel.py): Nq queries, Nk keys.
@@ -703,23 +601,13 @@ template <typename T, int DH> struct Geo {
     static constexpr size_t SMEM_DKV = SMEM + (size_t)NBUF * 2 * KT * sizeof(float);
 };
 
-template <typename K> int allow_big_lds(K kernel, size_t bytes) {
-    if (bytes <= 64 * 1024) return UCFVIT_OK;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) {
-        ucfvit_set_error("attention: cannot raise dynamic LDS to %zu bytes: %s", bytes, hipGetErrorString(e));
-        return UCFVIT_ERR_HIP;
-    }
-    return UCFVIT_OK;
-}
-
 template <typename T, int DH>
 int attn_fwd_launch_args(const AttnArgs<T>& a, int64_t B, float scale, hipStream_t s) {
     typedef Geo<T, DH> G;
     const dim3 grid((unsigned)((a.Nq + 64 * G::QB - 1) / (64 * G::QB)), (unsigned)a.H, (unsigned)B);
     auto kern = attn_fwd_kernel<T, DH, G::QB, G::NBUF>;
-    if (int rc = allow_big_lds(kern, G::SMEM)) return rc;
-    hipLaunchKernelGGL(kern, grid, dim3(AT_THREADS), G::SMEM, s, a, scale * 1.44269504088896340736f);
+    if (int rc = raise_lds_limit(kern, G::SMEM, "attention")) return rc;
+    hipLaunchKernelGGL(kern, grid, dim3(AT_THREADS), G::SMEM, s, a, scale * LOG2E_F);
     UCF_LAUNCH_CHECK("ucfvit_attention_fwd");
     return UCFVIT_OK;
 }
@@ -733,11 +621,11 @@ int attn_bwd_launch_args(AttnArgs<T> a, const void* out, float* delta, int64_t B
                        a.H);
     UCF_LAUNCH_CHECK("ucfvit_attention_bwd(delta)");
     a.delta = delta;
-    const float sl2 = scale * 1.44269504088896340736f;
+    const float sl2 = scale * LOG2E_F;
     auto k_dq = attn_bwd_dq_kernel<T, DH, G::QB, G::NBUF, OUTF>;
     auto k_dkv = attn_bwd_dkv_kernel<T, DH, G::QB, G::NBUF, OUTF>;
-    if (int rc = allow_big_lds(k_dq, G::SMEM)) return rc;
-    if (int rc = allow_big_lds(k_dkv, G::SMEM_DKV)) return rc;
+    if (int rc = raise_lds_limit(k_dq, G::SMEM, "attention")) return rc;
+    if (int rc = raise_lds_limit(k_dkv, G::SMEM_DKV, "attention")) return rc;
     const dim3 grid_q((unsigned)((a.Nq + 64 * G::QB - 1) / (64 * G::QB)), (unsigned)a.H, (unsigned)B);
     const dim3 grid_k((unsigned)((a.Nk + 64 * G::QB - 1) / (64 * G::QB)), (unsigned)a.H, (unsigned)B);
     hipLaunchKernelGGL(k_dq, grid_q, dim3(AT_THREADS), G::SMEM, s, a, scale, sl2);
@@ -772,20 +660,10 @@ int attn_fwd_launch(const void* qkv, void* out, float* lse, int64_t B, int64_t N
     return attn_fwd_launch_args<T, DH>(a, B, scale, s);
 }
 
+// the streaming backward of self-attention (the route decided that the fused kernel does not apply)
 template <typename T, int DH>
-int attn_bwd_launch(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* delta, float* cs_partial, int64_t B,
-                    int64_t N, int64_t H, float scale, hipStream_t s) {
-    // the FUSED backward (one launch, operands read once, delta = rowsum(dO o O) taken inside) is the default where it applies
-    {
-        const int rc = ucfvit_attention_fused_bwd(qkv, out, dout, lse, dqkv, cs_partial, B, N, H, DH, scale, sizeof(T) == 2 ? UCFVIT_BF16 : UCFVIT_F32, s);
-        if (rc == 1) return UCFVIT_OK;
-        if (rc < 0) return rc;
-    }
-    if (cs_partial) {
-        ucfvit_set_error("ucfvit_attention_bwd_colsum: this shape runs the streaming kernels, which produce no column sums (ask "
-                         "ucfvit_attention_bwd_colsum_supported first)");
-        return UCFVIT_ERR_UNSUPPORTED;
-    }
+int attn_bwd_launch(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* delta, int64_t B, int64_t N, int64_t H,
+                    float scale, hipStream_t s) {
     AttnArgs<T> a = self_args<T>(qkv, N, H, DH);
     const int64_t D = H * DH;
     a.dout = (const T*)dout;
@@ -799,16 +677,16 @@ int attn_bwd_launch(const void* qkv, const void* out, const void* dout, const fl
 }
 
 // ---- attention of a query block against another block's keys / values (ring sequence parallelism) ------------------------------------
-template <typename T, int DH>
-int attn_cross_fwd_launch(const void* q, const void* k, const void* v, void* out, float* lse, int64_t B, int64_t Nq, int64_t Nk, int64_t H,
-                          int64_t ldq, int64_t ldkv, float scale, hipStream_t s) {
+// what the forward and the backward of a (query block, key block) pair share; out / dO / the fp32 gradients are contiguous [B][N][H][DH]
+template <typename T>
+AttnArgs<T> cross_args(const void* q, const void* k, const void* v, const float* lse, int64_t Nq, int64_t Nk, int64_t H, int64_t DH, int64_t ldq,
+                       int64_t ldkv) {
     AttnArgs<T> a;
     memset(&a, 0, sizeof(a));
     a.q = (const T*)q;
     a.k = (const T*)k;
     a.v = (const T*)v;
-    a.out = (T*)out;
-    a.lse = lse;
+    a.lse = const_cast<float*>(lse);
     a.sq = ldq;
     a.skv = ldkv;
     a.bq = Nq * ldq;
@@ -818,6 +696,14 @@ int attn_cross_fwd_launch(const void* q, const void* k, const void* v, void* out
     a.Nq = (int)Nq;
     a.Nk = (int)Nk;
     a.H = (int)H;
+    return a;
+}
+
+template <typename T, int DH>
+int attn_cross_fwd_launch(const void* q, const void* k, const void* v, void* out, float* lse, int64_t B, int64_t Nq, int64_t Nk, int64_t H,
+                          int64_t ldq, int64_t ldkv, float scale, hipStream_t s) {
+    AttnArgs<T> a = cross_args<T>(q, k, v, lse, Nq, Nk, H, DH, ldq, ldkv);
+    a.out = (T*)out;
     return attn_fwd_launch_args<T, DH>(a, B, scale, s);
 }
 
@@ -825,27 +711,14 @@ template <typename T, int DH>
 int attn_cross_bwd_launch(const void* q, const void* k, const void* v, const void* out, const void* dout, const float* lse, float* dq, float* dk,
                           float* dv, float* delta, int64_t B, int64_t Nq, int64_t Nk, int64_t H, int64_t ldq, int64_t ldkv, float scale,
                           int accumulate, hipStream_t s) {
-    AttnArgs<T> a;
-    memset(&a, 0, sizeof(a));
-    const int64_t D = H * DH;
-    a.q = (const T*)q;
-    a.k = (const T*)k;
-    a.v = (const T*)v;
+    AttnArgs<T> a = cross_args<T>(q, k, v, lse, Nq, Nk, H, DH, ldq, ldkv);
     a.dout = (const T*)dout;
-    a.lse = const_cast<float*>(lse);
     a.dq = dq;
     a.dk = dk;
     a.dv = dv;
-    a.sq = ldq;
-    a.skv = ldkv;
-    a.bq = Nq * ldq;
-    a.bkv = Nk * ldkv;
-    a.so = a.sdo = a.sdq = a.sdkv = D;
-    a.bo = a.bdo = a.bdq = Nq * D;
-    a.bdkv = Nk * D;
-    a.Nq = (int)Nq;
-    a.Nk = (int)Nk;
-    a.H = (int)H;
+    a.sdo = a.sdq = a.sdkv = a.so;
+    a.bdo = a.bdq = a.bo;
+    a.bdkv = Nk * a.so;
     a.accumulate = accumulate;
     return attn_bwd_launch_args<T, DH, true>(a, out, delta, B, scale, s);
 }
@@ -927,38 +800,59 @@ extern "C" int ucfvit_attention_fwd(const void* qkv, void* out, float* lse, int6
     int rc = check_attn_args("ucfvit_attention_fwd", B, N, H, dh, dtype);
     if (rc) return rc;
     UCF_CHECK_ARG(ucf_is_aligned16(qkv) && ucf_is_aligned16(out), "ucfvit_attention_fwd: pointers must be 16-byte aligned");
-    {
-        rc = ucfvit_attention_short_fwd(qkv, out, lse, B, N, H, dh, scale, dtype, (hipStream_t)stream);
-        if (rc == 1) return UCFVIT_OK;
-        if (rc < 0) return rc;
+    const AttnRoute r = attn_route(ATTN_FWD, B, N, H, dh, dtype);
+    switch (r.family) {
+        case AK_SHORT_FWD:
+        case AK_S3_FWD: return ucfvit_attn_launch_short_fwd(r, qkv, out, lse, B, N, H, dh, scale, stream);
+        default: break;
     }
     ATTN_DISPATCH(attn_fwd_launch, qkv, out, lse, B, N, H, scale, (hipStream_t)stream);
+}
+
+// ucfvit_attention_bwd (cs_partial null) and ucfvit_attention_bwd_colsum: the fused backward (one launch, operands read once, delta =
+// rowsum(dO o O) taken inside) where the route says so, else the streaming kernels, which have no column sums to give
+static int attn_self_bwd(const char* name, const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* delta_ws,
+                         float* cs_partial, int64_t B, int64_t N, int64_t H, int64_t dh, float scale, int dtype, void* stream) {
+    int rc = check_attn_args(name, B, N, H, dh, dtype);
+    if (rc) return rc;
+    UCF_CHECK_ARG(ucf_is_aligned16(qkv) && ucf_is_aligned16(out) && ucf_is_aligned16(dout) && ucf_is_aligned16(dqkv),
+                  "%s: pointers must be 16-byte aligned", name);
+    const AttnRoute r = attn_route(ATTN_BWD, B, N, H, dh, dtype);
+    switch (r.family) {
+        case AK_FUSED_BWD: return ucfvit_attn_launch_fused_bwd(r, qkv, out, dout, lse, dqkv, cs_partial, B, N, H, dh, scale, stream);
+        default: break;
+    }
+    if (cs_partial) {
+        ucfvit_set_error("ucfvit_attention_bwd_colsum: this shape runs the streaming kernels, which produce no column sums (ask "
+                         "ucfvit_attention_bwd_colsum_supported first)");
+        return UCFVIT_ERR_UNSUPPORTED;
+    }
+    ATTN_DISPATCH(attn_bwd_launch, qkv, out, dout, lse, dqkv, delta_ws, B, N, H, scale, (hipStream_t)stream);
 }
 
 extern "C" int ucfvit_attention_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* delta_ws,
                                     int64_t B, int64_t N, int64_t H, int64_t dh, float scale, int dtype, void* stream) {
     if (B == 0) return UCFVIT_OK;                      // empty batch (pointers may be NULL)
     UCF_CHECK_ARG(qkv && out && dout && lse && dqkv && delta_ws, "ucfvit_attention_bwd: null pointer");
-    int rc = check_attn_args("ucfvit_attention_bwd", B, N, H, dh, dtype);
-    if (rc) return rc;
-    UCF_CHECK_ARG(ucf_is_aligned16(qkv) && ucf_is_aligned16(out) && ucf_is_aligned16(dout) && ucf_is_aligned16(dqkv),
-                  "ucfvit_attention_bwd: pointers must be 16-byte aligned");
-    ATTN_DISPATCH(attn_bwd_launch, qkv, out, dout, lse, dqkv, delta_ws, (float*)nullptr, B, N, H, scale, (hipStream_t)stream);
+    return attn_self_bwd("ucfvit_attention_bwd", qkv, out, dout, lse, dqkv, delta_ws, nullptr, B, N, H, dh, scale, dtype, stream);
 }
 
 extern "C" int ucfvit_attention_bwd_colsum_supported(int64_t B, int64_t N, int64_t H, int64_t dh, int dtype) {
-    return ucfvit_attention_fused_bwd_applies(B, N, H, dh, dtype);
+    return attn_route(ATTN_BWD, B, N, H, dh, dtype).colsum ? 1 : 0;
 }
 
 extern "C" int ucfvit_attention_bwd_colsum(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* delta_ws,
                                            float* colsum_partial, int64_t B, int64_t N, int64_t H, int64_t dh, float scale, int dtype, void* stream) {
     if (B == 0) return UCFVIT_OK;                      // empty batch (pointers may be NULL)
     UCF_CHECK_ARG(qkv && out && dout && lse && dqkv && delta_ws && colsum_partial, "ucfvit_attention_bwd_colsum: null pointer");
-    int rc = check_attn_args("ucfvit_attention_bwd_colsum", B, N, H, dh, dtype);
+    return attn_self_bwd("ucfvit_attention_bwd_colsum", qkv, out, dout, lse, dqkv, delta_ws, colsum_partial, B, N, H, dh, scale, dtype, stream);
+}
+
+extern "C" int ucfvit_attention_route(int64_t B, int64_t N, int64_t H, int64_t dh, int dtype, int backward, char* out, int64_t cap) {
+    UCF_CHECK_ARG(out || cap <= 0, "ucfvit_attention_route: null buffer");
+    int rc = check_attn_args("ucfvit_attention_route", B, N, H, dh, dtype);
     if (rc) return rc;
-    UCF_CHECK_ARG(ucf_is_aligned16(qkv) && ucf_is_aligned16(out) && ucf_is_aligned16(dout) && ucf_is_aligned16(dqkv),
-                  "ucfvit_attention_bwd_colsum: pointers must be 16-byte aligned");
-    ATTN_DISPATCH(attn_bwd_launch, qkv, out, dout, lse, dqkv, delta_ws, colsum_partial, B, N, H, scale, (hipStream_t)stream);
+    return attn_route_name(attn_route(backward ? ATTN_BWD : ATTN_FWD, B, N, H, dh, dtype), out, cap);
 }
 
 extern "C" int ucfvit_attention_cross_fwd(const void* q, const void* k, const void* v, void* out, float* lse, int64_t B, int64_t Nq, int64_t Nk,

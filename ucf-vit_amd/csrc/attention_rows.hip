@@ -5,7 +5,7 @@
 // One workgroup of 4 waves per (batch element, head).  A key / value row of the head (DH elements) is covered by LPR = DH / EPV
 // neighbouring lanes with one 16-byte vector each, so a wave reads whole contiguous head rows and 256 / LPR rows are in flight per
 // step.  Everything that touches qkv / dqkv goes through a buffer descriptor over exactly the batch element's N rows.
-#include "common.h"
+#include "attn_tile.h"
 
 namespace {
 
@@ -13,9 +13,6 @@ constexpr int AR_THREADS = 256;
 constexpr int AR_U = 4;          // key rows a thread requests before it consumes the first
 constexpr int AR_MAX_N = 8192;   // scores of one head live in LDS
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t ar_rsrc(const void* base, int bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);
-}
 template <typename T> __device__ __forceinline__ Vec16<T> ar_load(__amdgpu_buffer_rsrc_t r, int byte_off) {
     Vec16<T> v;
     v.v = __builtin_bit_cast(decltype(v.v), __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 0));
@@ -56,7 +53,7 @@ __global__ __launch_bounds__(AR_THREADS) void attn_rows_fwd_kernel(const T* __re
     const int h = blockIdx.x % H;
     const int64_t b = blockIdx.x / H;
     const int D = H * DH, rs_bytes = 3 * D * ES;
-    const __amdgpu_buffer_rsrc_t rQ = ar_rsrc(qkv + b * N * 3 * (int64_t)D, N * rs_bytes);
+    const __amdgpu_buffer_rsrc_t rQ = buffer_rsrc(qkv + b * N * 3 * (int64_t)D, N * rs_bytes);
     const int colb = (h * DH + c * EPV) * ES;
     const Vec16<T> qv = ar_load<T>(rQ, qrow * rs_bytes + colb);
     // scores s_j = q . K_j (unscaled)
@@ -141,8 +138,8 @@ __global__ __launch_bounds__(AR_THREADS) void attn_rows_bwd_kernel(const T* __re
     const int h = blockIdx.x % H;
     const int64_t b = blockIdx.x / H;
     const int D = H * DH, rs_bytes = 3 * D * ES;
-    const __amdgpu_buffer_rsrc_t rQ = ar_rsrc(qkv + b * N * 3 * (int64_t)D, N * rs_bytes);
-    const __amdgpu_buffer_rsrc_t rDQ = ar_rsrc(dqkv + b * N * 3 * (int64_t)D, N * rs_bytes);
+    const __amdgpu_buffer_rsrc_t rQ = buffer_rsrc(qkv + b * N * 3 * (int64_t)D, N * rs_bytes);
+    const __amdgpu_buffer_rsrc_t rDQ = buffer_rsrc(dqkv + b * N * 3 * (int64_t)D, N * rs_bytes);
     const int colb = (h * DH + c * EPV) * ES;
     const Vec16<T> qv = ar_load<T>(rQ, qrow * rs_bytes + colb);
     const Vec16<T> dov = *reinterpret_cast<const Vec16<T>*>(dout + b * D + h * DH + c * EPV);
@@ -247,7 +244,7 @@ int ar_fwd_launch(const void* qkv, void* out, float* lse, int64_t B, int64_t N, 
     constexpr int EPV = Vec16<T>::N;
     const size_t smem = (size_t)(((N + 3) & ~(int64_t)3) + AR_THREADS * EPV) * sizeof(float);
     hipLaunchKernelGGL((attn_rows_fwd_kernel<T, DH>), dim3((unsigned)(B * H)), dim3(AR_THREADS), smem, s, (const T*)qkv, (T*)out, lse, (int)N, (int)H,
-                       (int)qrow, scale * 1.44269504088896340736f);
+                       (int)qrow, scale * LOG2E_F);
     UCF_LAUNCH_CHECK("ucfvit_attention_rows_fwd");
     return UCFVIT_OK;
 }
@@ -258,7 +255,7 @@ int ar_bwd_launch(const void* qkv, const void* out, const void* dout, const floa
     constexpr int EPV = Vec16<T>::N;
     const size_t smem = (size_t)AR_THREADS * EPV * sizeof(float);
     hipLaunchKernelGGL((attn_rows_bwd_kernel<T, DH>), dim3((unsigned)(B * H)), dim3(AR_THREADS), smem, s, (const T*)qkv, (const T*)out, (const T*)dout, lse,
-                       (T*)dqkv, cs_partial, (int)N, (int)H, (int)qrow, scale, scale * 1.44269504088896340736f);
+                       (T*)dqkv, cs_partial, (int)N, (int)H, (int)qrow, scale, scale * LOG2E_F);
     UCF_LAUNCH_CHECK("ucfvit_attention_rows_bwd");
     return UCFVIT_OK;
 }

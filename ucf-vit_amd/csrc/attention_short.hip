@@ -7,26 +7,12 @@
 // streaming kernel.  Same "softmax index on the lane" layout as attention.hip: Sᵀ[key][q] = K·Qᵀ, accumulators feed the
 // next MFMA as operands, Vᵀ / Kᵀ / Qᵀ / dOᵀ come out of the row-major LDS images through ds_read_b64_tr_b16.
 // NB = number of 16-row blocks (compile time); rows >= N are zero-filled and masked.
-#include "common.h"
+#include "attn_route.h"
+#include "attn_tile.h"
 
 namespace {
 
 constexpr int AS_THREADS = 256;
-
-template <typename T> struct MmaS;
-template <> struct MmaS<bf16> {
-    typedef bf16x8 frag_t;
-    static __device__ __forceinline__ void mma(f32x4& acc, const frag_t& a, const frag_t& b) {
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
-    }
-};
-template <> struct MmaS<float> {
-    typedef f32x4 frag_t;
-    static __device__ __forceinline__ void mma(f32x4& acc, const frag_t& a, const frag_t& b) {
-#pragma unroll
-        for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], b[s], acc, 0, 0, 0);
-    }
-};
 
 template <typename T, int DH, int NB> struct AS {
     static constexpr int EPV = 16 / sizeof(T);
@@ -38,18 +24,8 @@ template <typename T, int DH, int NB> struct AS {
     static constexpr int NRC = (NB + BPC - 1) / BPC;  // row chunks (contraction over keys / queries)
     static constexpr int ROWS = NRC * BPC * 16;     // rows held in an LDS image (padded to whole chunks)
     static constexpr int IMG = ROWS * RB;
-    typedef typename MmaS<T>::frag_t frag_t;
+    typedef typename Mma16<T>::frag_t frag_t;
 };
-
-template <int SPR> __device__ __forceinline__ int swz_s(int row) {
-    if (SPR == 4) return (0x1230 >> (((row >> 2) & 3) * 4)) & 3;
-    if (SPR == 8) return row & 7;
-    return row & 15;
-}
-template <typename T, int DH> __device__ __forceinline__ int img_off(int row, int slot) {
-    constexpr int RB = DH * sizeof(T), SPR = RB / 16;
-    return row * RB + ((slot ^ swz_s<SPR>(row)) << 4);
-}
 
 // global rows [0, R) of a [.., row_stride] matrix -> LDS image of ROWS rows (rows >= R zero)
 template <typename T, int DH, int ROWS>
@@ -68,67 +44,8 @@ __device__ __forceinline__ void load_image(char* lds, const T* __restrict__ base
 #pragma unroll
     for (int i = 0; i < NIT; ++i) {
         const int p = tid + i * AS_THREADS;
-        if (p < ROWS * SPR) *reinterpret_cast<u32x4*>(lds + img_off<T, DH>(p / SPR, p % SPR)) = v[i];
+        if (p < ROWS * SPR) *reinterpret_cast<u32x4*>(lds + tile_off<T, DH>(p / SPR, p % SPR)) = v[i];
     }
-}
-
-template <typename T, int DH>
-__device__ __forceinline__ typename MmaS<T>::frag_t s_frag_row(const char* lds, int rb, int c, int lane) {
-    const int row = rb * 16 + (lane & 15), g = lane >> 4;
-    return *reinterpret_cast<const typename MmaS<T>::frag_t*>(lds + img_off<T, DH>(row, 4 * c + g));
-}
-template <typename T, int DH>
-__device__ __forceinline__ typename MmaS<T>::frag_t s_frag_tr(const char* lds, int rc, int db, int lane) {
-    typedef typename MmaS<T>::frag_t frag_t;
-    const int g = lane >> 4, i = lane & 15;
-    if constexpr (sizeof(T) == 2) {
-        const int q = i >> 2, p = i & 3;
-        const int slot = 2 * db + (p >> 1), sub = (p & 1) * 8;
-        const int r_lo = 32 * rc + 4 * g + q;
-        const char* a_lo = lds + img_off<T, DH>(r_lo, slot) + sub;
-        const char* a_hi = lds + img_off<T, DH>(r_lo + 16, slot) + sub;
-        short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(short4v, a_lo));
-        short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(short4v, a_hi));
-        short8v r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        return __builtin_bit_cast(frag_t, r);
-    } else {
-        const int slot = 4 * db + (i >> 2), sub = (i & 3) * 4;
-        f32x4 r;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) r[s] = *reinterpret_cast<const float*>(lds + img_off<T, DH>(16 * rc + 4 * g + s, slot) + sub);
-        return __builtin_bit_cast(frag_t, r);
-    }
-}
-// accumulator blocks -> operand fragment of row chunk rc; blocks >= nb contribute zeros
-template <typename T, int NBLK> __device__ __forceinline__ typename MmaS<T>::frag_t s_frag_acc(const f32x4 (&acc)[NBLK], int rc) {
-    typedef typename MmaS<T>::frag_t frag_t;
-    if constexpr (sizeof(T) == 2) {
-        bf16x8 r;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            r[j] = (bf16)acc[2 * rc][j];
-            r[4 + j] = (2 * rc + 1 < NBLK) ? (bf16)acc[(2 * rc + 1 < NBLK) ? 2 * rc + 1 : 0][j] : (bf16)0.f;
-        }
-        return __builtin_bit_cast(frag_t, r);
-    } else {
-        return __builtin_bit_cast(frag_t, acc[rc]);
-    }
-}
-template <typename T, int DH>
-__device__ __forceinline__ typename MmaS<T>::frag_t s_frag_global(const T* __restrict__ base, int64_t row_stride, int row, int R, int c, int lane) {
-    typedef typename MmaS<T>::frag_t frag_t;
-    const int g = lane >> 4;
-    u32x4 v = {0u, 0u, 0u, 0u};
-    if (row < R) v = *reinterpret_cast<const u32x4*>(base + (int64_t)row * row_stride + (4 * c + g) * (16 / (int)sizeof(T)));
-    return __builtin_bit_cast(frag_t, v);
-}
-__device__ __forceinline__ float gmax(float v) {
-    v = fmaxf(v, __shfl_xor(v, 16, 64));
-    return fmaxf(v, __shfl_xor(v, 32, 64));
-}
-__device__ __forceinline__ float gsum(float v) {
-    v += __shfl_xor(v, 16, 64);
-    return v + __shfl_xor(v, 32, 64);
 }
 
 // =====================================================================================================================
@@ -156,14 +73,14 @@ __global__ __launch_bounds__(AS_THREADS) void attn_s_fwd_kernel(const T* __restr
         const int q = qb * 16 + li;
         frag_t qf[A::NCH];
 #pragma unroll
-        for (int c = 0; c < A::NCH; ++c) qf[c] = s_frag_global<T, DH>(qbase, rs, q, N, c, lane);
+        for (int c = 0; c < A::NCH; ++c) qf[c] = frag_global<T, DH>(qbase, rs, q, N, c, lane);
         f32x4 s[NB];
         float mx = -INFINITY;
 #pragma unroll
         for (int kb = 0; kb < NB; ++kb) {
             s[kb] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int c = 0; c < A::NCH; ++c) MmaS<T>::mma(s[kb], s_frag_row<T, DH>(ldsK, kb, c, lane), qf[c]);
+            for (int c = 0; c < A::NCH; ++c) Mma16<T>::mma(s[kb], frag_row<T, DH>(ldsK, kb, c, lane), qf[c]);
             if (EXACT ? (kb == NB - 1) : (kb * 16 + 16 > N)) {   // only the ragged / padding key blocks pay for masking
 #pragma unroll
                 for (int r = 0; r < 4; ++r) s[kb][r] = (kb * 16 + 4 * g + r < N) ? s[kb][r] : -INFINITY;
@@ -172,7 +89,7 @@ __global__ __launch_bounds__(AS_THREADS) void attn_s_fwd_kernel(const T* __restr
             for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[kb][r]);
         }
         // softmax in the log2 domain with the scale folded into one fma per score: p = 2^(s*c - max*c)   (c > 0)
-        const float m = gmax(mx) * scale_log2e;
+        const float m = group_max(mx) * scale_log2e;
         float l = 0.f;
 #pragma unroll
         for (int kb = 0; kb < NB; ++kb)
@@ -182,15 +99,15 @@ __global__ __launch_bounds__(AS_THREADS) void attn_s_fwd_kernel(const T* __restr
                 s[kb][r] = p;
                 l += p;
             }
-        const float lt = gsum(l);
+        const float lt = group_sum(l);
         f32x4 o[A::NDB];
 #pragma unroll
         for (int d = 0; d < A::NDB; ++d) o[d] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int rc = 0; rc < A::NRC; ++rc) {
-            const frag_t pf = s_frag_acc<T, NB>(s, rc);
+            const frag_t pf = frag_from_acc<T, NB>(s, rc);
 #pragma unroll
-            for (int d = 0; d < A::NDB; ++d) MmaS<T>::mma(o[d], s_frag_tr<T, DH>(ldsV, rc, d, lane), pf);
+            for (int d = 0; d < A::NDB; ++d) Mma16<T>::mma(o[d], frag_tr<T, DH>(ldsV, rc, d, lane), pf);
         }
         if (q < N) {
             const float inv = 1.f / lt;
@@ -207,31 +124,6 @@ __global__ __launch_bounds__(AS_THREADS) void attn_s_fwd_kernel(const T* __restr
     }
 }
 
-template <typename K> int big_lds(K kernel, size_t bytes) {
-    if (bytes <= 64 * 1024) return UCFVIT_OK;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) {
-        ucfvit_set_error("attention(short): cannot raise dynamic LDS to %zu bytes: %s", bytes, hipGetErrorString(e));
-        return UCFVIT_ERR_HIP;
-    }
-    return UCFVIT_OK;
-}
-
-template <typename T, int DH, int NB>
-int launch_fwd(const void* qkv, void* out, float* lse, int64_t B, int64_t N, int64_t H, float scale, hipStream_t s) {
-    constexpr size_t smem = 2 * AS<T, DH, NB>::IMG;
-    const float sl2 = scale * 1.44269504088896340736f;
-    const dim3 grid((unsigned)(B * H)), block(AS_THREADS);
-    if ((N + 15) / 16 == NB) {
-        if (int rc = big_lds(attn_s_fwd_kernel<T, DH, NB, true>, smem)) return rc;
-        hipLaunchKernelGGL((attn_s_fwd_kernel<T, DH, NB, true>), grid, block, smem, s, (const T*)qkv, (T*)out, lse, (int)N, (int)H, sl2);
-    } else {
-        if (int rc = big_lds(attn_s_fwd_kernel<T, DH, NB, false>, smem)) return rc;
-        hipLaunchKernelGGL((attn_s_fwd_kernel<T, DH, NB, false>), grid, block, smem, s, (const T*)qkv, (T*)out, lse, (int)N, (int)H, sl2);
-    }
-    UCF_LAUNCH_CHECK("ucfvit_attention_fwd(short)");
-    return UCFVIT_OK;
-}
 // =====================================================================================================================
 // backward, fused (bf16, head dim 64 / 32, N <= 256): ONE launch per attention layer instead of delta + dQ + dK/dV.
 // Phase A: each wave takes query blocks and produces dQ with K and V resident in LDS; phase B: each wave takes key blocks and
@@ -259,17 +151,17 @@ template <int RB> __device__ __forceinline__ bf16x8 af_tr(const char* img, int b
     return __builtin_bit_cast(bf16x8, r);
 }
 // per-lane address bases of the row images (head dim 64: 128-byte rows, 8 slots, swizzle row & 7; head dim 32: 64-byte rows, 4 slots,
-// swizzle by row group, see swz_s): the fragment of k-chunk c of row block blk is at rowb[c] + blk * 16 RB, the transposed fragment of
+// swizzle by row group, see slot_swz): the fragment of k-chunk c of row block blk is at rowb[c] + blk * 16 RB, the transposed fragment of
 // head-dim block d of row chunk rc at (trb ^ 32 d) + rc * 32 RB
 template <int DH> struct AfBases {
     int rowb[DH / 32], trb;
     __device__ __forceinline__ AfBases(int lane) {
         constexpr int RB = DH * 2, SPR = RB / 16;
         const int g = lane >> 4, li = lane & 15, tq = li >> 2, tp = li & 3;
-        const int sw_row = swz_s<SPR>(li);                 // blocks start at multiples of 16 rows: the swizzle sees li only
+        const int sw_row = slot_swz<SPR>(li);                 // blocks start at multiples of 16 rows: the swizzle sees li only
 #pragma unroll
         for (int c = 0; c < DH / 32; ++c) rowb[c] = li * RB + (((4 * c + g) ^ sw_row) << 4);
-        const int sw_tr = swz_s<SPR>(4 * g + tq);          // chunks start at multiples of 32 rows
+        const int sw_tr = slot_swz<SPR>(4 * g + tq);          // chunks start at multiples of 32 rows
         trb = (4 * g + tq) * RB + ((((tp >> 1) ^ sw_tr)) << 4) + (tp & 1) * 8;
     }
 };
@@ -301,9 +193,6 @@ __device__ __forceinline__ void ag_fetch(AgStage<ROWS, DH>& st, const bf16* __re
 // All global accesses of the fused backward are RAW BUFFER loads / stores whose resource covers rows [0, N) of one (batch, head): rows >= N
 // are out of range for the hardware (loads return 0, stores are dropped), so there is no branch around any of them and hipcc's
 // s_waitcnt bookkeeping stays exact — a load requested a pass ahead is waited for with vmcnt(number of younger stores), not vmcnt(0).
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t ag_rsrc(const void* base, int bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);
-}
 template <int ROWS, int DH>
 __device__ __forceinline__ void ag_fetch(AgStage<ROWS, DH>& st, __amdgpu_buffer_rsrc_t r, int byte0, int row_bytes, int tid) {
     constexpr int SPR = DH / 8;
@@ -318,7 +207,7 @@ template <int ROWS, int DH> __device__ __forceinline__ void ag_store(const AgSta
 #pragma unroll
     for (int i = 0; i < AgStage<ROWS, DH>::NIT; ++i) {
         const int p = tid + i * AG_THREADS;
-        if (p < ROWS * SPR) *reinterpret_cast<u32x4*>(lds + img_off<bf16, DH>(p / SPR, p % SPR)) = st.v[i];
+        if (p < ROWS * SPR) *reinterpret_cast<u32x4*>(lds + tile_off<bf16, DH>(p / SPR, p % SPR)) = st.v[i];
     }
 }
 
@@ -443,7 +332,7 @@ __device__ __forceinline__ void ag_dq_pass(const AgCtx<DH, NB, EXACT>& cx, int b
         for (int c = 0; c < NCH; ++c)
 #pragma unroll
             for (int i = 0; i < 8; ++i) dl = fmaf((float)o.dof[j][c][i], (float)o.of[j][c][i], dl);
-        neg_delta[j] = -gsum(dl);                      // delta[q] = sum_d dO[q][d] O[q][d]; the lanes li, li + 16, .. hold the row's slots
+        neg_delta[j] = -group_sum(dl);                      // delta[q] = sum_d dO[q][d] O[q][d]; the lanes li, li + 16, .. hold the row's slots
         neg_lse[j] = -cx.ldsLse[q];
         if (g == 0) ldsDeltaW[q] = neg_delta[j];       // phase B reads -delta (after the barrier between the phases)
     }
@@ -470,8 +359,8 @@ __device__ __forceinline__ void ag_dq_pass(const AgCtx<DH, NB, EXACT>& cx, int b
                     f32x4 sacc = {0.f, 0.f, 0.f, 0.f}, dp = {neg_delta[j], neg_delta[j], neg_delta[j], neg_delta[j]};
 #pragma unroll
                     for (int c = 0; c < NCH; ++c) {
-                        MmaS<T>::mma(sacc, kfr[c], o.qf[j][c]);
-                        MmaS<T>::mma(dp, vfr[c], o.dof[j][c]);
+                        Mma16<T>::mma(sacc, kfr[c], o.qf[j][c]);
+                        Mma16<T>::mma(dp, vfr[c], o.dof[j][c]);
                     }
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
@@ -492,7 +381,7 @@ __device__ __forceinline__ void ag_dq_pass(const AgCtx<DH, NB, EXACT>& cx, int b
         for (int d = 0; d < NDB; ++d) {
             const bf16x8 ktr = af_tr<RB>(cx.slot0, cx.trb ^ (d << 5), rc);
 #pragma unroll
-            for (int j = 0; j < NJ; ++j) MmaS<T>::mma(dq[j][d], ktr, f[j]);
+            for (int j = 0; j < NJ; ++j) Mma16<T>::mma(dq[j][d], ktr, f[j]);
         }
         __builtin_amdgcn_sched_barrier(0);
 #ifdef AG_STAMP
@@ -556,8 +445,8 @@ __device__ __forceinline__ void ag_dkv_pass(const AgCtx<DH, NB, EXACT>& cx, int 
                     f32x4 sacc = {0.f, 0.f, 0.f, 0.f}, dp = nd4;
 #pragma unroll
                     for (int c = 0; c < NCH; ++c) {
-                        MmaS<T>::mma(sacc, qfr[c], o.kf[j][c]);
-                        MmaS<T>::mma(dp, dofr[c], o.vf[j][c]);
+                        Mma16<T>::mma(sacc, qfr[c], o.kf[j][c]);
+                        Mma16<T>::mma(dp, dofr[c], o.vf[j][c]);
                     }
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
@@ -586,8 +475,8 @@ __device__ __forceinline__ void ag_dkv_pass(const AgCtx<DH, NB, EXACT>& cx, int 
             const bf16x8 qtr = af_tr<RB>(cx.slot0, cx.trb ^ (d << 5), rc);
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
-                MmaS<T>::mma(dv[j][d], dotr, fp[j]);
-                MmaS<T>::mma(dk[j][d], qtr, fs[j]);
+                Mma16<T>::mma(dv[j][d], dotr, fp[j]);
+                Mma16<T>::mma(dk[j][d], qtr, fs[j]);
             }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -631,8 +520,8 @@ __global__ __launch_bounds__(AG_THREADS, 2) void attn_g_bwd_kernel(const bf16* _
     const int nqb = (N + 15) / 16;
     constexpr int STEP = AG_WAVES * NJ;                 // blocks between a wave's two passes (N <= 256: never more than two per phase)
     const int rs_bytes = (int)rs * 2, d_bytes = D * 2;
-    const __amdgpu_buffer_rsrc_t rQ = ag_rsrc(qbase, N * rs_bytes), rDO = ag_rsrc(dobase, N * d_bytes), rO = ag_rsrc(obase, N * d_bytes),
-                                 rDQ = ag_rsrc(dqbase, N * rs_bytes);
+    const __amdgpu_buffer_rsrc_t rQ = buffer_rsrc(qbase, N * rs_bytes), rDO = buffer_rsrc(dobase, N * d_bytes), rO = buffer_rsrc(obase, N * d_bytes),
+                                 rDQ = buffer_rsrc(dqbase, N * rs_bytes);
     AG_STAMP_HERE(0);
     AgOpsA<NJ, NCH> oa, oa2;
     ag_a_fetch<NJ, DH>(oa, wave * NJ, rQ, rs_bytes, rDO, rO, d_bytes, li, lane);     // first phase-A pass: requested with the images
@@ -742,7 +631,7 @@ __global__ __launch_bounds__(AG_THREADS, 3) void attn_s3_fwd_kernel(const bf16* 
     // workgroup has one global-memory round trip instead of one per pass
     constexpr int NPASS = (NB + AG_WAVES - 1) / AG_WAVES;
     const int rs_bytes = (int)rs * 2;
-    const __amdgpu_buffer_rsrc_t rQ = ag_rsrc(qbase, N * rs_bytes);
+    const __amdgpu_buffer_rsrc_t rQ = buffer_rsrc(qbase, N * rs_bytes);
     bf16x8 qf_all[NPASS][NCH];
 #pragma unroll
     for (int i = 0; i < NPASS; ++i)
@@ -758,7 +647,6 @@ __global__ __launch_bounds__(AG_THREADS, 3) void attn_s3_fwd_kernel(const bf16* 
     __syncthreads();
     const AfBases<DH> ab(lane);
     const int trb = ab.trb;
-    constexpr int nb_ = NB;
     const int nqb = (N + 15) / 16;
 #pragma unroll
     for (int ps = 0; ps < NPASS; ++ps) {
@@ -774,7 +662,7 @@ __global__ __launch_bounds__(AG_THREADS, 3) void attn_s3_fwd_kernel(const bf16* 
         for (int kb = 0; kb < NB; ++kb) {
             s[kb] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int c = 0; c < NCH; ++c) MmaS<T>::mma(s[kb], af_row<RB>(ldsK, ab.rowb[c], kb), qf[c]);
+            for (int c = 0; c < NCH; ++c) Mma16<T>::mma(s[kb], af_row<RB>(ldsK, ab.rowb[c], kb), qf[c]);
             if (EXACT ? (kb == NB - 1) : (kb * 16 + 16 > N)) {   // only the ragged / padding key blocks pay for masking
 #pragma unroll
                 for (int r = 0; r < 4; ++r) s[kb][r] = (kb * 16 + 4 * g + r < N) ? s[kb][r] : -INFINITY;
@@ -783,7 +671,7 @@ __global__ __launch_bounds__(AG_THREADS, 3) void attn_s3_fwd_kernel(const bf16* 
             for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[kb][r]);
             if ((kb & 3) == 3) __builtin_amdgcn_sched_barrier(0);
         }
-        const float m = gmax(mx) * scale_log2e;
+        const float m = group_max(mx) * scale_log2e;
         float l = 0.f;
 #pragma unroll
         for (int kb = 0; kb < NB; ++kb)
@@ -793,15 +681,15 @@ __global__ __launch_bounds__(AG_THREADS, 3) void attn_s3_fwd_kernel(const bf16* 
                 s[kb][r] = p;
                 l += p;
             }
-        const float lt = gsum(l);
+        const float lt = group_sum(l);
         f32x4 o[NDB];
 #pragma unroll
         for (int d = 0; d < NDB; ++d) o[d] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int rc = 0; rc < NRC; ++rc) {
-            const bf16x8 pf = s_frag_acc<T, nb_>(s, rc);
+            const bf16x8 pf = frag_from_acc<T, NB>(s, rc);
 #pragma unroll
-            for (int d = 0; d < NDB; ++d) MmaS<T>::mma(o[d], af_tr<RB>(ldsV, trb ^ (d << 5), rc), pf);
+            for (int d = 0; d < NDB; ++d) Mma16<T>::mma(o[d], af_tr<RB>(ldsV, trb ^ (d << 5), rc), pf);
             __builtin_amdgcn_sched_barrier(0);
         }
         if (q < N) {
@@ -819,40 +707,63 @@ __global__ __launch_bounds__(AG_THREADS, 3) void attn_s3_fwd_kernel(const bf16* 
     }
 }
 
-template <int DH, int NB>
-int launch_s3_fwd(const void* qkv, void* out, float* lse, int64_t B, int64_t N, int64_t H, float scale, hipStream_t s) {
-    constexpr size_t smem = 2 * (size_t)NB * 16 * (DH * 2);
-    const float sl2 = scale * 1.44269504088896340736f;
-    const dim3 grid((unsigned)(B * H)), block(AG_THREADS);
-    if ((N + 15) / 16 == NB) {
-        if (int rc = big_lds(attn_s3_fwd_kernel<DH, NB, true>, smem)) return rc;
-        hipLaunchKernelGGL((attn_s3_fwd_kernel<DH, NB, true>), grid, block, smem, s, (const bf16*)qkv, (bf16*)out, lse, (int)N, (int)H, sl2);
-    } else {
-        if (int rc = big_lds(attn_s3_fwd_kernel<DH, NB, false>, smem)) return rc;
-        hipLaunchKernelGGL((attn_s3_fwd_kernel<DH, NB, false>), grid, block, smem, s, (const bf16*)qkv, (bf16*)out, lse, (int)N, (int)H, sl2);
-    }
-    UCF_LAUNCH_CHECK("ucfvit_attention_fwd(short, 3 per CU)");
-    return UCFVIT_OK;
-}
 
-template <int DH, int NB>
-int launch_fused_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* cs_partial, int64_t B, int64_t N, int64_t H,
-                     float scale, hipStream_t s) {
-    constexpr int ROWS = ((NB + 1) / 2) * 32;
-    constexpr size_t smem = 2 * (size_t)ROWS * (DH * 2) + 2 * ROWS * sizeof(float) + AG_WAVES * DH * sizeof(float);
-    const float sl2 = scale * 1.44269504088896340736f;
-    const dim3 grid((unsigned)(B * H)), block(AG_THREADS);
-    if ((N + 15) / 16 == NB) {
-        if (int rc = big_lds(attn_g_bwd_kernel<DH, NB, true>, smem)) return rc;
-        hipLaunchKernelGGL((attn_g_bwd_kernel<DH, NB, true>), grid, block, smem, s, (const bf16*)qkv, (const bf16*)out, (const bf16*)dout, lse, (bf16*)dqkv, cs_partial, (int)N,
-                           (int)H, scale, sl2);
-    } else {
-        if (int rc = big_lds(attn_g_bwd_kernel<DH, NB, false>, smem)) return rc;
-        hipLaunchKernelGGL((attn_g_bwd_kernel<DH, NB, false>), grid, block, smem, s, (const bf16*)qkv, (const bf16*)out, (const bf16*)dout, lse, (bf16*)dqkv, cs_partial, (int)N,
-                           (int)H, scale, sl2);
+// =====================================================================================================================
+// launch: the three kernels are each instantiated per head dim, per NB bucket and per EXACT / masked; a family names its kernel,
+// its dynamic LDS and the buckets it exists for, launch_short picks the instantiation the route names
+// =====================================================================================================================
+static_assert(AS_THREADS == AG_THREADS, "one block size for the three families");
+
+struct ShortFwd {
+    static constexpr const char* name = "ucfvit_attention_fwd(short)";
+    static constexpr bool has(int nb) { return nb != 13; }
+    template <int DH, int NB> static constexpr size_t smem() { return 2 * AS<bf16, DH, NB>::IMG; }
+    template <int DH, int NB, bool EXACT> static auto kernel() { return attn_s_fwd_kernel<bf16, DH, NB, EXACT>; }
+};
+struct S3Fwd {
+    static constexpr const char* name = "ucfvit_attention_fwd(short, 3 per CU)";
+    static constexpr bool has(int nb) { return nb == 13; }
+    template <int DH, int NB> static constexpr size_t smem() { return 2 * (size_t)NB * 16 * (DH * 2); }
+    template <int DH, int NB, bool EXACT> static auto kernel() { return attn_s3_fwd_kernel<DH, NB, EXACT>; }
+};
+struct FusedBwd {
+    static constexpr const char* name = "ucfvit_attention_bwd(fused)";
+    static constexpr bool has(int nb) { return true; }
+    template <int DH, int NB> static constexpr size_t smem() {
+        constexpr int ROWS = ((NB + 1) / 2) * 32;
+        return 2 * (size_t)ROWS * (DH * 2) + 2 * ROWS * sizeof(float) + AG_WAVES * DH * sizeof(float);
     }
-    UCF_LAUNCH_CHECK("ucfvit_attention_bwd(fused)");
-    return UCFVIT_OK;
+    template <int DH, int NB, bool EXACT> static auto kernel() { return attn_g_bwd_kernel<DH, NB, EXACT>; }
+};
+
+template <class F, int DH, int NB, bool EXACT, typename... A> int launch_inst(int64_t BH, hipStream_t s, A... args) {
+    if constexpr (F::has(NB)) {
+        constexpr size_t smem = F::template smem<DH, NB>();
+        const auto kern = F::template kernel<DH, NB, EXACT>();
+        if (int rc = raise_lds_limit(kern, smem, "attention(short)")) return rc;
+        hipLaunchKernelGGL(kern, dim3((unsigned)BH), dim3(AS_THREADS), smem, s, args...);
+        UCF_LAUNCH_CHECK(F::name);
+        return UCFVIT_OK;
+    } else {
+        ucfvit_set_error("%s: no kernel for %d blocks", F::name, NB);      // attn_route names no such bucket for this family
+        return UCFVIT_ERR_HIP;
+    }
+}
+template <class F, int DH, int NB, typename... A> int pick_exact(const AttnRoute& r, int64_t BH, hipStream_t s, A... args) {
+    return r.exact ? launch_inst<F, DH, NB, true>(BH, s, args...) : launch_inst<F, DH, NB, false>(BH, s, args...);
+}
+template <class F, int DH, typename... A> int pick_nb(const AttnRoute& r, int64_t BH, hipStream_t s, A... args) {
+    switch (r.nb) {
+        case 4: return pick_exact<F, DH, 4>(r, BH, s, args...);
+        case 8: return pick_exact<F, DH, 8>(r, BH, s, args...);
+        case 13: return pick_exact<F, DH, 13>(r, BH, s, args...);
+        default: return pick_exact<F, DH, 16>(r, BH, s, args...);
+    }
+}
+// (The forward's bucket macro used to stand here and turn every launcher status but UCFVIT_OK into UCFVIT_ERR_HIP.  The launchers return
+// only UCFVIT_OK or UCFVIT_ERR_HIP, so handing their status through, as the backward always did, returns what the macro returned.)
+template <class F, typename... A> int launch_short(const AttnRoute& r, int64_t dh, int64_t BH, hipStream_t s, A... args) {
+    return dh == 64 ? pick_nb<F, 64>(r, BH, s, args...) : pick_nb<F, 32>(r, BH, s, args...);
 }
 
 }  // namespace
@@ -863,45 +774,16 @@ extern "C" int ucfvit_debug_attn_stamps(unsigned long long* out) {
 }
 #endif
 
-// returns 1 when handled, 0 when the shape is outside the short-sequence kernels (caller streams), <0 on error
-#define AS_PICK(FN, T, DH, ...)                          \
-    do {                                                 \
-        if (nb <= 4) return FN<T, DH, 4>(__VA_ARGS__) == UCFVIT_OK ? 1 : UCFVIT_ERR_HIP;   \
-        if (nb <= 8) return FN<T, DH, 8>(__VA_ARGS__) == UCFVIT_OK ? 1 : UCFVIT_ERR_HIP;   \
-        return FN<T, DH, 16>(__VA_ARGS__) == UCFVIT_OK ? 1 : UCFVIT_ERR_HIP;               \
-    } while (0)
-
-int ucfvit_attention_short_fwd(const void* qkv, void* out, float* lse, int64_t B, int64_t N, int64_t H, int64_t dh, float scale, int dtype,
-                               hipStream_t s) {
-    // bf16 only: the fp32 instantiations exceed the register file (the exact-fp32 parity mode keeps the streaming kernels)
-    if (dtype != UCFVIT_BF16 || N > 256 || (dh != 32 && dh != 64) || B * H >= (1ll << 31)) return 0;
-    const int nb = (int)((N + 15) / 16);
-    if (nb > 8 && nb <= 13) {          // 129 .. 208 tokens (N = 197): K and V resident as LDS images, three workgroups per CU
-        const int rc = dh == 64 ? launch_s3_fwd<64, 13>(qkv, out, lse, B, N, H, scale, s) : launch_s3_fwd<32, 13>(qkv, out, lse, B, N, H, scale, s);
-        return rc == UCFVIT_OK ? 1 : UCFVIT_ERR_HIP;
-    }
-    if (dh == 64) AS_PICK(launch_fwd, bf16, 64, qkv, out, lse, B, N, H, scale, s);
-    AS_PICK(launch_fwd, bf16, 32, qkv, out, lse, B, N, H, scale, s);
+int ucfvit_attn_launch_short_fwd(const AttnRoute& r, const void* qkv, void* out, float* lse, int64_t B, int64_t N, int64_t H, int64_t dh,
+                                 float scale, void* stream) {
+    const hipStream_t s = (hipStream_t)stream;
+    const float sl2 = scale * LOG2E_F;
+    if (r.family == AK_S3_FWD) return launch_short<S3Fwd>(r, dh, B * H, s, (const bf16*)qkv, (bf16*)out, lse, (int)N, (int)H, sl2);
+    return launch_short<ShortFwd>(r, dh, B * H, s, (const bf16*)qkv, (bf16*)out, lse, (int)N, (int)H, sl2);
 }
 
-int ucfvit_attention_fused_bwd_applies(int64_t B, int64_t N, int64_t H, int64_t dh, int dtype) {
-    return (dtype == UCFVIT_BF16 && N <= 256 && (dh == 64 || dh == 32) && B * H < (1ll << 31)) ? 1 : 0;
-}
-
-// fused backward (bf16, head dim 64 or 32, N <= 256; needs no delta workspace): 1 = handled, 0 = not applicable, <0 = error.
-// cs_partial (may be null): fp32 [B][2][H][dh], row b = the column sums of dQ over batch element b's tokens, then zeros for dK (see
-// ucfvit_attention_bwd_colsum)
-int ucfvit_attention_fused_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* cs_partial, int64_t B, int64_t N,
-                               int64_t H, int64_t dh, float scale, int dtype, hipStream_t s) {
-    if (!ucfvit_attention_fused_bwd_applies(B, N, H, dh, dtype)) return 0;
-    const int nb = (int)((N + 15) / 16);
-    int rc;
-#define AF_BWD(DH_)                                                                                       \
-    (nb <= 4 ? launch_fused_bwd<DH_, 4>(qkv, out, dout, lse, dqkv, cs_partial, B, N, H, scale, s)                     \
-             : nb <= 8 ? launch_fused_bwd<DH_, 8>(qkv, out, dout, lse, dqkv, cs_partial, B, N, H, scale, s)           \
-                       : nb <= 13 ? launch_fused_bwd<DH_, 13>(qkv, out, dout, lse, dqkv, cs_partial, B, N, H, scale, s) \
-                                  : launch_fused_bwd<DH_, 16>(qkv, out, dout, lse, dqkv, cs_partial, B, N, H, scale, s))
-    rc = dh == 64 ? AF_BWD(64) : AF_BWD(32);
-#undef AF_BWD
-    return rc == UCFVIT_OK ? 1 : rc;
+int ucfvit_attn_launch_fused_bwd(const AttnRoute& r, const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv,
+                                 float* cs_partial, int64_t B, int64_t N, int64_t H, int64_t dh, float scale, void* stream) {
+    return launch_short<FusedBwd>(r, dh, B * H, (hipStream_t)stream, (const bf16*)qkv, (const bf16*)out, (const bf16*)dout, lse, (bf16*)dqkv,
+                                  cs_partial, (int)N, (int)H, scale, scale * LOG2E_F);
 }
