@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define UCFVIT_ABI_VERSION 18
+#define UCFVIT_ABI_VERSION 19
 
 #define UCFVIT_OK 0
 #define UCFVIT_ERR_INVALID_ARGUMENT (-1)
@@ -439,6 +439,49 @@ int ucfvit_dice_ce_stats(const void* logits, const int64_t* labels, float* stats
 int ucfvit_dice_ce_from_stats(const void* logits, const int64_t* labels, float* stats, float* loss, void* dlogits, int64_t B, int64_t n, int64_t S,
                               int64_t S_total, int64_t stride_b, int64_t stride_c, int64_t stride_s, float smooth_nr, float smooth_dr,
                               float grad_scale, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * SAP segmentation head (reference simple/arch.py:491-536): ConvTranspose{2,3}d(D -> K, kernel = stride = p, no bias) followed by a 1x1
+ * convolution (K -> C, bias) with no nonlinearity between them, run as ONE Linear layer on the tokens:
+ *   W_eff[(delta, c)][d] = sum_k W_neck[d][k][delta] W_head[c][k]        delta = the P = p^nd offsets inside a patch, (kx p + ky) p + kz
+ *   rows[B S][P C] = tokens[B S][D] · W_effᵀ  (ucfvit_gemm, fp32 output),  map[b][c][voxel] = rows[b, token][(delta, c)] + bias[c]
+ * token t = (tx s + ty) s + tz of the s^nd grid, voxel (tx p + kx, ty p + ky, tz p + kz) of the (s p)^nd map; nd = 2 or 3, any p, s, C >= 1.
+ * Nothing here uses a floating-point atomic; every sum has a fixed order (results are bitwise reproducible).
+ *
+ * ucfvit_sap_fold:    w_neck fp32 [D][K][P], w_head fp32 [C][K] -> w_eff [P C][D] in `dtype` (summed in fp32 over k ascending, rounded once)
+ * ucfvit_sap_unfold:  dw_eff fp32 [P C][D] -> dw_neck fp32 [D][K][P] = sum_c dw_eff[(delta, c)][d] w_head[c][k] and
+ *                     dw_head fp32 [C][K] = sum_{d, delta} dw_eff[(delta, c)][d] w_neck[d][k][delta] (per d, then over d: ucfvit_reduce_rows);
+ *                     workspace: ucfvit_sap_unfold_workspace bytes.  P C <= 16384.
+ * ucfvit_sap_scatter_fwd: rows fp32 -> map fp32, one add per element.
+ * ucfvit_sap_scatter_bwd: dmap fp32 -> drows in `dtype` (the inverse permutation) and, unless dbias is NULL, dbias fp32 [C] = sum over b
+ *                     and voxels (two stages; workspace: ucfvit_sap_scatter_bwd_workspace bytes). */
+int ucfvit_sap_fold(const float* w_neck, const float* w_head, void* w_eff, int64_t D, int64_t K, int64_t P, int64_t C, int dtype, void* stream);
+int64_t ucfvit_sap_unfold_workspace(int64_t D, int64_t K, int64_t C);
+int ucfvit_sap_unfold(const float* dw_eff, const float* w_neck, const float* w_head, float* dw_neck, float* dw_head, int64_t D, int64_t K,
+                      int64_t P, int64_t C, void* workspace, void* stream);
+int ucfvit_sap_scatter_fwd(const float* rows, const float* bias, float* map, int64_t B, int64_t s, int64_t p, int64_t C, int nd, void* stream);
+int64_t ucfvit_sap_scatter_bwd_workspace(int64_t B, int64_t s, int64_t p, int64_t C, int nd);
+int ucfvit_sap_scatter_bwd(const float* dmap, void* drows, float* dbias, int64_t B, int64_t s, int64_t p, int64_t C, int nd, void* workspace,
+                           int dtype, void* stream);
+
+/* Dice + binary cross-entropy over channels 1..C-1 of a segmentation map (reference utils/metrics.py:95-121, the loss of
+ * train_sap_simple.py): p = sigmoid(z), I = sum p t, n = B (C - 1) S,
+ *   loss = weight mean(BCE) + (1 - weight) (1 - (2 I + smooth) / (sum p + sum t + smooth))
+ * logits [B][C][S] contiguous in `dtype`, targets fp32 [B][C][S] with values in [0, 1] (not necessarily one-hot).
+ * BCE(z, t) = t min(softplus(-z), 100) + (1 - t) min(softplus(z), 100): binary_cross_entropy(sigmoid(z), t) with its clamp of the logarithms
+ * at -100, evaluated without forming log(sigmoid) (so it stays exact where fp32 sigmoid has rounded to 0 or 1, |z| > ~17).
+ * ucfvit_dice_bce_stats:      one pass; stats fp32 [ucfvit_dice_bce_stats_floats() = 4] = sum p t, sum p, sum t, sum BCE (per-workgroup partial
+ *                             sums, then one fixed-order sum of the partials); workspace: ucfvit_dice_bce_workspace bytes.
+ * ucfvit_dice_bce_from_stats: loss (unless NULL) and dlogits (unless NULL; fp32 whatever `dtype`, channel 0 exact zeros) =
+ *                             g (weight (p - t) / n + (1 - weight) p (1 - p) ((2 I + smooth) / Dn^2 - 2 t / Dn)),  Dn = sum p + sum t + smooth,
+ *                             g = grad_scale, times *grad_scale_dev when that device pointer is not NULL (the upstream gradient of autograd,
+ *                             read on the device: no host synchronisation). */
+int ucfvit_dice_bce_stats_floats(void);
+int64_t ucfvit_dice_bce_workspace(int64_t B, int64_t C, int64_t S);
+int ucfvit_dice_bce_stats(const void* logits, const float* targets, float* stats, int64_t B, int64_t C, int64_t S, void* workspace, int dtype,
+                          void* stream);
+int ucfvit_dice_bce_from_stats(const void* logits, const float* targets, const float* stats, float* loss, float* dlogits, int64_t B, int64_t C,
+                               int64_t S, float weight, float smooth, float grad_scale, const float* grad_scale_dev, int dtype, void* stream);
 
 /* Channels-last instance norm (+ LeakyReLU, + residual) for the layout of the convolution kernels below: x, res, y [B][S][C] bf16,
  * mean / rstd [B][C] fp32; C a power of two in 8..2048.  Same formulas as ucfvit_instnorm_fwd / _bwd, one entry point per pass:

@@ -919,6 +919,66 @@ def dice_grad_times(dl, g):
     return (flat * g.to(dl.dtype)).as_strided(dl.shape, dl.stride())
 
 
+class SapHeadFn(torch.autograd.Function):
+    """SAP.mask_head (reference simple/arch.py:523-533): ConvTranspose neck (kernel = stride = p, no bias) + 1x1 header on the token grid, as
+    ONE Linear layer.  The two convolutions have no nonlinearity between them, so their weights fold into W_eff [p^nd C, D] (ops.sap_fold,
+    fp32, rounded once to the compute dtype); the tokens go through ucfvit_gemm with an fp32 output and ops.sap_scatter_fwd moves the C
+    channels into the [B, C, *(s p,) * nd] map.  The 256-channel map of the two-step form never exists.  Backward: inverse scatter, the data
+    and weight gradient GEMMs of a Linear layer, ops.sap_unfold back to the gradients of the two convolution weights (fp32, fixed order)."""
+
+    @staticmethod
+    def forward(ctx, x, w_neck, w_head, b_head, p, s, nd, cdtype):
+        B, S, D = x.shape
+        if S != s ** nd:
+            raise ValueError(f"SapHeadFn: {S} tokens do not fill a grid of {s}^{nd}")
+        x2 = _as(x, cdtype).view(B * S, D)                       # x may be a slice (class token stripped): _as makes it dense
+        wn, wh, bh = compute_param(w_neck, torch.float32), compute_param(w_head, torch.float32), compute_param(b_head, torch.float32)
+        w_eff = ops.sap_fold(wn, wh, cdtype)
+        N = w_eff.shape[0]
+        rows = ops.gemm(x2, w_eff, B * S, N, D, ops.LAYOUT_KC, ops.LAYOUT_KC, out_dtype=torch.float32)
+        out = ops.sap_scatter_fwd(rows, bh, B, p, s, nd)
+        ctx.save_for_backward(x2, w_eff, w_neck, w_head)
+        ctx.geom, ctx.cdtype, ctx.in_dtype, ctx.in_shape = (p, s, nd), cdtype, x.dtype, x.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x2, w_eff, w_neck, w_head = ctx.saved_tensors
+        p, s, nd = ctx.geom
+        d = dout if dout.dtype == torch.float32 else dout.float()
+        drows, dbias = ops.sap_scatter_bwd(d if d.is_contiguous() else d.contiguous(), p, s, nd, ctx.cdtype, want_dbias=ctx.needs_input_grad[3])
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = _ret_grad(ops.linear_dgrad(drows, w_eff).view(ctx.in_shape), ctx.in_dtype)
+        gn = gh = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            dw_eff = ops.linear_wgrad(drows, x2)
+            gn, gh = ops.sap_unfold(dw_eff, compute_param(w_neck, torch.float32), compute_param(w_head, torch.float32))
+        return dx, gn, gh, dbias, None, None, None, None
+
+
+class DiceBCEFn(torch.autograd.Function):
+    """utils/metrics.DiceBLoss with act=True (reference utils/metrics.py:95-121): one statistics pass in forward, the gradient pass in backward
+    with autograd's upstream scalar read on the device.  logits fp32 or bf16 [B, C, *spatial], targets fp32 of the same shape."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, weight, smooth):
+        lg = logits if logits.is_contiguous() else logits.contiguous()
+        tg = targets if targets.is_contiguous() else targets.contiguous()
+        stats = ops.dice_bce_stats(lg, tg)
+        loss, _ = ops.dice_bce_from_stats(lg, tg, stats, weight, smooth, want_grad=False)
+        ctx.save_for_backward(lg, tg, stats)
+        ctx.weight, ctx.smooth = weight, smooth
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        lg, tg, stats = ctx.saved_tensors
+        gd = g if g.dtype == torch.float32 else g.float()
+        _, dl = ops.dice_bce_from_stats(lg, tg, stats, ctx.weight, ctx.smooth, 1.0, gd.contiguous(), want_loss=False)
+        return _ret_grad(dl, lg.dtype), None, None, None
+
+
 # ---------------------------------------------------------------------------------------------- public helpers
 def instnorm_act(x, res=None, eps=1e-5, slope=0.01):
     return InstNormActFn.apply(x, res, eps, slope)
@@ -926,6 +986,10 @@ def instnorm_act(x, res=None, eps=1e-5, slope=0.01):
 
 def dice_ce(logits, labels, smooth_nr=1e-5, smooth_dr=1e-5):
     return DiceCEFn.apply(logits, labels, smooth_nr, smooth_dr)
+
+
+def dice_bce(logits, targets, weight=0.5, smooth=1.0):
+    return DiceBCEFn.apply(logits, targets, float(weight), float(smooth))
 
 
 def cross_entropy(logits, labels):

@@ -700,6 +700,120 @@ def dice_ce_from_stats(logits, labels, stats, S_total, smooth_nr=1e-5, smooth_dr
     return loss, dl
 
 
+# ------------------------------------------------------------------------------------------------ SAP head and Dice + BCE
+def _sap_dims(p, s, nd):
+    if nd not in (2, 3) or p < 1 or s < 1:
+        raise ValueError(f"sap head: need nd in (2, 3), p >= 1, s >= 1 (got nd={nd}, p={p}, s={s})")
+    return p ** nd, s ** nd
+
+
+def sap_fold(w_neck, w_head, dtype):
+    """w_neck fp32 [D, K, *(p,) * nd] (ConvTranspose weight), w_head fp32 [C, K, 1, ..] (1x1 convolution weight) -> W_eff [P C, D] in `dtype`:
+    the Linear weight of header(neck(.)), rows ordered (offset in the patch, class)"""
+    L = _l.load()
+    _chk(w_neck, "sap_fold.w_neck"), _chk(w_head, "sap_fold.w_head")
+    if w_neck.dtype != torch.float32 or w_head.dtype != torch.float32:
+        raise TypeError("sap_fold: the weights are folded in fp32")
+    D, K = w_neck.shape[0], w_neck.shape[1]
+    P, C = w_neck.numel() // (D * K), w_head.shape[0]
+    if w_head.numel() != C * K:
+        raise ValueError(f"sap_fold: w_head {tuple(w_head.shape)} does not take the {K} channels of w_neck {tuple(w_neck.shape)}")
+    w_eff = torch.empty((P * C, D), dtype=dtype, device=w_neck.device)
+    _l.check(L.ucfvit_sap_fold(w_neck.data_ptr(), w_head.data_ptr(), w_eff.data_ptr(), D, K, P, C, dt(w_eff), _stream()), "ucfvit_sap_fold")
+    return w_eff
+
+
+def sap_unfold(dw_eff, w_neck, w_head):
+    """dw_eff fp32 [P C, D] -> (dw_neck fp32 like w_neck, dw_head fp32 like w_head)"""
+    L = _l.load()
+    _chk(dw_eff, "sap_unfold.dw_eff"), _chk(w_neck, "sap_unfold.w_neck"), _chk(w_head, "sap_unfold.w_head")
+    if dw_eff.dtype != torch.float32 or w_neck.dtype != torch.float32 or w_head.dtype != torch.float32:
+        raise TypeError("sap_unfold: fp32 operands only")
+    D, K = w_neck.shape[0], w_neck.shape[1]
+    P, C = w_neck.numel() // (D * K), w_head.shape[0]
+    if tuple(dw_eff.shape) != (P * C, D) or w_head.numel() != C * K:
+        raise ValueError(f"sap_unfold: dw_eff {tuple(dw_eff.shape)} / w_head {tuple(w_head.shape)} do not fit w_neck {tuple(w_neck.shape)}")
+    dw_neck, dw_head = torch.empty_like(w_neck), torch.empty_like(w_head)
+    ws = workspace(L.ucfvit_sap_unfold_workspace(D, K, C), dw_eff.device)
+    _l.check(L.ucfvit_sap_unfold(dw_eff.data_ptr(), w_neck.data_ptr(), w_head.data_ptr(), dw_neck.data_ptr(), dw_head.data_ptr(), D, K, P, C,
+                                 ws.data_ptr(), _stream()), "ucfvit_sap_unfold")
+    return dw_neck, dw_head
+
+
+def sap_scatter_fwd(rows, bias, B, p, s, nd):
+    """rows fp32 [B s^nd, p^nd C] (columns ordered (offset in the patch, class)), bias fp32 [C] -> map fp32 [B, C, *(s p,) * nd]"""
+    L = _l.load()
+    _chk(rows, "sap_scatter_fwd.rows"), _chk(bias, "sap_scatter_fwd.bias")
+    P, S = _sap_dims(p, s, nd)
+    C = bias.numel()
+    if rows.dtype != torch.float32 or bias.dtype != torch.float32:
+        raise TypeError("sap_scatter_fwd: rows and bias must be float32")
+    if rows.dim() != 2 or tuple(rows.shape) != (B * S, P * C):
+        raise ValueError(f"sap_scatter_fwd: rows must be [{B * S}, {P * C}], got {tuple(rows.shape)}")
+    out = torch.empty((B, C) + (s * p,) * nd, dtype=torch.float32, device=rows.device)
+    _l.check(L.ucfvit_sap_scatter_fwd(rows.data_ptr(), bias.data_ptr(), out.data_ptr(), B, s, p, C, nd, _stream()), "ucfvit_sap_scatter_fwd")
+    return out
+
+
+def sap_scatter_bwd(dmap, p, s, nd, dtype, want_dbias=True):
+    """dmap fp32 [B, C, *(s p,) * nd] -> (drows [B s^nd, p^nd C] in `dtype`, dbias fp32 [C] or None)"""
+    L = _l.load()
+    _chk(dmap, "sap_scatter_bwd.dmap")
+    P, S = _sap_dims(p, s, nd)
+    if dmap.dtype != torch.float32:
+        raise TypeError("sap_scatter_bwd: dmap must be float32")
+    if dmap.dim() != nd + 2 or tuple(dmap.shape[2:]) != (s * p,) * nd:
+        raise ValueError(f"sap_scatter_bwd: dmap must be [B, C, {', '.join([str(s * p)] * nd)}], got {tuple(dmap.shape)}")
+    B, C = dmap.shape[0], dmap.shape[1]
+    drows = torch.empty((B * S, P * C), dtype=dtype, device=dmap.device)
+    dbias = torch.empty(C, dtype=torch.float32, device=dmap.device) if want_dbias else None
+    ws = workspace(L.ucfvit_sap_scatter_bwd_workspace(B, s, p, C, nd), dmap.device) if want_dbias else None
+    _l.check(L.ucfvit_sap_scatter_bwd(dmap.data_ptr(), drows.data_ptr(), _p(dbias), B, s, p, C, nd, _p(ws), dt(drows), _stream()),
+             "ucfvit_sap_scatter_bwd")
+    return drows, dbias
+
+
+def _dice_bce_layout(logits, targets, name):
+    _chk(logits, f"{name}.logits"), _chk(targets, f"{name}.targets")
+    if targets.dtype != torch.float32:
+        raise TypeError(f"{name}: targets must be float32")
+    if logits.dim() < 3 or targets.shape != logits.shape or logits.shape[1] < 2:
+        raise ValueError(f"{name}: logits and targets must both be [B, classes >= 2, *spatial], got {tuple(logits.shape)} and {tuple(targets.shape)}")
+    B, C = logits.shape[0], logits.shape[1]
+    return B, C, logits.numel() // (B * C)
+
+
+def dice_bce_stats(logits, targets):
+    """logits [B, C, *spatial] (fp32 or bf16), targets fp32 of the same shape -> fp32 [4]: sum p t, sum p, sum t, sum BCE over channels 1.."""
+    L = _l.load()
+    B, C, S = _dice_bce_layout(logits, targets, "dice_bce_stats")
+    stats = torch.empty(L.ucfvit_dice_bce_stats_floats(), dtype=torch.float32, device=logits.device)
+    ws = workspace(L.ucfvit_dice_bce_workspace(B, C, S), logits.device)
+    _l.check(L.ucfvit_dice_bce_stats(logits.data_ptr(), targets.data_ptr(), stats.data_ptr(), B, C, S, ws.data_ptr(), dt(logits), _stream()),
+             "ucfvit_dice_bce_stats")
+    return stats
+
+
+def dice_bce_from_stats(logits, targets, stats, weight=0.5, smooth=1.0, grad_scale=1.0, grad_scale_dev=None, want_loss=True, want_grad=True):
+    """-> (loss fp32 scalar or None, dlogits fp32 or None); the gradient is scaled by grad_scale and, when given, by the fp32 device
+    scalar grad_scale_dev (autograd's upstream gradient, read by the kernel)"""
+    L = _l.load()
+    B, C, S = _dice_bce_layout(logits, targets, "dice_bce_from_stats")
+    _chk(stats, "dice_bce_from_stats.stats")
+    if stats.dtype != torch.float32 or stats.numel() != L.ucfvit_dice_bce_stats_floats():
+        raise TypeError("dice_bce_from_stats: stats must be the fp32 tensor dice_bce_stats returns")
+    if grad_scale_dev is not None:
+        _chk(grad_scale_dev, "dice_bce_from_stats.grad_scale_dev")
+        if grad_scale_dev.dtype != torch.float32 or grad_scale_dev.numel() != 1:
+            raise TypeError("dice_bce_from_stats: grad_scale_dev must be one float32 value")
+    loss = torch.empty((), dtype=torch.float32, device=logits.device) if want_loss else None
+    dl = torch.empty(logits.shape, dtype=torch.float32, device=logits.device) if want_grad else None
+    _l.check(L.ucfvit_dice_bce_from_stats(logits.data_ptr(), targets.data_ptr(), stats.data_ptr(), _p(loss), _p(dl), B, C, S, float(weight),
+                                          float(smooth), float(grad_scale), _p(grad_scale_dev), dt(logits), _stream()),
+             "ucfvit_dice_bce_from_stats")
+    return loss, dl
+
+
 # ------------------------------------------------------------------------------------------------ UNETR decoder, channels-last bf16
 def _chk_cl(t, name, C=None):
     _chk(t, name)

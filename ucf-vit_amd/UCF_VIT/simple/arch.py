@@ -337,7 +337,10 @@ class VIT(nn.Module):
 
 
 class SAP(VIT):
-    """Segmentation head on the ViT encoder (reference :491-536): ConvTranspose neck + 1x1 conv (MIOpen; SURVEY §2 out of scope)."""
+    """Segmentation head on the ViT encoder (reference :491-536): ConvTranspose neck (embed_dim -> 256, kernel = stride = patch) + 1x1
+    header (256 -> classes).  `neck` and `mask_header` hold the parameters (state_dict as the reference's); the arithmetic is HF.SapHeadFn:
+    the two convolutions have no nonlinearity between them, so they run folded into one Linear layer on the tokens plus a scatter into the
+    [B, classes, *spatial] fp32 map, all on the HIP kernels ("SAP head")."""
 
     def __init__(self, *args, **kwargs):
         self.sqrt_len = kwargs.pop('sqrt_len', '')
@@ -353,14 +356,12 @@ class SAP(VIT):
         self.init_weights('')
 
     def mask_head(self, x: torch.Tensor):
-        s = self.sqrt_len
-        B, _, C = x.shape
-        x = x.float()
-        if self.twoD:
-            x = x.reshape(B, s, s, C).permute(0, 3, 1, 2)
-        else:
-            x = x.reshape(B, s, s, s, C).permute(0, 4, 1, 2, 3)
-        return self.mask_header(self.neck(x))
+        """x [B, sqrt_len^nd, embed_dim] (may be a slice: class token stripped) -> [B, classes, *(sqrt_len * patch,) * nd] fp32"""
+        if not x.is_cuda:
+            raise RuntimeError(f"SAP.mask_head: expected tokens on the MI355X (cuda) device, got {x.device}. "
+                               "UCF_VIT operators run only through libucfvit_hip.so; there is no CPU path.")
+        head = self.mask_header[0]
+        return HF.SapHeadFn.apply(x, self.neck[0].weight, head.weight, head.bias, self.patch_size, self.sqrt_len, 2 if self.twoD else 3, _cd(self))
 
     def forward_head(self, x: torch.Tensor) -> torch.Tensor:
         return self.mask_head(self.pool(x))

@@ -30,14 +30,20 @@ def cross_entropy_loss(logits, labels):
 
 class DiceBLoss(torch.nn.Module):
     """Dice + binary cross-entropy over the non-background channels of a segmentation map (reference utils/metrics.py:95-121, the
-    loss of train_sap_simple.py:44-46): sigmoid, channels 1.. flattened, loss = w * BCE + (1 - w) * (1 - dice).  Loss arithmetic on
-    the [B, classes, ...] output map runs on torch ops in fp32 (outside the token path)."""
+    loss of train_sap_simple.py:44-46): sigmoid, channels 1.. flattened, loss = w * BCE + (1 - w) * (1 - dice).  On GPU tensors with
+    act=True the loss and its gradient are two HIP passes over the map (HF.DiceBCEFn: ucfvit_dice_bce_stats / _from_stats; targets are
+    cast to fp32, soft targets allowed).  CPU tensors, or act=False (inputs that are probabilities already), keep the torch arithmetic below
+    (a checker for the kernels; no training path uses it)."""
 
     def __init__(self, weight=0.5, num_class=2, size_average=True):
         super().__init__()
         self.weight, self.num_class = weight, num_class
 
     def forward(self, inputs, targets, smooth=1, act=True):
+        if act and inputs.is_cuda:
+            if inputs.dtype not in (torch.float32, torch.bfloat16):
+                inputs = inputs.float()
+            return HF.dice_bce(inputs, targets.float().contiguous(), self.weight, smooth)
         inputs = inputs.float()
         if act:
             inputs = torch.sigmoid(inputs)

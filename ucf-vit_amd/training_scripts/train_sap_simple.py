@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """SAP segmentation training on adaptively patched input — entry point compatible with the reference's
 training_scripts/train_sap_simple.py:  python train_sap_simple.py <config.yaml> [MPI]
-The ViT encoder (patch-embedding convolution on the pseudo image, position embedding from seq_ps, Blocks) runs on the HIP kernels;
-the transposed-convolution neck, the 1x1 header and the Dice+BCE loss stay on torch / MIOpen."""
+The whole step runs on the HIP kernels: the ViT encoder (patch-embedding convolution on the pseudo image, position embedding from
+seq_ps, Blocks), the transposed-convolution neck and the 1x1 header folded into one Linear layer plus a scatter (HF.SapHeadFn), and the
+Dice+BCE loss (HF.DiceBCEFn behind utils/metrics.DiceBLoss)."""
 import sys
 
 import torch
