@@ -949,12 +949,13 @@ int launch_fwd_mc(const bf16* x, const bf16* wp, bf16* y, ConvGeo g, float* stat
     return UCFVIT_OK;
 }
 
-// UCFVIT_CONV_STRIP — a TEST hook (tests/test_conv3d.py runs every shape through both kernel families and compares them bit for bit):
-// 0 never, 1 (default) when the (x, y) columns fill the chip, 2 whenever the column kernel applies.  Read once (thread-safe static).
+// UCFVIT_CONV_STRIP=0|2|3 — a TEST hook (tests/test_conv3d.py runs every shape through both kernel families and compares them bit for bit;
+// tests/test_conv3d_ops.py runs its case table under 0, 2 and 3 against float64): 0 never, 1 (default) when the (x, y) columns fill the chip,
+// 2 whenever the column kernel applies, 3 as 2 with the branching (non-FAST) memory operations.  Read once (thread-safe static).
 static int strip_mode() {
     static const int flag = [] {
         const char* e = getenv("UCFVIT_CONV_STRIP");
-        return (e && e[0] >= '0' && e[0] <= '3') ? e[0] - '0' : 1;      // 3 (test hook): column kernels with the branching memory operations
+        return (e && e[0] >= '0' && e[0] <= '3') ? e[0] - '0' : 1;
     }();
     return flag;
 }
@@ -968,11 +969,11 @@ static FwdPlan fwd_plan(const ConvGeo& g, int ksize, bool has_bias, bool out_bf1
     if (cpc == 32 && ksize == 3 && out_bf16 && g.Cin > 32 && !has_bias && g.Cout % 32 == 0 && g.cout_store == g.Cout && g.ldy == g.Cout && strip_mode() &&
         (g.Z == 16 || g.Z == 32 || g.Z == 64)) {
         const int64_t wgs = (int64_t)g.B * ((g.X + 1) / 2) * ((g.Y + 7) / 8) * (g.Cout / 32);
-        if (strip_mode() == 2 || wgs >= 512) return FwdPlan{2, 2, 8};
+        if (strip_mode() >= 2 || wgs >= 512) return FwdPlan{2, 2, 8};
     }
     if (g.Cin == cpc && g.Z > 16 && strip_mode()) {
         const int64_t cols = (int64_t)g.B * ((g.X + 1) / 2) * ((g.Y + 7) / 8);
-        if (strip_mode() == 2 || cols * (nb16 % 4 == 0 ? nb16 / 4 : nb16 % 2 == 0 ? nb16 / 2 : nb16) >= 512) {
+        if (strip_mode() >= 2 || cols * (nb16 % 4 == 0 ? nb16 / 4 : nb16 % 2 == 0 ? nb16 / 2 : nb16) >= 512) {
             if (nb16 % 4 == 0) return FwdPlan{1, 2, 4};
             if (nb16 % 2 == 0 || cpc == 32) return FwdPlan{1, 2, 8};      // (CPC 32, NB 1): the 4 x 8 tile's prefetch would not fit in registers
             return FwdPlan{1, 4, 8};
