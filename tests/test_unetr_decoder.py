@@ -1,6 +1,7 @@
 """csrc/unetr_decoder.hip (the HBM-bound part of the UNETR conv decoder) against oracle/unetr_decoder_ref.py — the
 plain-torch restatement of monai's UnetResBlock normalisation chain and DiceCELoss (PARITY UNPINNED against monai itself: not vendored,
-no reference fixtures).  Tolerances: fp32 1e-4 rel (statistics over up to 10^6 voxels), bf16 3e-2."""
+no reference fixtures).  Tolerances: fp32 1e-4 rel (statistics over up to 10^6 voxels), bf16 3e-2.
+The per-element bounds and the exact cases of these kernels live in tests/test_norm_loss_ops.py."""
 import pytest
 import torch
 
