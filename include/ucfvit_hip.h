@@ -287,7 +287,8 @@ int ucfvit_quadtree_serialize(const float* img, const int32_t* nodes, const int3
  * domain uint8 [B][N][N][N] indexed [z][y][x] (cubic, N <= 256); value = sum(region) / norm_factor (norm_factor = int(255 / channels),
  * transform.py:120); children in the reference's order (x fastest, then y, then z); fixed_length L must be 7n+1; stop when the first
  * maximum node is 2 wide.  nodes int32 [B][L][6] = (x1, x2, y1, y2, z1, z2), values, count as for the quadtree; seq_ps fp32 [B][L][4] =
- * (size, centre x, y, z), padding size 0 / centre -1.  workspace: ucfvit_octree_workspace bytes.
+ * (size, centre x, y, z), padding size 0 / centre -1.  workspace: ucfvit_octree_workspace bytes.  N^3 * 255 / norm_factor < 2^31 (values
+ * are int32): refused otherwise, e.g. N >= 204 with norm_factor 1.
  * ucfvit_octree_serialize: img fp32 [B][N][N][N][C]; leaf img[z1:z2, y1:y2, x1:x2, :] -> p^3 by linear interpolation with aligned corners
  * (the reference's scipy RegularGridInterpolator on linspace(0, n, n) -> linspace(0, n, p)), seq fp32 [B][L][p][p][p][C]. */
 int64_t ucfvit_octree_workspace(int64_t B, int64_t N);

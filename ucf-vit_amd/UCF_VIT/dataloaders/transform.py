@@ -23,7 +23,7 @@ class Patchify(torch.nn.Module):
 
     def __init__(self, fixed_length=196, patch_size=16, num_channels=3):
         super().__init__()
-        if fixed_length % 3 != 1:
+        if fixed_length < 1 or fixed_length % 3 != 1:              # -2 % 3 == 1 in Python: the sign is checked apart
             raise ValueError("Quadtree fixed length needs to be 3n+1, where n is some integer")      # train_unetr_simple.py:214
         self.fixed_length, self.patch_size, self.num_channels = fixed_length, patch_size, num_channels
 
@@ -48,7 +48,7 @@ class Patchify_3D(torch.nn.Module):
 
     def __init__(self, fixed_length=729, patch_size=8, num_channels=1):
         super().__init__()
-        if fixed_length % 7 != 1:
+        if fixed_length < 1 or fixed_length % 7 != 1:
             raise ValueError("Octtree fixed length needs to be 7n+1, where n is some integer")       # train_unetr_simple.py:218
         self.fixed_length, self.patch_size, self.num_channels = fixed_length, patch_size, num_channels
         self.norm_factor = int(255 / num_channels)

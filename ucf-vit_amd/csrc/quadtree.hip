@@ -407,6 +407,11 @@ extern "C" int ucfvit_octree_build(const uint8_t* domain, int32_t* nodes, int32_
     UCF_CHECK_ARG(N > 0 && N <= 256, "ucfvit_octree_build: cubic volumes of side 1..256 (got %lld)", (long long)N);
     UCF_CHECK_ARG(L >= 1 && L % 7 == 1, "ucfvit_octree_build: fixed_length=%lld must be 7n+1 (every refinement adds seven nodes)", (long long)L);
     UCF_CHECK_ARG(norm_factor >= 1 && norm_factor <= 255, "ucfvit_octree_build: norm_factor=%d out of range", norm_factor);
+    // node values are int32 (kernel and `values` output): a dense volume's root value N^3 * 255 / norm_factor must stay below 2^31, or the
+    // maximum search (which starts at -1) finds no node and indexes the node list out of bounds
+    UCF_CHECK_ARG(N * N * N * 255 / norm_factor < (1ll << 31),
+                  "ucfvit_octree_build: N=%lld with norm_factor=%d: node values up to N^3 * 255 / norm_factor do not fit int32", (long long)N,
+                  norm_factor);
     const size_t smem = 2 * (size_t)(L + 8) * sizeof(ONode);
     UCF_CHECK_ARG(smem <= 150 * 1024, "ucfvit_octree_build: fixed_length=%lld does not fit the LDS node lists", (long long)L);
     hipStream_t s = (hipStream_t)stream;
