@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define UCFVIT_ABI_VERSION 19
+#define UCFVIT_ABI_VERSION 20
 
 #define UCFVIT_OK 0
 #define UCFVIT_ERR_INVALID_ARGUMENT (-1)
@@ -540,6 +540,8 @@ int ucfvit_instnorm_cl_bwd2(const void* dy, const void* y, const void* x, const 
  *   [Cout / (16 MB)][Cin / CPC][ksize^3][16 MB][max(CPC, 16)] with MB = 2 when Cout % 32 == 0, else 1 (ucfvit_conv3d_wgrad_size floats; for
  *   CPC = 8 columns 8..15 are scratch).  workspace: ucfvit_conv3d_wgrad_workspace bytes (per-workgroup partials, folded in a fixed order:
  *   deterministic).
+ * Dispatch: conv_fwd_route() / conv_wgrad_route() in csrc/conv_route.h decide once per call which instantiation runs and with what
+ *   geometry; the size queries return fields of the same route and ucfvit_conv3d_route names it.
  * ucfvit_depth_to_space2: the transposed convolution is the GEMM x[V][Cin] * w[Cin][8 Cout] followed by this shuffle of
  *   cols [B Xi Yi Zi][(dx, dy, dz)][C] into out [B][2 Xi][2 Yi][2 Zi][C] (to_space = 1) — or its inverse for the backward pass (0).  The
  *   space tensor may be a channel slice of a wider channels-last buffer (voxel-row stride ld_space elements): the up-sampled map is written
@@ -559,6 +561,16 @@ int64_t ucfvit_conv3d_wgrad_size(int64_t Cin, int64_t Cout, int ksize);
 int64_t ucfvit_conv3d_wgrad_workspace(int64_t B, int64_t X, int64_t Y, int64_t Z, int64_t Cin, int64_t Cout, int ksize);
 int ucfvit_conv3d_wgrad(const void* x, const void* dy, float* dw_packed, void* workspace, int64_t B, int64_t X, int64_t Y, int64_t Z,
                         int64_t Cin, int64_t Cout, int ksize, void* stream);
+/* which kernel ucfvit_conv3d_fwd (pass = 0; the data gradient is the same call) or ucfvit_conv3d_wgrad (pass = 1, which ignores has_bias,
+ * out_dtype, ldy and cout_store) would run for these arguments, as text.  mode = the value of the test hook UCFVIT_CONV_STRIP to assume
+ * (0 .. 3), or -1 for this process's own.  Forward: "tile", "strip-fast", "strip-branching" (the column kernel with its branch-free or its
+ * branching memory operations; "-share" appended for 3x3x3 with 16 input channels) or "mc1" / "mc2" / "mc4" (the multi-chunk column kernel
+ * and its z tiles), then the instantiation and the statistics rows per batch element (0: no statistics epilogue), e.g.
+ * "strip-fast-share cpc16 ks3 nb1 4x8 depth2 rows8".  Weight gradient: "wgrad cpc32 ks3 mb2 n_wg24 tiles_per_wg2 slots1 n_out884736"
+ * (n_wg workgroups, each walking tiles_per_wg tiles and writing `slots` partials of n_out floats).  Host only, no HIP call; returns the
+ * length (the text is cut to cap - 1 characters), or < 0 for arguments the entry points refuse */
+int ucfvit_conv3d_route(int pass, int64_t B, int64_t X, int64_t Y, int64_t Z, int64_t Cin, int64_t Cout, int ksize, int has_bias, int out_dtype,
+                        int64_t ldy, int64_t cout_store, int mode, char* out, int64_t cap);
 int ucfvit_depth_to_space2(const void* src, void* dst, int64_t B, int64_t Xi, int64_t Yi, int64_t Zi, int64_t C, int64_t ld_space, int to_space,
                            const void* skip, int64_t Cs, void* stream);
 int ucfvit_pad_channels8(const float* src, void* dst, int64_t B, int64_t C, int64_t S, void* stream);

@@ -3,10 +3,12 @@ through UCF_VIT._hip.ops and UCF_VIT._hip.conv.  The references never call the p
 zero-padded float64 volume, each times the tap's [Cin, Cout] matrix (_conv64); a weight gradient is the matching 27 products (_wgrad64).
 U = 2^-24 (fp32 unit roundoff), UB = 2^-8 (bf16).  All operands are drawn on the CPU (the same values with and without a GPU).
 
-Routing (_plan restates fwd_plan, dispatch_fwd and the `fast` predicate of launch_fwd_strip; _wplan restates wgrad_plan).  Asserted against
+Routing (_plan restates conv_fwd_route of csrc/conv_route.h, _wplan restates conv_wgrad_route; neither calls the library).  Asserted against
 the library for every case under every UCFVIT_CONV_STRIP value: ucfvit_conv3d_fwd_stats_rows is > 0 exactly when the kind is 1 or 2 and
 equals ceil(X/TX) ceil(Y/TY) 4 for the restated tile, ucfvit_conv3d_wgrad_workspace equals n_wg SLOTS n_out 4 with the restated n_wg
-(test_conv_route_queries_every_mode: one child per value, the hook is read once per process; test_conv_wgrad_plan_...).  Branches and the
+(test_conv_route_queries_every_mode: one child per value, the hook is read once per process; test_conv_wgrad_plan_...); the text of
+ucfvit_conv3d_route, which takes the hook value as an argument, equals the restated plan for every (case, epilogue, mode) in one process
+(test_conv_route_text_equals_the_restated_plan, test_conv_wgrad_route_text_equals_the_restated_plan).  Branches and the
 cases that reach them (test_conv_table_reaches_every_branch asserts this list from the restated plans):
     tile  conv_fwd_kernel            hook 0 and the default at small sizes: every entry of the table.  CPC 8 / 16 / 32 x KS 3 / 1 (the 17 channel
                                      pairs of _COMBOS), NB 4 / 2 / 1 (Cout 64, 32, 16 and 48), multi-chunk Cin 64 / 128 / 256 (the "mc" shapes and two
@@ -77,7 +79,7 @@ Forced modes: UCFVIT_CONV_STRIP = 0, 2, 3 each run the forced table (48 cases, b
 checked, no further child after a failure); the children save the outputs of four epilogues, the parent compares the Tier 1 ones with the
 float64 reference computed in the parent and the real-valued ones with each other.
 
-Finding.  The hook value 3 could not do what the source said: fwd_plan tested strip_mode() == 2, so under 3 the column kernels were chosen by
+Finding.  The hook value 3 could not do what the source said: the forward plan (conv_fwd_route today) tested the hook for == 2, so under 3 the column kernels were chosen by
 size as under the default, and no shape of a test's size reached conv_fwd_strip_kernel<FAST = false> that way.  csrc/conv3d.hip now forces
 the column kernels for 2 and 3 alike (the default and 0 are unchanged).  With that, the branching kernel passed both tiers at first run,
 bit-identical to the FAST one.  No defect found in any kernel: no ratio above 1, no sentinel touched, no NaN.
@@ -239,7 +241,7 @@ class Plan:
 
 
 def _plan(c, e, mode):
-    """fwd_plan + dispatch_fwd + the `fast` predicate of launch_fwd_strip, restated"""
+    """conv_fwd_route of csrc/conv_route.h, restated"""
     cpc, nb16 = min(c.cin, 32), c.cout // 16
     nch = c.cin // cpc
     cs, ldy = e.cs_of(c), e.ld_of(c)
@@ -295,7 +297,7 @@ class WC:
 
 
 def _wplan(c):
-    """wgrad_plan restated -> dict(MB, cpc, tiles, n_wg, tpw, slots, n_out, d)"""
+    """conv_wgrad_route of csrc/conv_route.h restated -> dict(MB, cpc, tiles, n_wg, tpw, slots, n_out, d)"""
     kin, kout = c.kdims
     cpc = min(kin, 32)
     MB = 2 if kout % 32 == 0 else 1
@@ -820,7 +822,7 @@ def test_conv_wgrad_bounds(c):
 
 
 def test_conv_wgrad_plan_and_tiles_per_workgroup():
-    """CPU: the workspace query against the restated wgrad_plan on every case; the cases the table names for tiles_per_wg > 1 have it (n_wg
+    """CPU: the workspace query against the restated conv_wgrad_route on every case; the cases the table names for tiles_per_wg > 1 have it (n_wg
     from the QUERY below the tile count), the role-swapped calls hand the kernel the exchanged channel counts"""
     multi = []
     for c in WGRAD:
@@ -1188,6 +1190,77 @@ def test_conv_route_queries_every_mode(mode):
         assert got[1] == 2 and got[2] == 1                            # only the selection cases
     else:
         assert got[1] > 20 and got[2] >= 5
+
+
+def _route_text(pass_, B, X, Y, Z, cin, cout, ks, bias=False, out32=False, ldy=None, cs=None, mode=-1, cap=160):
+    """ucfvit_conv3d_route: pass 0 the forward launch of these arguments, 1 the weight gradient; mode = the hook value to assume, -1 the process's"""
+    import ctypes
+    from UCF_VIT._hip import lib
+    buf = ctypes.create_string_buffer(cap)
+    n = lib.load().ucfvit_conv3d_route(pass_, B, X, Y, Z, cin, cout, ks, int(bias), lib.F32 if out32 else lib.BF16, ldy or cout, cs or cout, mode, buf, cap)
+    assert 0 < n < cap and len(buf.value) == n, f"ucfvit_conv3d_route returned {n}: {lib.load().ucfvit_last_error()}"
+    return buf.value.decode()
+
+
+def _plan_text(c, e, mode):
+    """the restated plan in the words of ucfvit_conv3d_route; rows: the statistics rows of the plan's own kernel and tile"""
+    p = _plan(c, e, mode)
+    rows = _cdiv(c.X, p.TX) * _cdiv(c.Y, p.TY) * 4 if p.kind else 0
+    return f"{p.name} cpc{min(c.cin, 32)} ks{c.ks} nb{p.NB} {p.TX}x{p.TY} depth{p.depth} rows{rows}"
+
+
+def test_conv_route_text_equals_the_restated_plan():
+    """CPU, one process: for every case, every epilogue it runs and every hook value 0 .. 3 handed in as an argument, the library names the
+    kernel, CPC, KS, NB, tile, DEPTH and statistics rows that _plan restates; a dense bf16 launch has the rows of ucfvit_conv3d_fwd_stats_rows
+    as restated; mode -1 is this process's own hook value"""
+    seen = set()
+    for c in FWD:
+        for en in _epis(c):
+            e = EPIS[en]
+            for mode in range(4):
+                said = _route_text(0, *c.shape, c.cin, c.cout, c.ks, e.bias, e.out32, e.ld_of(c), e.cs_of(c), mode)
+                assert said == _plan_text(c, e, mode), f"{c.id} {en} mode {mode}: ucfvit_conv3d_route says '{said}', the restated plan '{_plan_text(c, e, mode)}'"
+                if not e.out32 and e.cs_of(c) == c.cout and e.ld_of(c) == c.cout:
+                    assert said.endswith(f" rows{_stats_rows(c, e.bias, mode)}"), (c.id, en, mode, said)
+                seen.add(said.split()[0])
+            assert _route_text(0, *c.shape, c.cin, c.cout, c.ks, e.bias, e.out32, e.ld_of(c), e.cs_of(c)) == _plan_text(c, e, _mode())
+    assert seen == {"tile", "strip-fast", "strip-fast-share", "strip-branching", "strip-branching-share", "mc1", "mc2", "mc4"}, seen
+
+
+def test_conv_wgrad_route_text_equals_the_restated_plan():
+    """CPU: for every weight-gradient case, with the channel counts the kernel sees (role-swapped ones included), the library names the MB,
+    n_wg, tiles_per_wg, slots and n_out that _wplan restates, and both size queries are fields of the same route"""
+    from UCF_VIT._hip import lib
+    L = lib.load()
+    for c in WGRAD:
+        (kin, kout), p = c.kdims, _wplan(c)
+        said = _route_text(1, c.B, c.X, c.Y, c.Z, kin, kout, c.ks)
+        want = f"wgrad cpc{p['cpc']} ks{c.ks} mb{p['MB']} n_wg{p['n_wg']} tiles_per_wg{p['tpw']} slots{p['slots']} n_out{p['n_out']}"
+        assert said == want, f"{c.id}: ucfvit_conv3d_route says '{said}', the restated plan '{want}'"
+        assert said == _route_text(1, c.B, c.X, c.Y, c.Z, kin, kout, c.ks, bias=True, out32=True, ldy=7, cs=99, mode=3)     # pass 1 ignores the epilogue
+        assert L.ucfvit_conv3d_wgrad_workspace(c.B, c.X, c.Y, c.Z, kin, kout, c.ks) == p["n_wg"] * p["slots"] * p["n_out"] * 4
+        assert L.ucfvit_conv3d_wgrad_size(kin, kout, c.ks) == p["n_out"]
+
+
+def test_conv_route_query_cuts_the_text_to_the_room_given():
+    """the length returned is the whole text's, the text is cut to cap - 1 characters and terminated, cap 0 writes nothing; arguments the
+    entry points refuse are an error"""
+    import ctypes
+    from UCF_VIT._hip import lib as L
+    lib = L.load()
+    args = (0, 2, 3, 9, 17, 16, 16, 3, 0, L.BF16, 16, 16, 2)
+    name = b"strip-fast-share cpc16 ks3 nb1 4x8 depth2 rows8"
+    assert _route_text(*args[:8], mode=2).encode() == name
+    for cap, want in ((4, b"str\0x"), (1, b"\0xxxx"), (len(name), name[:-1] + b"\0x"), (len(name) + 1, name + b"\0x")):
+        buf = ctypes.create_string_buffer(b"x" * 64, 64)
+        assert lib.ucfvit_conv3d_route(*args, buf, cap) == len(name)
+        assert buf.raw[:len(want)] == want, (cap, buf.raw)
+    buf = ctypes.create_string_buffer(b"x" * 64, 64)
+    assert lib.ucfvit_conv3d_route(*args, buf, 0) == len(name) and buf.raw == b"x" * 64
+    for bad in ((0, 2, 3, 9, 17, 24, 16, 3, 0, L.BF16, 16, 16, 2), (1, 2, 3, 9, 17, 16, 24, 3, 0, L.BF16, 16, 16, 2), (0, 2, 3, 9, 17, 16, 16, 3, 0, L.BF16, 16, 17, 2),
+                (2, 2, 3, 9, 17, 16, 16, 3, 0, L.BF16, 16, 16, 2), (0, 2, 3, 9, 17, 16, 16, 3, 0, L.BF16, 16, 16, 4)):
+        assert lib.ucfvit_conv3d_route(*bad, buf, 64) < 0 and b"ucfvit_conv3d_route" in lib.ucfvit_last_error()
+    assert buf.raw == b"x" * 64
 
 
 @pytest.mark.parametrize("part", range(4))

@@ -14,7 +14,7 @@ GEMM_SCHED_BYTES = 1024
 # loss-scaler state block (UCFVIT_GS_* of include/ucfvit_hip.h)
 GS_SCALE, GS_INV_SCALE, GS_FOUND_INF, GS_GROWTH_TRACKER, GS_APPLIED_STEPS, GS_SKIPPED_STEPS = 0, 1, 2, 3, 4, 5
 GS_GROWTH_FACTOR, GS_BACKOFF_FACTOR, GS_GROWTH_INTERVAL, GS_MIN_SCALE, GS_STATE_FLOATS = 6, 7, 8, 9, 16
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))  # .../ucf-vit_amd
 # UCFVIT_HIP_LIB: an alternative build of the same library (A/B measurements of kernel variants); never a non-HIP fallback
@@ -113,6 +113,7 @@ SIGNATURES = {
     "ucfvit_conv3d_wgrad_size": (_I64, [_I64, _I64, _I]),
     "ucfvit_conv3d_wgrad_workspace": (_I64, [_I64, _I64, _I64, _I64, _I64, _I64, _I]),
     "ucfvit_conv3d_wgrad": (c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I, _P]),
+    "ucfvit_conv3d_route": (c_int, [_I, _I64, _I64, _I64, _I64, _I64, _I64, _I, _I, _I, _I64, _I64, _I, c_char_p, _I64]),
     "ucfvit_depth_to_space2": (c_int, [_P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I, _P, _I64, _P]),
     "ucfvit_pad_channels8": (c_int, [_P, _P, _I64, _I64, _I64, _P]),
     "ucfvit_pad_rows8": (c_int, [_P, c_int, _P, _I64, _I64, _I64, _P]),

@@ -23,6 +23,7 @@
 //   (Cout/16) x (Cin/16) accumulator blocks spread over its 4 waves (7 taps each), and writes ONE partial per workgroup; the partials are
 //   folded by ucfvit_reduce_rows in a fixed order (deterministic, no atomics).
 #include "common.h"
+#include "conv_route.h"
 
 namespace {
 
@@ -34,10 +35,9 @@ __device__ __forceinline__ f32x4 mma(const frag_t& a, const frag_t& b, const f32
 }
 
 template <int CPC, int KS> struct CG {                // CPC = channels per contraction chunk (8, 16 or 32), KS = kernel size (3 or 1)
-    static constexpr int NT = KS * KS * KS;           // taps
+    static constexpr int NT = conv_taps(KS);          // taps
     static constexpr int PAD = KS / 2;
-    static constexpr int TPS = 32 / CPC;              // taps folded into one 32-wide MFMA step
-    static constexpr int NTS = (NT + TPS - 1) / TPS;  // MFMA steps per chunk (KS 3: 27, 14, 7; KS 1: 1)
+    static constexpr int NTS = conv_steps(CPC, KS);   // MFMA steps per chunk, 32 / CPC taps folded into each (KS 3: 27, 14, 7; KS 1: 1)
     static constexpr int VS = CPC * 2;                // bytes per voxel in the LDS image
     static constexpr int PPV = VS / 16;               // 16-byte pieces per voxel
 };
@@ -69,6 +69,39 @@ __device__ __forceinline__ void stage_halo(char* halo, const bf16* __restrict__ 
         *reinterpret_cast<u32x4*>(halo + hv * VS + piece * 16) =
             load_voxel(x, g, b, x0 + hx - PAD, y0 + hy - PAD, z0 + hz - PAD, g.Cin, ch0 + piece * 8);
     }
+}
+
+// 16-byte piece p of the weight slab [NTS][CB][32] bf16 of channel chunk cc, output channels co0 .. co0 + CB - 1; its place in LDS is byte 16 p
+template <int NTS, int CB> __device__ __forceinline__ u32x4 wslab_piece(const bf16* wp, int Cout, int cc, int co0, int p) {
+    const int piece = p & 3, row = (p >> 2) % CB, ts = (p >> 2) / CB;
+    return *reinterpret_cast<const u32x4*>(wp + ((int64_t)(cc * NTS + ts) * Cout + co0 + row) * 32 + piece * 8);
+}
+
+// Step ts of a staged chunk: the byte offset, in the halo image of a tile with HY x HZ voxel rows, of the 8 contraction values lane (li, lg)
+// multiplies for the tile's first voxel row — voxel li of the tap, channel bytes chb .. chb + 15
+template <int CPC, int KS, int HY, int HZ> __device__ __forceinline__ int tap_offset(int ts, int li, int lg) {
+    typedef CG<CPC, KS> G;
+    int tap, chb;
+    if (CPC == 32) {
+        tap = ts;
+        chb = lg * 16;
+    } else if (CPC == 16) {
+        tap = 2 * ts + (lg >> 1);
+        chb = (lg & 1) * 16;
+    } else {
+        tap = 4 * ts + lg;
+        chb = 0;
+    }
+    if (tap > G::NT - 1) tap = G::NT - 1;               // padding step: its weights are zero, read any staged voxel
+    const int dx = KS == 3 ? tap / 9 : 0, dy = KS == 3 ? (tap / 3) % 3 : 0, dz = KS == 3 ? tap % 3 : 0;
+    return ((dx * HY + dy) * HZ + dz + li) * G::VS + chb;
+}
+
+// one stored (rounded) output o of a channel into the channel's sums relative to its shift
+__device__ __forceinline__ void stats_add(float o, float shift, float& s1, float& s2) {
+    const float q = o - shift;
+    s1 += q;
+    s2 = fmaf(q, q, s2);
 }
 
 __device__ __forceinline__ void decode_tile(const ConvGeo& g, int t, int& b, int& ix, int& iy, int& iz) {
@@ -124,6 +157,7 @@ __global__ __launch_bounds__(CT) void conv_fwd_kernel(const bf16* __restrict__ x
     for (int cc = 0; cc < nchunks; ++cc) {
         if (cc) __syncthreads();
         stage_halo<CPC, PAD, HX, HY, HZ>(halo, x, g, b, x0, y0, z0, cc * CPC, tid);
+        // (this kernel keeps its own copy of wslab_piece and tap_offset: calling them changes its instruction schedule)
         for (int p = tid; p < G::NTS * CB * 4; p += CT) {
             const int piece = p & 3, row = (p >> 2) % CB, ts = (p >> 2) / CB;
             *reinterpret_cast<u32x4*>(wl + p * 16) =
@@ -229,8 +263,8 @@ __global__ __launch_bounds__(CT) void conv_fwd_strip_kernel(const bf16* __restri
     // (Measured at 512 x 512 x 128, B = 2: the 16 -> 16 full-resolution layer 1567 -> 1440 us, 16 -> 32 3154 -> 3022; with 32 input channels
     // — two MFMAs per fragment already — 544 -> 569 us, so those keep one fragment per (row, tap).)
     constexpr bool SHARE = KS == 3 && CPC == 16 && RPW <= TY && TY % RPW == 0;
-    constexpr int NST = CPC == 16 ? 5 : 9;              // step types (dy-free), SHARE only
-    if constexpr (SHARE && CPC == 16) {
+    constexpr int NST = 5;                              // step types (dy-free), SHARE only
+    if constexpr (SHARE) {
         for (int p = tid; p < NST * 3 * CB * 4; p += CT) {
             const int piece = p & 3, row = (p >> 2) % CB, slot = (p >> 2) / CB, st = slot / 3, dy = slot % 3, second = piece >> 1;
             // (dx, dz) of the two taps of step type st: 0x(dx << 2 | dz) per half
@@ -244,10 +278,7 @@ __global__ __launch_bounds__(CT) void conv_fwd_strip_kernel(const bf16* __restri
             *reinterpret_cast<u32x4*>(wl + p * 16) = v;
         }
     } else {
-        for (int p = tid; p < G::NTS * CB * 4; p += CT) {
-            const int piece = p & 3, row = (p >> 2) % CB, ts = (p >> 2) / CB;
-            *reinterpret_cast<u32x4*>(wl + p * 16) = *reinterpret_cast<const u32x4*>(wp + ((int64_t)ts * g.Cout + co0 + row) * 32 + piece * 8);
-        }
+        for (int p = tid; p < G::NTS * CB * 4; p += CT) *reinterpret_cast<u32x4*>(wl + p * 16) = wslab_piece<G::NTS, CB>(wp, g.Cout, 0, co0, p);
     }
     // this thread's pieces of a halo: fixed (hx, hy, hz, piece) for every z tile
     int hoff[NPT], hxy[NPT], hzz[NPT];
@@ -293,7 +324,7 @@ __global__ __launch_bounds__(CT) void conv_fwd_strip_kernel(const bf16* __restri
 #pragma unroll
         for (int e = 0; e < 4; ++e) bv[nb][e] = (FAST && bias) ? bias[co0 + nb * 16 + lg * 4 + e] : 0.f;
     // stats (optional): per-channel sum and sum of squares of the ROUNDED outputs of this column, per wave — the instance-norm statistics of the
-    // layer's output without a pass over it ([column * 4 + wave][2][Cout] partials, folded by ucfvit_instnorm_cl_stats_fold)
+    // layer's output without a pass over it ([column * 4 + wave][3][Cout] partials, folded by ucfvit_instnorm_cl_stats_fold)
     float st1[NB][4], st2[NB][4], shf[NB][4];
     float cnt = 0.f;
 #pragma unroll
@@ -342,41 +373,23 @@ __global__ __launch_bounds__(CT) void conv_fwd_strip_kernel(const bf16* __restri
                 }
             }
         }
-        f32x4 acc[RPW][NB];
-#pragma unroll
-        for (int r = 0; r < RPW; ++r)
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb) acc[r][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+        f32x4 acc[RPW][NB] = {};
         if constexpr (SHARE) {
             const int xl = (wave * RPW) / TY, yl0 = (wave * RPW) % TY;
 #pragma unroll
             for (int st = 0; st < NST; ++st) {
                 frag_t a[3][NB];
-                int dx, dz, chb;
-                if (CPC == 32) {
-                    dx = st / 3;
-                    dz = st % 3;
-                    chb = lg * 16;
+                // this lane's half of the step: lanes lg 0, 1 the first tap, lg 2, 3 the second (the padding half reads the first tap's voxels
+                // against zero weights)
+                const int second = lg >> 1;
+                const int dxdz = st == 0 ? (second ? 0x1 : 0x0) : st == 1 ? (second ? 0x5 : 0x4) : st == 2 ? (second ? 0x9 : 0x8)
+                               : st == 3 ? (second ? 0x6 : 0x2) : 0xA;
+                const int dx = dxdz >> 2, dz = dxdz & 3, chb = (lg & 1) * 16;
 #pragma unroll
-                    for (int dy = 0; dy < 3; ++dy)
+                for (int dy = 0; dy < 3; ++dy)
 #pragma unroll
-                        for (int nb = 0; nb < NB; ++nb)
-                            a[dy][nb] = *reinterpret_cast<const frag_t*>(wl + (((9 * dx + 3 * dy + dz) * CB + nb * 16 + li) * 64 + lg * 16));
-                } else {
-                    // this lane's half of the step: lanes lg 0, 1 the first tap, lg 2, 3 the second (the padding half reads the first tap's voxels
-                    // against zero weights)
-                    const int second = lg >> 1;
-                    const int dxdz = st == 0 ? (second ? 0x1 : 0x0) : st == 1 ? (second ? 0x5 : 0x4) : st == 2 ? (second ? 0x9 : 0x8)
-                                   : st == 3 ? (second ? 0x6 : 0x2) : 0xA;
-                    dx = dxdz >> 2;
-                    dz = dxdz & 3;
-                    chb = (lg & 1) * 16;
-#pragma unroll
-                    for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-                        for (int nb = 0; nb < NB; ++nb)
-                            a[dy][nb] = *reinterpret_cast<const frag_t*>(wl + (((st * 3 + dy) * CB + nb * 16 + li) * 64 + lg * 16));
-                }
+                    for (int nb = 0; nb < NB; ++nb)
+                        a[dy][nb] = *reinterpret_cast<const frag_t*>(wl + (((st * 3 + dy) * CB + nb * 16 + li) * 64 + lg * 16));
                 const int boff = (((dx + xl) * HY + yl0) * HZ + dz + li) * G::VS + chb;
 #pragma unroll
                 for (int j = 0; j < RPW + 2; ++j) {
@@ -397,20 +410,7 @@ __global__ __launch_bounds__(CT) void conv_fwd_strip_kernel(const bf16* __restri
             frag_t a[NB];
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb) a[nb] = *reinterpret_cast<const frag_t*>(wl + ((ts * CB + nb * 16 + li) * 64 + lg * 16));
-            int tap, chb;
-            if (CPC == 32) {
-                tap = ts;
-                chb = lg * 16;
-            } else if (CPC == 16) {
-                tap = 2 * ts + (lg >> 1);
-                chb = (lg & 1) * 16;
-            } else {
-                tap = 4 * ts + lg;
-                chb = 0;
-            }
-            if (tap > G::NT - 1) tap = G::NT - 1;
-            const int dx = KS == 3 ? tap / 9 : 0, dy = KS == 3 ? (tap / 3) % 3 : 0, dz = KS == 3 ? tap % 3 : 0;
-            const int boff = ((dx * HY + dy) * HZ + dz + li) * G::VS + chb;
+            const int boff = tap_offset<CPC, KS, HY, HZ>(ts, li, lg);
 #pragma unroll
             for (int r = 0; r < RPW; ++r) {
                 const int row = wave * RPW + r, xl = row / TY, yl = row % TY;
@@ -450,11 +450,7 @@ __global__ __launch_bounds__(CT) void conv_fwd_strip_kernel(const bf16* __restri
                     else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rY, ob, 0, 0);
                     if (stats && valid) {
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            const float q = o.get(e) - shf[nb][e];
-                            st1[nb][e] += q;
-                            st2[nb][e] = fmaf(q, q, st2[nb][e]);
-                        }
+                        for (int e = 0; e < 4; ++e) stats_add(o.get(e), shf[nb][e], st1[nb][e], st2[nb][e]);
                     }
                 }
             }
@@ -482,11 +478,7 @@ __global__ __launch_bounds__(CT) void conv_fwd_strip_kernel(const bf16* __restri
                         *reinterpret_cast<Vec4<OutT>*>(yp + c) = o;
                         if (stats) {
 #pragma unroll
-                            for (int e = 0; e < 4; ++e) {
-                                const float q = o.get(e) - shf[nb][e];
-                                st1[nb][e] += q;
-                                st2[nb][e] = fmaf(q, q, st2[nb][e]);
-                            }
+                            for (int e = 0; e < 4; ++e) stats_add(o.get(e), shf[nb][e], st1[nb][e], st2[nb][e]);
                         }
                     } else {
 #pragma unroll
@@ -576,8 +568,7 @@ __global__ __launch_bounds__(CT) void conv3_fwd_mc_kernel(const bf16* __restrict
         for (int i = 0; i < NWT; ++i) {
             const int p = tid + i * CT;
             if (p < NWP) {
-                const int piece = p & 3, row = (p >> 2) % CB, ts = (p >> 2) / CB;
-                const u32x4 v = *reinterpret_cast<const u32x4*>(wp + ((int64_t)(cc * G::NTS + ts) * g.Cout + co0 + row) * 32 + piece * 8);
+                const u32x4 v = wslab_piece<G::NTS, CB>(wp, g.Cout, cc, co0, p);
                 if (WPRE)
                     wpre[i] = v;
                 else
@@ -585,13 +576,7 @@ __global__ __launch_bounds__(CT) void conv3_fwd_mc_kernel(const bf16* __restrict
             }
         }
     };
-    f32x4 acc[TZT][RPW][NB];
-#pragma unroll
-    for (int z = 0; z < TZT; ++z)
-#pragma unroll
-        for (int r = 0; r < RPW; ++r)
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb) acc[z][r][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 acc[TZT][RPW][NB] = {};
     fetch(0);
     if (WPRE) wfetch(0);
     for (int cc = 0; cc < nch; ++cc) {
@@ -617,8 +602,7 @@ __global__ __launch_bounds__(CT) void conv3_fwd_mc_kernel(const bf16* __restrict
                 frag_t a[NB];
 #pragma unroll
                 for (int nb = 0; nb < NB; ++nb) a[nb] = *reinterpret_cast<const frag_t*>(wl + ((ts * CB + nb * 16 + li) * 64 + lg * 16));
-                const int dx = ts / 9, dy = (ts / 3) % 3, dz = ts % 3;
-                const int boff = ((dx * HY + dy) * HZ + dz + li) * G::VS + lg * 16;
+                const int boff = tap_offset<32, 3, HY, HZ>(ts, li, lg);
 #pragma unroll
                 for (int r = 0; r < RPW; ++r) {
                     const int row = wave * RPW + r, xl = row / TY, yl = row % TY;
@@ -661,7 +645,7 @@ __global__ __launch_bounds__(CT) void conv3_fwd_mc_kernel(const bf16* __restrict
                     *reinterpret_cast<bf16x4*>(yp + nb * 16) = o;
                     if (stats) {
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) {
+                        for (int e = 0; e < 4; ++e) {           // (stats_add, kept in place: the call changes this kernel's schedule)
                             const float q = (float)o[e] - shf[nb][e];
                             st1[nb][e] += q;
                             st2[nb][e] = fmaf(q, q, st2[nb][e]);
@@ -682,7 +666,7 @@ __global__ __launch_bounds__(CT) void conv3_fwd_mc_kernel(const bf16* __restrict
 }
 
 // ---------------------------------------------------------------------------------------------------------------- weight gradient
-constexpr int TZW = 32;       // z extent of a weight-gradient tile = one 32-deep contraction step per (x, y) row
+constexpr int TZW = CONV_WGRAD_TZ;       // z extent of a weight-gradient tile = one 32-deep contraction step per (x, y) row
 
 // KS 3: wave w owns taps w, w + 4, ... (7 accumulator sets) and walks every (x, y) row of the tile; ONE partial per workgroup.
 // KS 1: there is one tap, so the waves split the rows instead (row % 4 == wave) and each writes its own partial (4 per workgroup).
@@ -860,99 +844,23 @@ template <typename S> __global__ __launch_bounds__(CT) void padrow8_kernel(const
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------- host
 int conv_check(const char* name, const void* x, const void* w, const void* y, int64_t B, int64_t X, int64_t Y, int64_t Z, int64_t Cin,
                int64_t Cout, int ksize) {
     UCF_CHECK_ARG(x && w && y, "%s: null pointer", name);
     UCF_CHECK_ARG(B > 0 && X > 0 && Y > 0 && Z > 0, "%s: empty volume", name);
     UCF_CHECK_ARG(B * X * Y * Z < (1ll << 31), "%s: more than 2^31 voxels", name);
-    UCF_CHECK_ARG(ksize == 1 || ksize == 3, "%s: kernel size must be 1 or 3 (got %d)", name, ksize);
-    UCF_CHECK_ARG(Cin == 8 || Cin == 16 || (Cin > 0 && Cin % 32 == 0), "%s: Cin must be 8, 16 or a multiple of 32 (got %lld)", name, (long long)Cin);
-    UCF_CHECK_ARG(Cout > 0 && Cout % 16 == 0, "%s: Cout must be a multiple of 16 (got %lld)", name, (long long)Cout);
+    UCF_CHECK_ARG(conv_ksize_ok(ksize), "%s: kernel size must be 1 or 3 (got %d)", name, ksize);
+    UCF_CHECK_ARG(conv_cin_ok(Cin), "%s: Cin must be 8, 16 or a multiple of 32 (got %lld)", name, (long long)Cin);
+    UCF_CHECK_ARG(conv_cout_ok(Cout), "%s: Cout must be a multiple of 16 (got %lld)", name, (long long)Cout);
     UCF_CHECK_ARG(ucf_is_aligned16(x) && ucf_is_aligned16(w) && ucf_is_aligned16(y), "%s: operands must be 16-byte aligned", name);
     return UCFVIT_OK;
 }
 
-template <int CPC, int NB, int TX, int TY, int KS, typename OutT>
-int launch_fwd(const bf16* x, const bf16* wp, const float* bias, OutT* y, ConvGeo g, hipStream_t s) {
-    typedef CG<CPC, KS> G;
-    g.tx = (g.X + TX - 1) / TX;
-    g.ty = (g.Y + TY - 1) / TY;
-    g.tz = (g.Z + 15) / 16;
-    const int64_t tiles = (int64_t)g.B * g.tx * g.ty * g.tz;
-    UCF_CHECK_ARG(tiles < (1ll << 31) && g.Cout / (16 * NB) < 65536, "ucfvit_conv3d_fwd: grid too large");
-    g.tiles = (int)tiles;
-    constexpr int SMEM = (TX + 2 * G::PAD) * (TY + 2 * G::PAD) * (16 + 2 * G::PAD) * G::VS + G::NTS * 16 * NB * 64;
-    static_assert(SMEM <= 160 * 1024, "LDS budget");
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute((const void*)conv_fwd_kernel<CPC, NB, TX, TY, KS, OutT>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-        attr_done = true;
-    }
-    hipLaunchKernelGGL((conv_fwd_kernel<CPC, NB, TX, TY, KS, OutT>), dim3(g.tiles, g.Cout / (16 * NB)), dim3(CT), SMEM, s, x, wp, bias, y, g);
-    UCF_LAUNCH_CHECK("ucfvit_conv3d_fwd");
-    return UCFVIT_OK;
-}
-
-static int strip_mode();
-
-template <int CPC, int NB, int TX, int TY, int KS, typename OutT, bool FAST, int DEPTH>
-int launch_fwd_strip_v(const bf16* x, const bf16* wp, const float* bias, OutT* y, const ConvGeo& g, float* stats, int64_t cols, hipStream_t s) {
-    typedef CG<CPC, KS> G;
-    constexpr int WSLOTS = (KS == 3 && CPC == 16) ? 15 : G::NTS;            // the dy-free step arrangement of conv_fwd_strip_kernel (SHARE)
-    constexpr int SMEM = (TX + 2 * G::PAD) * (TY + 2 * G::PAD) * (16 + 2 * G::PAD) * G::VS + WSLOTS * 16 * NB * 64;
-    static_assert(SMEM <= 160 * 1024, "LDS budget");
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute((const void*)conv_fwd_strip_kernel<CPC, NB, TX, TY, KS, OutT, FAST, DEPTH>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-        attr_done = true;
-    }
-    hipLaunchKernelGGL((conv_fwd_strip_kernel<CPC, NB, TX, TY, KS, OutT, FAST, DEPTH>), dim3((unsigned)cols, g.Cout / (16 * NB)), dim3(CT), SMEM, s, x, wp,
-                       bias, y, g, stats);
-    UCF_LAUNCH_CHECK("ucfvit_conv3d_fwd");
-    return UCFVIT_OK;
-}
-
-template <int CPC, int NB, int TX, int TY, int KS, typename OutT>
-int launch_fwd_strip(const bf16* x, const bf16* wp, const float* bias, OutT* y, ConvGeo g, float* stats, hipStream_t s) {
-    g.tx = (g.X + TX - 1) / TX;
-    g.ty = (g.Y + TY - 1) / TY;
-    g.tz = (g.Z + 15) / 16;
-    const int64_t cols = (int64_t)g.B * g.tx * g.ty;
-    UCF_CHECK_ARG(cols < (1ll << 31) && g.Cout / (16 * NB) < 65536, "ucfvit_conv3d_fwd: grid too large");
-    g.tiles = (int)cols;
-    // the branch-free form (see conv_fwd_strip_kernel): 4-channel aligned output rows, a batch element's input and output below 4 GB
-    const int64_t vox = (int64_t)g.X * g.Y * g.Z, lim = (1ll << 32) - 64;
-    const bool fast = (g.ldy & 3) == 0 && (g.cout_store & 3) == 0 && vox * g.Cin * 2 < lim && vox * g.ldy * (int64_t)sizeof(OutT) < lim && strip_mode() != 3;
-    if (fast) {
-        if constexpr (CPC <= 16) return launch_fwd_strip_v<CPC, NB, TX, TY, KS, OutT, true, 2>(x, wp, bias, y, g, stats, cols, s);
-        else return launch_fwd_strip_v<CPC, NB, TX, TY, KS, OutT, true, 1>(x, wp, bias, y, g, stats, cols, s);
-    }
-    return launch_fwd_strip_v<CPC, NB, TX, TY, KS, OutT, false, 1>(x, wp, bias, y, g, stats, cols, s);
-}
-
-template <int TZT>
-int launch_fwd_mc(const bf16* x, const bf16* wp, bf16* y, ConvGeo g, float* stats, hipStream_t s) {
-    g.tx = (g.X + 1) / 2;
-    g.ty = (g.Y + 7) / 8;
-    g.tz = TZT;
-    const int64_t cols = (int64_t)g.B * g.tx * g.ty;
-    UCF_CHECK_ARG(cols < (1ll << 31) && g.Cout / 32 < 65536, "ucfvit_conv3d_fwd: grid too large");
-    g.tiles = (int)cols;
-    constexpr int SMEM = 4 * 10 * 18 * 64 + 27 * 32 * 64;
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute((const void*)conv3_fwd_mc_kernel<TZT>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-        attr_done = true;
-    }
-    hipLaunchKernelGGL((conv3_fwd_mc_kernel<TZT>), dim3((unsigned)cols, g.Cout / 32), dim3(CT), SMEM, s, x, wp, y, g, stats);
-    UCF_LAUNCH_CHECK("ucfvit_conv3d_fwd");
-    return UCFVIT_OK;
-}
-
 // UCFVIT_CONV_STRIP=0|2|3 — a TEST hook (tests/test_conv3d.py runs every shape through both kernel families and compares them bit for bit;
-// tests/test_conv3d_ops.py runs its case table under 0, 2 and 3 against float64): 0 never, 1 (default) when the (x, y) columns fill the chip,
-// 2 whenever the column kernel applies, 3 as 2 with the branching (non-FAST) memory operations.  Read once (thread-safe static).
-static int strip_mode() {
+// tests/test_conv3d_ops.py runs its case table under 0, 2 and 3 against float64): the `mode` of conv_fwd_route (conv_route.h), 1 by default.
+// Read once (thread-safe static), and only here: the entry points hand it to the route.
+int strip_mode() {
     static const int flag = [] {
         const char* e = getenv("UCFVIT_CONV_STRIP");
         return (e && e[0] >= '0' && e[0] <= '3') ? e[0] - '0' : 1;
@@ -960,115 +868,64 @@ static int strip_mode() {
     return flag;
 }
 
-// which forward kernel serves a launch: 0 = one tile per workgroup, 1 = single-chunk column kernel, 2 = multi-chunk column kernel; TX, TY = its tile
-struct FwdPlan {
-    int kind, TX, TY;
-};
-static FwdPlan fwd_plan(const ConvGeo& g, int ksize, bool has_bias, bool out_bf16) {
-    const int cpc = g.Cin < 32 ? g.Cin : 32, nb16 = g.Cout / 16;
-    if (cpc == 32 && ksize == 3 && out_bf16 && g.Cin > 32 && !has_bias && g.Cout % 32 == 0 && g.cout_store == g.Cout && g.ldy == g.Cout && strip_mode() &&
-        (g.Z == 16 || g.Z == 32 || g.Z == 64)) {
-        const int64_t wgs = (int64_t)g.B * ((g.X + 1) / 2) * ((g.Y + 7) / 8) * (g.Cout / 32);
-        if (strip_mode() >= 2 || wgs >= 512) return FwdPlan{2, 2, 8};
+// the one launch: the kernel's dynamic LDS limit raised once, the launch, its check
+template <auto Kernel, typename... Args>
+int conv_launch(const char* who, int64_t gx, int64_t gy, int smem, hipStream_t s, Args... args) {
+    static bool attr_done = false;
+    if (!attr_done) {
+        (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+        attr_done = true;
     }
-    if (g.Cin == cpc && g.Z > 16 && strip_mode()) {
-        const int64_t cols = (int64_t)g.B * ((g.X + 1) / 2) * ((g.Y + 7) / 8);
-        if (strip_mode() >= 2 || cols * (nb16 % 4 == 0 ? nb16 / 4 : nb16 % 2 == 0 ? nb16 / 2 : nb16) >= 512) {
-            if (nb16 % 4 == 0) return FwdPlan{1, 2, 4};
-            if (nb16 % 2 == 0 || cpc == 32) return FwdPlan{1, 2, 8};      // (CPC 32, NB 1): the 4 x 8 tile's prefetch would not fit in registers
-            return FwdPlan{1, 4, 8};
-        }
-    }
-    return FwdPlan{0, 0, 0};
+    hipLaunchKernelGGL(Kernel, dim3((unsigned)gx, (unsigned)gy), dim3(CT), smem, s, args...);
+    UCF_LAUNCH_CHECK(who);
+    return UCFVIT_OK;
+}
+
+// CONV_SWITCH: the runtime (Cin, ksize) of a route as the compile-time (CPC_, KS_) of the statement it is given
+#define CONV_SWITCH_CPC(CIN, ...)                                        \
+    if ((CIN) == 8) { constexpr int CPC_ = 8; __VA_ARGS__ }              \
+    else if ((CIN) == 16) { constexpr int CPC_ = 16; __VA_ARGS__ }       \
+    else { constexpr int CPC_ = 32; __VA_ARGS__ }
+#define CONV_SWITCH(CIN, KSIZE, ...)                                                    \
+    do {                                                                                \
+        if ((KSIZE) == 3) { constexpr int KS_ = 3; CONV_SWITCH_CPC(CIN, __VA_ARGS__) }  \
+        else { constexpr int KS_ = 1; CONV_SWITCH_CPC(CIN, __VA_ARGS__) }               \
+    } while (0)
+
+// the route's (kind, nb, fast, tzt) as template arguments.  TY and the column kernel's TX are those conv_fwd_route names for (CPC, NB)
+template <int CPC, int NB, int TY, int KS, typename OutT>
+int run_fwd_nb(const ConvFwdRoute& r, const bf16* x, const bf16* wp, const float* bias, OutT* y, const ConvGeo& g, float* stats, hipStream_t s) {
+    constexpr int STX = NB == 1 && CPC < 32 ? 4 : 2, DEPTH = CPC <= 16 ? 2 : 1;
+    static_assert(conv_fwd_smem(CPC, KS, NB, STX, TY, KS == 3 && CPC == 16) <= 160 * 1024, "LDS budget");
+    const char* who = "ucfvit_conv3d_fwd";
+    if (r.kind == CK_TILE) return conv_launch<conv_fwd_kernel<CPC, NB, 2, TY, KS, OutT>>(who, r.gx, r.gy, r.smem, s, x, wp, bias, y, g);
+    if (r.fast) return conv_launch<conv_fwd_strip_kernel<CPC, NB, STX, TY, KS, OutT, true, DEPTH>>(who, r.gx, r.gy, r.smem, s, x, wp, bias, y, g, stats);
+    return conv_launch<conv_fwd_strip_kernel<CPC, NB, STX, TY, KS, OutT, false, 1>>(who, r.gx, r.gy, r.smem, s, x, wp, bias, y, g, stats);
 }
 
 template <int CPC, int KS, typename OutT>
-int dispatch_fwd(const bf16* x, const bf16* wp, const float* bias, OutT* y, const ConvGeo& g, float* stats, hipStream_t s) {
-    const int nb16 = g.Cout / 16;
-    const FwdPlan pl = fwd_plan(g, KS, bias != nullptr, sizeof(OutT) == 2);
+int run_fwd(const ConvFwdRoute& r, const bf16* x, const bf16* wp, const float* bias, OutT* y, const ConvGeo& g, float* stats, hipStream_t s) {
     if constexpr (CPC == 32 && KS == 3 && sizeof(OutT) == 2) {
-        if (pl.kind == 2) {
-            if (g.Z == 16) return launch_fwd_mc<1>(x, wp, (bf16*)y, g, stats, s);
-            if (g.Z == 32) return launch_fwd_mc<2>(x, wp, (bf16*)y, g, stats, s);
-            return launch_fwd_mc<4>(x, wp, (bf16*)y, g, stats, s);
+        if (r.kind == CK_MC) {
+            const char* who = "ucfvit_conv3d_fwd";
+            if (r.tzt == 1) return conv_launch<conv3_fwd_mc_kernel<1>>(who, r.gx, r.gy, r.smem, s, x, wp, y, g, stats);
+            if (r.tzt == 2) return conv_launch<conv3_fwd_mc_kernel<2>>(who, r.gx, r.gy, r.smem, s, x, wp, y, g, stats);
+            return conv_launch<conv3_fwd_mc_kernel<4>>(who, r.gx, r.gy, r.smem, s, x, wp, y, g, stats);
         }
     }
-    if (pl.kind == 1) {
-        if (nb16 % 4 == 0) return launch_fwd_strip<CPC, 4, 2, 4, KS, OutT>(x, wp, bias, y, g, stats, s);
-        if (nb16 % 2 == 0) return launch_fwd_strip<CPC, 2, 2, 8, KS, OutT>(x, wp, bias, y, g, stats, s);
-        if constexpr (CPC == 32)
-            return launch_fwd_strip<CPC, 1, 2, 8, KS, OutT>(x, wp, bias, y, g, stats, s);
-        else
-            return launch_fwd_strip<CPC, 1, 4, 8, KS, OutT>(x, wp, bias, y, g, stats, s);
-    }
-    UCF_CHECK_ARG(!stats, "ucfvit_conv3d_fwd: this launch has no statistics epilogue (ask ucfvit_conv3d_fwd_stats_rows first)");
-    if (nb16 % 4 == 0) return launch_fwd<CPC, 4, 2, 4, KS, OutT>(x, wp, bias, y, g, s);
-    if (nb16 % 2 == 0) return launch_fwd<CPC, 2, 2, 8, KS, OutT>(x, wp, bias, y, g, s);
-    return launch_fwd<CPC, 1, 2, 8, KS, OutT>(x, wp, bias, y, g, s);
+    if (r.nb == 4) return run_fwd_nb<CPC, 4, 4, KS, OutT>(r, x, wp, bias, y, g, stats, s);
+    if (r.nb == 2) return run_fwd_nb<CPC, 2, 8, KS, OutT>(r, x, wp, bias, y, g, stats, s);
+    return run_fwd_nb<CPC, 1, 8, KS, OutT>(r, x, wp, bias, y, g, stats, s);
 }
 
-template <int CPC, int MB, int TX, int TY, int KS> struct WG {
-    static constexpr int NBK = CPC >= 16 ? CPC / 16 : 1;
-    static constexpr int PB = 16 * MB * 16 * NBK;
-    static constexpr int PAD = KS / 2;
-    static constexpr int SMEM = TX * TY * TZW * 32 * MB + (TX + 2 * PAD) * (TY + 2 * PAD) * (TZW + 2 * PAD) * CPC * 2 + 64;
-    static constexpr int SLOTS = KS == 3 ? 1 : 4;          // partials per workgroup
-};
-
-constexpr int64_t WGRAD_PART_FLOATS = 32ll << 20;      // cap of the partial-sum scratch (128 MiB)
-
-// geometry shared by the workspace query and the launch
-template <int CPC, int MB, int TX, int TY, int KS>
-void wgrad_plan(ConvGeo& g, int& n_wg, int& tiles_per_wg, int& gy, int64_t& n_out) {
-    typedef WG<CPC, MB, TX, TY, KS> W;
-    g.tx = (g.X + TX - 1) / TX;
-    g.ty = (g.Y + TY - 1) / TY;
-    g.tz = (g.Z + TZW - 1) / TZW;
-    g.tiles = g.B * g.tx * g.ty * g.tz;
-    gy = (g.Cin / CPC) * (g.Cout / (16 * MB));
-    n_out = (int64_t)gy * CG<CPC, KS>::NT * W::PB;
-    int64_t cap = WGRAD_PART_FLOATS / (n_out * W::SLOTS);
-    if (cap < 1) cap = 1;
-    if (cap > 1024) cap = 1024;
-    n_wg = (int)(g.tiles < cap ? g.tiles : cap);
-    tiles_per_wg = (g.tiles + n_wg - 1) / n_wg;
-    n_wg = (g.tiles + tiles_per_wg - 1) / tiles_per_wg;
+// text into out, cut to cap - 1 characters and terminated; returns the length of the whole text
+int conv_text(const char* text, char* out, int64_t cap) {
+    int n = 0;
+    for (; text[n]; ++n)
+        if (n < cap - 1) out[n] = text[n];
+    if (cap > 0) out[n < cap - 1 ? n : cap - 1] = 0;
+    return n;
 }
-
-template <int CPC, int MB, int TX, int TY, int KS>
-int launch_wgrad(const bf16* x, const bf16* dy, float* dw, float* ws, ConvGeo g, hipStream_t s) {
-    typedef WG<CPC, MB, TX, TY, KS> W;
-    int n_wg, tpw, gy;
-    int64_t n_out;
-    wgrad_plan<CPC, MB, TX, TY, KS>(g, n_wg, tpw, gy, n_out);
-    constexpr int SMEM = W::SMEM;
-    static_assert(SMEM <= 160 * 1024, "LDS budget");
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute((const void*)conv_wgrad_kernel<CPC, MB, TX, TY, KS>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-        attr_done = true;
-    }
-    hipLaunchKernelGGL((conv_wgrad_kernel<CPC, MB, TX, TY, KS>), dim3(n_wg, gy), dim3(CT), SMEM, s, x, dy, ws, g, tpw);
-    UCF_LAUNCH_CHECK("ucfvit_conv3d_wgrad");
-    return ucfvit_reduce_rows(ws, dw, (int64_t)n_wg * W::SLOTS, n_out, 0, s);
-}
-
-// which instantiation serves (Cin, Cout):  CPC = min(Cin, 32);  forward NB = largest of 4, 2, 1 dividing Cout / 16;  weight gradient MB = 2
-// when Cout % 32 == 0
-#define CONV_SWITCH(CIN, KSIZE, ...)                                         \
-    do {                                                                     \
-        if ((KSIZE) == 3) {                                                  \
-            constexpr int KS_ = 3;                                           \
-            if ((CIN) == 8) { constexpr int CPC_ = 8; __VA_ARGS__ }          \
-            else if ((CIN) == 16) { constexpr int CPC_ = 16; __VA_ARGS__ }   \
-            else { constexpr int CPC_ = 32; __VA_ARGS__ }                    \
-        } else {                                                             \
-            constexpr int KS_ = 1;                                           \
-            if ((CIN) == 8) { constexpr int CPC_ = 8; __VA_ARGS__ }          \
-            else if ((CIN) == 16) { constexpr int CPC_ = 16; __VA_ARGS__ }   \
-            else { constexpr int CPC_ = 32; __VA_ARGS__ }                    \
-        }                                                                    \
-    } while (0)
 
 }  // namespace
 
@@ -1079,58 +936,76 @@ extern "C" int ucfvit_conv3d_fwd(const void* x, const void* w_packed, const floa
     if (int rc = conv_check("ucfvit_conv3d_fwd", x, w_packed, y, B, X, Y, Z, Cin, Cout, ksize)) return rc;
     UCF_CHECK_ARG(cout_store > 0 && cout_store <= Cout && ldy >= cout_store && ldy < (1ll << 31), "ucfvit_conv3d_fwd: need 0 < cout_store <= Cout, ldy >= cout_store");
     UCF_CHECK_ARG(out_dtype == UCFVIT_BF16 || out_dtype == UCFVIT_F32, "ucfvit_conv3d_fwd: bad out_dtype %d", out_dtype);
-    ConvGeo g{(int)B, (int)X, (int)Y, (int)Z, (int)Cin, (int)Cout, 0, 0, 0, 0, (int)ldy, (int)cout_store, accumulate ? 1 : 0};
-    hipStream_t s = (hipStream_t)stream;
     UCF_CHECK_ARG(!stats_partial || (out_dtype == UCFVIT_BF16 && !accumulate && cout_store == Cout && ldy == Cout),
                   "ucfvit_conv3d_fwd: statistics need a dense bf16 output without accumulation");
+    const ConvFwdRoute r = conv_fwd_route(B, X, Y, Z, Cin, Cout, ksize, bias != nullptr, out_dtype, ldy, cout_store, strip_mode());
+    UCF_CHECK_ARG(!stats_partial || r.stats_rows, "ucfvit_conv3d_fwd: this launch has no statistics epilogue (ask ucfvit_conv3d_fwd_stats_rows first)");
+    UCF_CHECK_ARG(!r.grid_too_large, "ucfvit_conv3d_fwd: grid too large");
+    const ConvGeo g{(int)B, (int)X, (int)Y, (int)Z, (int)Cin, (int)Cout, r.tx, r.ty, r.tz, (int)r.gx, (int)ldy, (int)cout_store, accumulate ? 1 : 0};
+    hipStream_t s = (hipStream_t)stream;
     CONV_SWITCH(Cin, ksize, {
-        if (out_dtype == UCFVIT_BF16) return dispatch_fwd<CPC_, KS_, bf16>((const bf16*)x, (const bf16*)w_packed, bias, (bf16*)y, g, stats_partial, s);
-        return dispatch_fwd<CPC_, KS_, float>((const bf16*)x, (const bf16*)w_packed, bias, (float*)y, g, stats_partial, s);
+        if (out_dtype == UCFVIT_BF16) return run_fwd<CPC_, KS_, bf16>(r, (const bf16*)x, (const bf16*)w_packed, bias, (bf16*)y, g, stats_partial, s);
+        return run_fwd<CPC_, KS_, float>(r, (const bf16*)x, (const bf16*)w_packed, bias, (float*)y, g, stats_partial, s);
     });
     return UCFVIT_OK;
 }
 
-// rows per batch element of the statistics partials [B][rows][2][Cout] that ucfvit_conv3d_fwd writes for this launch (dense bf16 output, no
+// rows per batch element of the statistics partials [B][rows][3][Cout] that ucfvit_conv3d_fwd writes for this launch (dense bf16 output, no
 // accumulation), 0 when the kernel that serves it has no statistics epilogue (the caller then runs ucfvit_instnorm_cl_stats on the output)
 extern "C" int64_t ucfvit_conv3d_fwd_stats_rows(int64_t B, int64_t X, int64_t Y, int64_t Z, int64_t Cin, int64_t Cout, int ksize, int has_bias) {
-    if (!(Cin == 8 || Cin == 16 || (Cin > 0 && Cin % 32 == 0)) || Cout <= 0 || Cout % 16 || !(ksize == 1 || ksize == 3)) return 0;
-    ConvGeo g{(int)B, (int)X, (int)Y, (int)Z, (int)Cin, (int)Cout, 0, 0, 0, 0, (int)Cout, (int)Cout, 0};
-    const FwdPlan pl = fwd_plan(g, ksize, has_bias != 0, true);
-    if (pl.kind == 0) return 0;
-    return (int64_t)((X + pl.TX - 1) / pl.TX) * ((Y + pl.TY - 1) / pl.TY) * 4;
+    if (!conv_shape_ok(Cin, Cout, ksize)) return 0;
+    return conv_fwd_route(B, X, Y, Z, Cin, Cout, ksize, has_bias != 0, UCFVIT_BF16, Cout, Cout, strip_mode()).stats_rows;
 }
 
 // number of fp32 values of the packed weight gradient [Cout/(16 MB)][Cin/CPC][taps][16 MB][16 NBK] and bytes of scratch for the partials
+// (0: a shape the kernels are not instantiated for)
 extern "C" int64_t ucfvit_conv3d_wgrad_size(int64_t Cin, int64_t Cout, int ksize) {
-    const int64_t cpc = Cin < 32 ? Cin : 32;
-    const int64_t nbk16 = cpc >= 16 ? cpc : 16;
-    return (Cin / cpc) * (ksize == 3 ? 27 : 1) * Cout * nbk16;
+    return conv_shape_ok(Cin, Cout, ksize) ? conv_wgrad_route(1, 1, 1, 1, Cin, Cout, ksize).n_out : 0;
 }
 extern "C" int64_t ucfvit_conv3d_wgrad_workspace(int64_t B, int64_t X, int64_t Y, int64_t Z, int64_t Cin, int64_t Cout, int ksize) {
-    if (!(Cin == 8 || Cin == 16 || (Cin > 0 && Cin % 32 == 0)) || Cout <= 0 || Cout % 16 || !(ksize == 1 || ksize == 3)) return 0;
-    ConvGeo g{(int)B, (int)X, (int)Y, (int)Z, (int)Cin, (int)Cout, 0, 0, 0, 0, 0, 0, 0};
-    int n_wg = 0, tpw = 0, gy = 0;
-    int64_t n_out = 0;
-    CONV_SWITCH(Cin, ksize, {
-        if (Cout % 32 == 0)
-            wgrad_plan<CPC_, 2, 2, 4, KS_>(g, n_wg, tpw, gy, n_out);
-        else
-            wgrad_plan<CPC_, 1, 2, 4, KS_>(g, n_wg, tpw, gy, n_out);
-    });
-    return (int64_t)n_wg * (ksize == 3 ? 1 : 4) * n_out * (int64_t)sizeof(float);
+    return conv_shape_ok(Cin, Cout, ksize) ? conv_wgrad_route(B, X, Y, Z, Cin, Cout, ksize).workspace_bytes : 0;
 }
 // x [..][Cin], dy [..][Cout] bf16 -> dw_packed fp32 (layout above; UCF_VIT/_hip/conv.py:unpack_conv_wgrad turns it into [Cout][Cin][k][k][k])
 extern "C" int ucfvit_conv3d_wgrad(const void* x, const void* dy, float* dw_packed, void* workspace, int64_t B, int64_t X, int64_t Y,
                                    int64_t Z, int64_t Cin, int64_t Cout, int ksize, void* stream) {
     if (int rc = conv_check("ucfvit_conv3d_wgrad", x, dy, dw_packed, B, X, Y, Z, Cin, Cout, ksize)) return rc;
     UCF_CHECK_ARG(workspace, "ucfvit_conv3d_wgrad: null workspace");
-    ConvGeo g{(int)B, (int)X, (int)Y, (int)Z, (int)Cin, (int)Cout, 0, 0, 0, 0, 0, 0, 0};
+    const ConvWgradRoute r = conv_wgrad_route(B, X, Y, Z, Cin, Cout, ksize);
+    const ConvGeo g{(int)B, (int)X, (int)Y, (int)Z, (int)Cin, (int)Cout, r.tx, r.ty, r.tz, r.tiles, 0, 0, 0};
     hipStream_t s = (hipStream_t)stream;
+    const bf16 *xb = (const bf16*)x, *dyb = (const bf16*)dy;
+    float* ws = (float*)workspace;
+    const char* who = "ucfvit_conv3d_wgrad";
     CONV_SWITCH(Cin, ksize, {
-        if (Cout % 32 == 0) return launch_wgrad<CPC_, 2, 2, 4, KS_>((const bf16*)x, (const bf16*)dy, dw_packed, (float*)workspace, g, s);
-        return launch_wgrad<CPC_, 1, 2, 4, KS_>((const bf16*)x, (const bf16*)dy, dw_packed, (float*)workspace, g, s);
+        static_assert(conv_wgrad_smem(CPC_, KS_, 2) <= 160 * 1024, "LDS budget");
+        if (int rc = r.mb == 2 ? conv_launch<conv_wgrad_kernel<CPC_, 2, CONV_WGRAD_TX, CONV_WGRAD_TY, KS_>>(who, r.n_wg, r.gy, r.smem, s, xb, dyb, ws, g, r.tiles_per_wg)
+                               : conv_launch<conv_wgrad_kernel<CPC_, 1, CONV_WGRAD_TX, CONV_WGRAD_TY, KS_>>(who, r.n_wg, r.gy, r.smem, s, xb, dyb, ws, g, r.tiles_per_wg))
+            return rc;
     });
-    return UCFVIT_OK;
+    return ucfvit_reduce_rows(ws, dw_packed, (int64_t)r.n_wg * r.slots, r.n_out, 0, s);
+}
+
+// the route of a launch as text (host only): pass 0 = ucfvit_conv3d_fwd, 1 = ucfvit_conv3d_wgrad; mode = UCFVIT_CONV_STRIP to assume, -1 = this process's
+extern "C" int ucfvit_conv3d_route(int pass, int64_t B, int64_t X, int64_t Y, int64_t Z, int64_t Cin, int64_t Cout, int ksize, int has_bias,
+                                   int out_dtype, int64_t ldy, int64_t cout_store, int mode, char* out, int64_t cap) {
+    UCF_CHECK_ARG(out || cap <= 0, "ucfvit_conv3d_route: null buffer");
+    UCF_CHECK_ARG((pass == 0 || pass == 1) && mode >= -1 && mode <= 3, "ucfvit_conv3d_route: pass must be 0 or 1, mode -1 .. 3");
+    UCF_CHECK_ARG(B > 0 && X > 0 && Y > 0 && Z > 0 && B * X * Y * Z < (1ll << 31) && conv_shape_ok(Cin, Cout, ksize) &&
+                      (pass == 1 || (cout_store > 0 && cout_store <= Cout && ldy >= cout_store && ldy < (1ll << 31))),
+                  "ucfvit_conv3d_route: a shape the convolution entry points refuse");
+    char text[160];
+    if (pass == 1) {
+        const ConvWgradRoute w = conv_wgrad_route(B, X, Y, Z, Cin, Cout, ksize);
+        snprintf(text, sizeof text, "wgrad cpc%d ks%d mb%d n_wg%d tiles_per_wg%d slots%d n_out%lld", w.cpc, w.ks, w.mb, w.n_wg, w.tiles_per_wg, w.slots,
+                 (long long)w.n_out);
+        return conv_text(text, out, cap);
+    }
+    const ConvFwdRoute r = conv_fwd_route(B, X, Y, Z, Cin, Cout, ksize, has_bias != 0, out_dtype, ldy, cout_store, mode < 0 ? strip_mode() : mode);
+    const char* const mc[5] = {"", "mc1", "mc2", "", "mc4"};
+    const char* kind = r.kind == CK_TILE ? "tile" : (r.kind == CK_MC ? mc[r.tzt] : (r.fast ? "strip-fast" : "strip-branching"));
+    snprintf(text, sizeof text, "%s%s cpc%d ks%d nb%d %dx%d depth%d rows%lld", kind, r.share ? "-share" : "", r.cpc, r.ks, r.nb, r.TX, r.TY, r.depth,
+             (long long)r.stats_rows);
+    return conv_text(text, out, cap);
 }
 
 // to_space = 1: cols [B Xi Yi Zi][8 C] -> space[voxel * ld_space + c] over [B][2Xi][2Yi][2Zi] voxels;  to_space = 0: the inverse.  bf16, C % 8 == 0,
