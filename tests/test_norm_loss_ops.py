@@ -8,15 +8,18 @@ Kernels and the cases that reach them (chunks_of, cl_chunks_of, apply_grid, cl_a
 test_tables_reach_every_branch asserts this list from them):
     in_stats_partial / in_stats_final,     test_row_family: fp32 and bf16, rows 2x3 and 2x5 (apply_grid caps 342 / 205), S = 4 | 8 (one short chunk),
       in_apply<T, RES 0 / 1>,              16376 (one ragged chunk), 16384, 16392 (a second chunk of one vector), 32776 (3 chunks); forward with
-      in_bwd_partial / _final,             and without res, slope 0.01 and 1; backward with dres (a residual was added) and without
+      in_bwd_partial, bwd_means<2>,        and without res, slope 0.01 and 1; backward with dres (a residual was added) and without
       in_bwd_apply<T, RES 0 / 1>
     incl_stats_partial, incl_stats_fold    test_cl_family[stats]: C = 8, 32, 64, 128, 256 (cv = C / 8 = 1 .. 32: the threadIdx.x % cv ownership and the
                                            t += cv LDS folds) x S cv = CLV - cv, CLV, CLV + cv, 2 CLV + 3 cv (1, 1, 2, 3 chunks), and S cv < 256
     incl_apply<RES 0 / 1>, incl_apply2     test_cl_family[apply]: the same shapes
     incl_bwd_partial<NEED_Y 0 / 1>,        test_cl_family[bwd]: the same shapes; dy dense (ld = C) and a channel slice (ld = 2 C at offset C, ld = C + 8 at
-      cl_fold, incl_bwd_final,             offset 8, ld 48 at 16), each with one and with several chunks; the three instantiations: mask from y with dres,
+      cl_fold, bwd_means<2>,               offset 8, ld 48 at 16), each with one and with several chunks; the three instantiations: mask from y with dres,
       incl_bwd_apply<1,1> <1,0> <0,0>      mask from y without, mask recomputed from x; the buffer behind a sliced dy is compared bit for bit afterwards
-    incl_bwd2_partial / _final / _apply    test_cl_family[bwd2]: the same shapes and slices
+    incl_bwd2_partial, bwd_means<3>,       test_cl_family[bwd2]: the same shapes and slices
+      incl_bwd2_apply
+    (bwd_means<K> is one kernel for both layouts, the row layout being C = 1; cl_fold is cl_stage + cl_channel_sums, which incl_stats_partial
+    calls directly; the double wave butterfly of every final kernel is wave_sum(double) of common.h, the triples' is mom_wave_fold)
     C = 512, 2048 (cv = 64, 256 = NT)      test_cl_wide_channels: all four parts at S = 6 and 3.  The library computes them, so correct values are required
                                            (any library error, a refusal included, fails); the fold is single-stage there (C > NT)
     incl_stats_fold1 + incl_stats_fold     test_cl_stats_fold_stages: C = 256 through ops.instnorm_cl_stats at S = 65536 (512 partial rows: one stage) and
@@ -96,7 +99,7 @@ Not covered: the means kept in the workspace by ops.instnorm_cl_bwd (the two hal
 Measured on an MI355X: 135 GPU tests + 67 CPU tests, 50 s for the file (the GPU tests 15 s); the two fold-stage cases take 2.0 s each (the float64
 reference of 2 x 65537 x 256 values), every other GPU test stays below half a second.
 Mutation check (nothing of it committed), one line each: the mask from n in incl_bwd_apply<RES> failed test_cl_family[*-bwd] on all 22 cases and
-test_cl_wide_channels[*-bwd] on both; t starting at cg + cv in cl_fold failed the same 24; S for S_total in dice_bwd failed all 25 test_dice cases.
+test_cl_wide_channels[*-bwd] on both; t starting at cg + cv in cl_fold (the loop is now cl_channel_sums) failed the same 24; S for S_total in dice_bwd failed all 25 test_dice cases.
   worst err / bound                               bf16 out   fp32 out
   in_apply y (own statistics)                     0.994      0.180
   in_bwd dx / dres                                0.995 / 0.928      0.134 / 0.492

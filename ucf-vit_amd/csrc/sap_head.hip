@@ -117,8 +117,7 @@ __global__ __launch_bounds__(64) void dbias_final_kernel(const float* __restrict
     const int c = blockIdx.x;
     double s = 0.0;
     for (int i = threadIdx.x; i < B * chunks; i += 64) s += part[((i / chunks) * C + c) * chunks + i % chunks];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    s = wave_sum(s);
     if (threadIdx.x == 0) dbias[c] = (float)s;
 }
 
@@ -290,9 +289,7 @@ __global__ __launch_bounds__(64) void dbce_stats_final_kernel(const float* __res
 #pragma unroll
         for (int k = 0; k < DBCE_STATS; ++k) s[k] += part[(int64_t)i * DBCE_STATS + k];
 #pragma unroll
-    for (int k = 0; k < DBCE_STATS; ++k)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s[k] += __shfl_xor(s[k], o, 64);
+    for (int k = 0; k < DBCE_STATS; ++k) s[k] = wave_sum(s[k]);
     if (threadIdx.x == 0)
 #pragma unroll
         for (int k = 0; k < DBCE_STATS; ++k) stats[k] = (float)s[k];

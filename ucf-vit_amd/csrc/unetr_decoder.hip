@@ -84,6 +84,12 @@ __device__ __forceinline__ Mom mom_wave_fold(Mom a) {
     }
     return a;
 }
+// mean and 1 / sqrt(var + eps) of a folded triple (biased variance M2 / n; nothing counted: variance 0)
+__device__ __forceinline__ void mom_finish(const Mom& a, float eps, float& mean, float& rstd) {
+    const double var = a.n > 0.0 ? fmax(a.m2 / a.n, 0.0) : 0.0;
+    mean = (float)a.m;
+    rstd = (float)(1.0 / sqrt(var + (double)eps));
+}
 
 // pass 2: one wave per row folds the chunk triples in a fixed order (2048 chunks of 16384 at the full volume)
 __global__ __launch_bounds__(64) void in_stats_final(const float* __restrict__ part, float* __restrict__ mean, float* __restrict__ rstd, int chunks,
@@ -95,11 +101,7 @@ __global__ __launch_bounds__(64) void in_stats_final(const float* __restrict__ p
         mom_add(a, (double)p[0], (double)p[1], (double)p[2]);
     }
     a = mom_wave_fold(a);
-    if (threadIdx.x == 0) {
-        const double var = a.n > 0.0 ? fmax(a.m2 / a.n, 0.0) : 0.0;
-        mean[row] = (float)a.m;
-        rstd[row] = (float)(1.0 / sqrt(var + (double)eps));
-    }
+    if (threadIdx.x == 0) mom_finish(a, eps, mean[row], rstd[row]);
 }
 
 // ---- apply: y = lrelu((x - mean) rstd [+ res], slope)   (slope 1: no activation) ------------------------------------------------------
@@ -149,23 +151,24 @@ __global__ __launch_bounds__(NT) void in_bwd_partial(const T* __restrict__ dy, c
         part[(row * chunks + blockIdx.x) * 2 + 1] = s2;
     }
 }
-__global__ __launch_bounds__(64) void in_bwd_final(const float* __restrict__ part, float* __restrict__ m1, float* __restrict__ m2, int64_t S,
-                                                   int chunks) {
-    const int64_t row = blockIdx.x;
-    double s1 = 0.0, s2 = 0.0;
-    for (int c = threadIdx.x; c < chunks; c += 64) {
-        s1 += part[(row * chunks + c) * 2 + 0];
-        s2 += part[(row * chunks + c) * 2 + 1];
-    }
+// the K means over the S voxels from the chunk sums [B][chunks][K][C] of a backward pass in either layout (the row layout is C = 1): one wave
+// per (b, c) adds its chunks lane-strided in double, then the butterfly; table k goes to out.m[k][b C + c]
+template <int K> struct Means {
+    float* m[K];
+};
+template <int K>
+__global__ __launch_bounds__(64) void bwd_means(const float* __restrict__ part, Means<K> out, int64_t S, int C, int chunks) {
+    const int64_t b = blockIdx.x / C;
+    const int c = blockIdx.x % C;
+    double s[K] = {};
+    for (int ch = threadIdx.x; ch < chunks; ch += 64)
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        s1 += __shfl_xor(s1, o, 64);
-        s2 += __shfl_xor(s2, o, 64);
-    }
-    if (threadIdx.x == 0) {
-        m1[row] = (float)(s1 / (double)S);
-        m2[row] = (float)(s2 / (double)S);
-    }
+        for (int k = 0; k < K; ++k) s[k] += part[(b * chunks + ch) * K * C + k * C + c];
+#pragma unroll
+    for (int k = 0; k < K; ++k) s[k] = wave_sum(s[k]);
+    if (threadIdx.x == 0)
+#pragma unroll
+        for (int k = 0; k < K; ++k) out.m[k][blockIdx.x] = (float)(s[k] / (double)S);
 }
 template <typename T, bool RES>
 __global__ __launch_bounds__(NT) void in_bwd_apply(const T* __restrict__ dy, const T* __restrict__ y, const T* __restrict__ x,
@@ -258,8 +261,7 @@ __global__ __launch_bounds__(64) void dice_final(const float* __restrict__ part,
         for (int k = 0; k < DSTAT; ++k) {
             double s = 0.0;
             for (int c = threadIdx.x; c < chunks; c += 64) s += part[((int64_t)b * chunks + c) * DSTAT + k];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+            s = wave_sum(s);
             if (threadIdx.x == 0) stats[b * DSTAT + k] = (float)s;
             if (k == 3 * MAXC) total_ce += s;
         }
@@ -324,18 +326,43 @@ __global__ __launch_bounds__(NT) void dice_bwd(const T* __restrict__ logits, con
 // size are multiples of C/8), so the per-channel sums live in registers and are folded once per workgroup through LDS.
 constexpr int CLV = 4096;          // 16-byte vectors per workgroup in the reduction passes
 
-__device__ __forceinline__ void cl_fold(const float (&s1)[8], const float (&s2)[8], float (*red)[17], float* out, int C, int cv) {
+// this thread's 8 consecutive entries, from k0 on, of any number of fp32 tables [B][C]: ld_chan(b * C + cg * 8, Tab{mean, m}, Tab{rstd, r}, ...)
+struct Tab {
+    const float* t;
+    float (&v)[8];
+};
+template <typename... T> __device__ __forceinline__ void ld_chan(int64_t k0, T... tab) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) ((tab.v[e] = tab.t[k0 + e]), ...);
+}
+
+// the workgroup fold of K per-thread sums of 8 channels each: cl_stage puts them into LDS (red: NT rows of 8 K + 1 floats), cl_channel_sums adds
+// the sums k0 .. k0 + N - 1 of channel c over the NT / cv threads of its channel group in sequence, cl_fold writes all of them as [K][C].  The sums are K separate
+// arrays handed over by reference: as one [K][8] array or an array of pointers the callers' loops compile to other registers and, under
+// -ffp-contract=fast, to other multiply-add contractions, which changes result bits (profiles/norm_loss_refactor.md)
+template <typename... A> __device__ __forceinline__ void cl_stage(float (*red)[8 * sizeof...(A) + 1], const A&... s) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-        red[threadIdx.x][e] = s1[e];
-        red[threadIdx.x][8 + e] = s2[e];
+        int k = 0;
+        ((red[threadIdx.x][8 * k++ + e] = s[e]), ...);
     }
     __syncthreads();
-    for (int o = threadIdx.x; o < 2 * C; o += NT) {
-        const int k = o / C, c = o % C, cg = c >> 3, e = c & 7;
-        float s = 0.f;
-        for (int t = cg; t < NT; t += cv) s += red[t][k * 8 + e];
-        out[o] = s;                                                 // [2][C]
+}
+template <int K, int N> __device__ __forceinline__ void cl_channel_sums(const float (*red)[8 * K + 1], int k0, int c, int cv, float (&a)[N]) {
+    const int cg = c >> 3, e = c & 7;
+#pragma unroll
+    for (int j = 0; j < N; ++j) a[j] = 0.f;
+    for (int t = cg; t < NT; t += cv)
+#pragma unroll
+        for (int j = 0; j < N; ++j) a[j] += red[t][(k0 + j) * 8 + e];
+}
+template <typename... A> __device__ __forceinline__ void cl_fold(float (*red)[8 * sizeof...(A) + 1], float* out, int C, int cv, const A&... s) {
+    constexpr int K = sizeof...(A);
+    cl_stage(red, s...);
+    for (int o = threadIdx.x; o < K * C; o += NT) {
+        float a[1];
+        cl_channel_sums<K>(red, o / C, o % C, cv, a);
+        out[o] = a[0];
     }
 }
 
@@ -348,9 +375,7 @@ __global__ __launch_bounds__(NT) void incl_stats_partial(const bf16* __restrict_
     const int64_t nvec = S * cv, vlo = (int64_t)blockIdx.x * CLV, vhi = min(nvec, vlo + CLV);
     const bf16x8* xb = reinterpret_cast<const bf16x8*>(x + b * S * C);
     const bf16x8 sh = xb[vlo + threadIdx.x % cv];                   // shift = the chunk's first voxel (vlo is a multiple of cv)
-    float s1[8], s2[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) s1[e] = s2[e] = 0.f;
+    float s1[8] = {}, s2[8] = {};
     for (int64_t i = vlo + threadIdx.x; i < vhi; i += NT) {
         const bf16x8 v = xb[i];
 #pragma unroll
@@ -360,29 +385,20 @@ __global__ __launch_bounds__(NT) void incl_stats_partial(const bf16* __restrict_
             s2[e] += d * d;
         }
     }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        red[threadIdx.x][e] = s1[e];
-        red[threadIdx.x][8 + e] = s2[e];
-    }
-    __syncthreads();
+    cl_stage(red, s1, s2);
     const float n = (float)((vhi - vlo) / cv);                      // voxels of the chunk
     float* out = part + (b * chunks + blockIdx.x) * 3 * C;
     for (int c = threadIdx.x; c < C; c += NT) {
-        const int cg = c >> 3, e = c & 7;
-        float a1 = 0.f, a2 = 0.f;
-        for (int t = cg; t < NT; t += cv) {
-            a1 += red[t][e];
-            a2 += red[t][8 + e];
-        }
+        float a[2];
+        cl_channel_sums<2>(red, 0, c, cv, a);
+        const float a1 = a[0], a2 = a[1];
         out[c] = n;
         out[C + c] = (float)x[(b * S + vlo / cv) * C + c] + a1 / n;
         out[2 * C + c] = fmaxf(a2 - a1 * (a1 / n), 0.f);
     }
 }
 // ---- fold of the convolution kernels' statistics epilogue: partial rows [B][rows][3][C] of (count, mean, M2) per channel (conv3d.hip:
-// stats_row_write) combined with the parallel-variance formula in double: n = na + nb, d = mb - ma, m = ma + d nb / n,
-// M2 = M2a + M2b + d^2 na nb / n.  Rows that stored nothing carry count 0 and drop out.
+// stats_row_write) combined in double (mom_add).  Rows that stored nothing carry count 0 and drop out.
 // first stage when there are many partial rows (a full-resolution layer writes 32768 per batch element): workgroup (g, b) combines the rows
 // [g rpg, (g + 1) rpg) -> [B][G][3][C]; a thread owns a channel, NT / C rows in flight, the threads of a channel are combined in a fixed order
 __global__ __launch_bounds__(NT) void incl_stats_fold1(const float* __restrict__ part, float* __restrict__ out, int rows, int C, int rpg) {
@@ -420,19 +436,8 @@ __global__ __launch_bounds__(64) void incl_stats_fold(const float* __restrict__ 
         const float* p = part + (b * rows + r) * 3 * C + c;
         mom_add(a, (double)p[0], (double)p[C], (double)p[2 * C]);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {                          // butterfly: every lane ends with the same combination order
-        const double nb = __shfl_xor(a.n, o, 64), mb = __shfl_xor(a.m, o, 64), m2b = __shfl_xor(a.m2, o, 64);
-        const bool lower = (threadIdx.x & o) == 0;              // combine (lower, upper) in that order on both sides
-        Mom lo = lower ? a : Mom{nb, mb, m2b};
-        if (lower) mom_add(lo, nb, mb, m2b); else mom_add(lo, a.n, a.m, a.m2);
-        a = lo;
-    }
-    if (threadIdx.x == 0) {
-        const double var = a.n > 0.0 ? fmax(a.m2 / a.n, 0.0) : 0.0;             // a.n == S: every voxel of the batch element was stored once
-        mean[blockIdx.x] = (float)a.m;
-        rstd[blockIdx.x] = (float)(1.0 / sqrt(var + (double)eps));
-    }
+    a = mom_wave_fold(a);
+    if (threadIdx.x == 0) mom_finish(a, eps, mean[blockIdx.x], rstd[blockIdx.x]);       // a.n == S: every voxel of the batch element was stored once
 }
 template <bool RES>
 __global__ __launch_bounds__(NT) void incl_apply(const bf16* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd,
@@ -440,11 +445,7 @@ __global__ __launch_bounds__(NT) void incl_apply(const bf16* __restrict__ x, con
     const int64_t b = blockIdx.y;
     const int cv = C >> 3, cg = threadIdx.x % cv;
     float m[8], r[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        m[e] = mean[b * C + cg * 8 + e];
-        r[e] = rstd[b * C + cg * 8 + e];
-    }
+    ld_chan(b * C + cg * 8, Tab{mean, m}, Tab{rstd, r});
     const int64_t nvec = S * cv;
     const bf16x8* xb = reinterpret_cast<const bf16x8*>(x + b * S * C);
     const bf16x8* rb = reinterpret_cast<const bf16x8*>(res + b * S * C);
@@ -471,13 +472,8 @@ __global__ __launch_bounds__(NT) void incl_bwd_partial(const bf16* __restrict__ 
     __shared__ float red[NT][17];
     const int64_t b = blockIdx.y;
     const int cv = C >> 3, cg = threadIdx.x % cv, cvs = __builtin_ctz(cv);
-    float m[8], r[8], s1[8], s2[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        m[e] = mean[b * C + cg * 8 + e];
-        r[e] = rstd[b * C + cg * 8 + e];
-        s1[e] = s2[e] = 0.f;
-    }
+    float m[8], r[8], s1[8] = {}, s2[8] = {};
+    ld_chan(b * C + cg * 8, Tab{mean, m}, Tab{rstd, r});
     const int64_t nvec = S * cv, vlo = (int64_t)blockIdx.x * CLV, vhi = min(nvec, vlo + CLV);
     const bf16x8* gb = reinterpret_cast<const bf16x8*>(dy) + b * S * ldg8;       // dy rows may be ldg8 16-byte units apart (a channel slice)
     const bf16x8* yb = reinterpret_cast<const bf16x8*>(y + b * S * C);
@@ -494,26 +490,7 @@ __global__ __launch_bounds__(NT) void incl_bwd_partial(const bf16* __restrict__ 
             s2[e] += g * n;
         }
     }
-    cl_fold(s1, s2, red, part + (b * chunks + blockIdx.x) * 2 * C, C, cv);
-}
-__global__ __launch_bounds__(64) void incl_bwd_final(const float* __restrict__ part, float* __restrict__ m1, float* __restrict__ m2, int64_t S,
-                                                     int C, int chunks) {
-    const int64_t b = blockIdx.x / C;
-    const int c = blockIdx.x % C;
-    double s1 = 0.0, s2 = 0.0;
-    for (int ch = threadIdx.x; ch < chunks; ch += 64) {
-        s1 += part[(b * chunks + ch) * 2 * C + c];
-        s2 += part[(b * chunks + ch) * 2 * C + C + c];
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        s1 += __shfl_xor(s1, o, 64);
-        s2 += __shfl_xor(s2, o, 64);
-    }
-    if (threadIdx.x == 0) {
-        m1[blockIdx.x] = (float)(s1 / (double)S);
-        m2[blockIdx.x] = (float)(s2 / (double)S);
-    }
+    cl_fold(red, part + (b * chunks + blockIdx.x) * 2 * C, C, cv, s1, s2);
 }
 template <bool RES, bool WRES>
 __global__ __launch_bounds__(NT) void incl_bwd_apply(const bf16* __restrict__ dy, const bf16* __restrict__ y, const bf16* __restrict__ x,
@@ -523,13 +500,7 @@ __global__ __launch_bounds__(NT) void incl_bwd_apply(const bf16* __restrict__ dy
     const int64_t b = blockIdx.y;
     const int cv = C >> 3, cg = threadIdx.x % cv, cvs = __builtin_ctz(cv);
     float m[8], r[8], a1[8], a2[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        m[e] = mean[b * C + cg * 8 + e];
-        r[e] = rstd[b * C + cg * 8 + e];
-        a1[e] = m1[b * C + cg * 8 + e];
-        a2[e] = m2[b * C + cg * 8 + e];
-    }
+    ld_chan(b * C + cg * 8, Tab{mean, m}, Tab{rstd, r}, Tab{m1, a1}, Tab{m2, a2});
     const int64_t nvec = S * cv;
     const bf16x8* gb = reinterpret_cast<const bf16x8*>(dy) + b * S * ldg8;
     const bf16x8* yb = reinterpret_cast<const bf16x8*>(y + b * S * C);
@@ -561,13 +532,7 @@ __global__ __launch_bounds__(NT) void incl_apply2(const bf16* __restrict__ x, co
     const int64_t b = blockIdx.y;
     const int cv = C >> 3, cg = threadIdx.x % cv;
     float m[8], r[8], m2[8], r2[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        m[e] = mean[b * C + cg * 8 + e];
-        r[e] = rstd[b * C + cg * 8 + e];
-        m2[e] = mean2[b * C + cg * 8 + e];
-        r2[e] = rstd2[b * C + cg * 8 + e];
-    }
+    ld_chan(b * C + cg * 8, Tab{mean, m}, Tab{rstd, r}, Tab{mean2, m2}, Tab{rstd2, r2});
     const int64_t nvec = S * cv;
     const bf16x8* xb = reinterpret_cast<const bf16x8*>(x + b * S * C);
     const bf16x8* x2b = reinterpret_cast<const bf16x8*>(x2 + b * S * C);
@@ -590,15 +555,8 @@ __global__ __launch_bounds__(NT) void incl_bwd2_partial(const bf16* __restrict__
     __shared__ float red[NT][25];
     const int64_t b = blockIdx.y;
     const int cv = C >> 3, cg = threadIdx.x % cv, cvs = __builtin_ctz(cv);
-    float m[8], r[8], m2[8], r2[8], s1[8], s2[8], s3[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        m[e] = mean[b * C + cg * 8 + e];
-        r[e] = rstd[b * C + cg * 8 + e];
-        m2[e] = mean2[b * C + cg * 8 + e];
-        r2[e] = rstd2[b * C + cg * 8 + e];
-        s1[e] = s2[e] = s3[e] = 0.f;
-    }
+    float m[8], r[8], m2[8], r2[8], s1[8] = {}, s2[8] = {}, s3[8] = {};
+    ld_chan(b * C + cg * 8, Tab{mean, m}, Tab{rstd, r}, Tab{mean2, m2}, Tab{rstd2, r2});
     const int64_t nvec = S * cv, vlo = (int64_t)blockIdx.x * CLV, vhi = min(nvec, vlo + CLV);
     const bf16x8* gb = reinterpret_cast<const bf16x8*>(dy) + b * S * ldg8;
     const bf16x8* yb = reinterpret_cast<const bf16x8*>(y + b * S * C);
@@ -614,35 +572,7 @@ __global__ __launch_bounds__(NT) void incl_bwd2_partial(const bf16* __restrict__
             s3[e] += dn * ((float)zv[e] - m2[e]) * r2[e];
         }
     }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        red[threadIdx.x][e] = s1[e];
-        red[threadIdx.x][8 + e] = s2[e];
-        red[threadIdx.x][16 + e] = s3[e];
-    }
-    __syncthreads();
-    float* out = part + (b * chunks + blockIdx.x) * 3 * C;
-    for (int o = threadIdx.x; o < 3 * C; o += NT) {
-        const int k = o / C, c = o % C, cgo = c >> 3, e = c & 7;
-        float s = 0.f;
-        for (int t = cgo; t < NT; t += cv) s += red[t][k * 8 + e];
-        out[o] = s;                                                 // [3][C]
-    }
-}
-__global__ __launch_bounds__(64) void incl_bwd2_final(const float* __restrict__ part, float* __restrict__ mm, int64_t S, int C, int chunks, int BC) {
-    const int64_t b = blockIdx.x / C;
-    const int c = blockIdx.x % C;
-    double s[3] = {0.0, 0.0, 0.0};
-    for (int ch = threadIdx.x; ch < chunks; ch += 64)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) s[k] += part[(b * chunks + ch) * 3 * C + k * C + c];
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s[k] += __shfl_xor(s[k], o, 64);
-    if (threadIdx.x == 0)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) mm[k * BC + blockIdx.x] = (float)(s[k] / (double)S);
+    cl_fold(red, part + (b * chunks + blockIdx.x) * 3 * C, C, cv, s1, s2, s3);
 }
 __global__ __launch_bounds__(NT) void incl_bwd2_apply(const bf16* __restrict__ dy, const bf16* __restrict__ y, const bf16* __restrict__ x,
                                                       const float* __restrict__ mean, const float* __restrict__ rstd, const bf16* __restrict__ x2,
@@ -652,17 +582,7 @@ __global__ __launch_bounds__(NT) void incl_bwd2_apply(const bf16* __restrict__ d
     const int64_t b = blockIdx.y;
     const int cv = C >> 3, cg = threadIdx.x % cv, cvs = __builtin_ctz(cv);
     float m[8], r[8], m2[8], r2[8], a1[8], a2[8], a3[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const int64_t k = b * C + cg * 8 + e;
-        m[e] = mean[k];
-        r[e] = rstd[k];
-        m2[e] = mean2[k];
-        r2[e] = rstd2[k];
-        a1[e] = mm[k];
-        a2[e] = mm[BC + k];
-        a3[e] = mm[2 * BC + k];
-    }
+    ld_chan(b * C + cg * 8, Tab{mean, m}, Tab{rstd, r}, Tab{mean2, m2}, Tab{rstd2, r2}, Tab{mm, a1}, Tab{mm + BC, a2}, Tab{mm + 2 * BC, a3});
     const int64_t nvec = S * cv;
     const bf16x8* gb = reinterpret_cast<const bf16x8*>(dy) + b * S * ldg8;
     const bf16x8* yb = reinterpret_cast<const bf16x8*>(y + b * S * C);
@@ -733,11 +653,8 @@ extern "C" int ucfvit_instnorm_fwd(const void* x, const void* res, void* y, floa
     IN_DISPATCH(T, {
         hipLaunchKernelGGL((in_stats_partial<T>), dim3(ch, (unsigned)rows), dim3(NT), 0, s, (const T*)x, part, S, ch);
         hipLaunchKernelGGL(in_stats_final, dim3((unsigned)rows), dim3(64), 0, s, part, mean, rstd, ch, eps);
-        const dim3 g(apply_grid(S, rows), (unsigned)rows);
-        if (res)
-            hipLaunchKernelGGL((in_apply<T, true>), g, dim3(NT), 0, s, (const T*)x, mean, rstd, (const T*)res, (T*)y, S, slope);
-        else
-            hipLaunchKernelGGL((in_apply<T, false>), g, dim3(NT), 0, s, (const T*)x, mean, rstd, (const T*)nullptr, (T*)y, S, slope);
+        const auto apply = res ? in_apply<T, true> : in_apply<T, false>;
+        hipLaunchKernelGGL(apply, dim3(apply_grid(S, rows), (unsigned)rows), dim3(NT), 0, s, (const T*)x, mean, rstd, (const T*)res, (T*)y, S, slope);
     });
     UCF_LAUNCH_CHECK("ucfvit_instnorm_fwd");
     return UCFVIT_OK;
@@ -755,14 +672,10 @@ extern "C" int ucfvit_instnorm_bwd(const void* dy, const void* y, const void* x,
     IN_DISPATCH(T, {
         hipLaunchKernelGGL((in_bwd_partial<T>), dim3(ch, (unsigned)rows), dim3(NT), 0, s, (const T*)dy, (const T*)y, (const T*)x, mean, rstd, part,
                            S, ch, slope);
-        hipLaunchKernelGGL(in_bwd_final, dim3((unsigned)rows), dim3(64), 0, s, part, m1, m2, S, ch);
-        const dim3 g(apply_grid(S, rows), (unsigned)rows);
-        if (dres)
-            hipLaunchKernelGGL((in_bwd_apply<T, true>), g, dim3(NT), 0, s, (const T*)dy, (const T*)y, (const T*)x, mean, rstd, m1, m2, (T*)dx,
-                               (T*)dres, S, slope);
-        else
-            hipLaunchKernelGGL((in_bwd_apply<T, false>), g, dim3(NT), 0, s, (const T*)dy, (const T*)y, (const T*)x, mean, rstd, m1, m2, (T*)dx,
-                               (T*)nullptr, S, slope);
+        hipLaunchKernelGGL(bwd_means<2>, dim3((unsigned)rows), dim3(64), 0, s, part, Means<2>{{m1, m2}}, S, 1, ch);
+        const auto apply = dres ? in_bwd_apply<T, true> : in_bwd_apply<T, false>;
+        hipLaunchKernelGGL(apply, dim3(apply_grid(S, rows), (unsigned)rows), dim3(NT), 0, s, (const T*)dy, (const T*)y, (const T*)x, mean, rstd, m1, m2,
+                           (T*)dx, (T*)dres, S, slope);
     });
     UCF_LAUNCH_CHECK("ucfvit_instnorm_bwd");
     return UCFVIT_OK;
@@ -778,6 +691,23 @@ static int dice_check(const char* name, const void* logits, const int64_t* label
     UCF_CHECK_ARG(stride_b > 0 && stride_c > 0 && stride_s > 0, "%s: strides must be positive", name);
     return UCFVIT_OK;
 }
+// chunk sums of the local voxels into part, then their fold: the sums to stats [B][DSTAT], the loss of those sums to loss
+static void launch_dice_sums(const void* logits, const int64_t* labels, float* part, float* stats, float* loss, int64_t B, int64_t n, int64_t S,
+                             int64_t sb, int64_t sc, int64_t ss, float s_nr, float s_dr, int dtype, hipStream_t s) {
+    const int ch = chunks_of(S);
+    IN_DISPATCH(T, {
+        hipLaunchKernelGGL((dice_partial<T>), dim3(ch, (unsigned)B), dim3(NT), 0, s, (const T*)logits, labels, part, (int)n, S, ch, sb, sc, ss);
+    });
+    hipLaunchKernelGGL(dice_final, dim3(1), dim3(64), 0, s, part, stats, loss, (int)B, (int)n, S, ch, s_nr, s_dr);
+}
+static void launch_dice_bwd(const void* logits, const int64_t* labels, const float* stats, void* dlogits, int64_t B, int64_t n, int64_t S,
+                            int64_t S_total, int64_t sb, int64_t sc, int64_t ss, float s_nr, float s_dr, float gscale, int dtype, hipStream_t s) {
+    const dim3 g(apply_grid(S * 4, B), (unsigned)B);
+    IN_DISPATCH(T, {
+        hipLaunchKernelGGL((dice_bwd<T>), g, dim3(NT), 0, s, (const T*)logits, labels, stats, (T*)dlogits, (int)B, (int)n, S, s_nr, s_dr, gscale, sb, sc,
+                           ss, S_total);
+    });
+}
 
 // logits element (b, class c, voxel i) at logits[b stride_b + c stride_c + i stride_s] (dlogits alike): N C (D) H W is (n S, S, 1), a
 // channels-last tensor with row stride ld is (S ld, 1, ld)
@@ -787,19 +717,10 @@ extern "C" int ucfvit_dice_ce(const void* logits, const int64_t* labels, float* 
     if (int rc = dice_check("ucfvit_dice_ce", logits, labels, B, n, S, stride_b, stride_c, stride_s, dtype)) return rc;
     UCF_CHECK_ARG(loss && workspace, "ucfvit_dice_ce: null pointer");
     hipStream_t s = (hipStream_t)stream;
-    const int ch = chunks_of(S);
     float* part = (float*)workspace;
-    float* stats = part + B * ch * DSTAT;
-    IN_DISPATCH(T, {
-        hipLaunchKernelGGL((dice_partial<T>), dim3(ch, (unsigned)B), dim3(NT), 0, s, (const T*)logits, labels, part, (int)n, S, ch, stride_b,
-                           stride_c, stride_s);
-        hipLaunchKernelGGL(dice_final, dim3(1), dim3(64), 0, s, part, stats, loss, (int)B, (int)n, S, ch, smooth_nr, smooth_dr);
-        if (dlogits) {
-            const dim3 g(apply_grid(S * 4, B), (unsigned)B);
-            hipLaunchKernelGGL((dice_bwd<T>), g, dim3(NT), 0, s, (const T*)logits, labels, stats, (T*)dlogits, (int)B, (int)n, S, smooth_nr,
-                               smooth_dr, grad_scale, stride_b, stride_c, stride_s, S);
-        }
-    });
+    float* stats = part + B * chunks_of(S) * DSTAT;
+    launch_dice_sums(logits, labels, part, stats, loss, B, n, S, stride_b, stride_c, stride_s, smooth_nr, smooth_dr, dtype, s);
+    if (dlogits) launch_dice_bwd(logits, labels, stats, dlogits, B, n, S, S, stride_b, stride_c, stride_s, smooth_nr, smooth_dr, grad_scale, dtype, s);
     UCF_LAUNCH_CHECK("ucfvit_dice_ce");
     return UCFVIT_OK;
 }
@@ -812,15 +733,9 @@ extern "C" int ucfvit_dice_ce_stats(const void* logits, const int64_t* labels, f
                                     int64_t stride_c, int64_t stride_s, void* workspace, int dtype, void* stream) {
     if (int rc = dice_check("ucfvit_dice_ce_stats", logits, labels, B, n, S, stride_b, stride_c, stride_s, dtype)) return rc;
     UCF_CHECK_ARG(stats && workspace, "ucfvit_dice_ce_stats: null pointer");
-    hipStream_t s = (hipStream_t)stream;
-    const int ch = chunks_of(S);
     float* part = (float*)workspace;
-    float* scratch_loss = part + B * ch * DSTAT;          // (the local loss value is of no use: the first word of the stats area of the workspace)
-    IN_DISPATCH(T, {
-        hipLaunchKernelGGL((dice_partial<T>), dim3(ch, (unsigned)B), dim3(NT), 0, s, (const T*)logits, labels, part, (int)n, S, ch, stride_b,
-                           stride_c, stride_s);
-    });
-    hipLaunchKernelGGL(dice_final, dim3(1), dim3(64), 0, s, part, stats, scratch_loss, (int)B, (int)n, S, ch, 1.0f, 1.0f);
+    float* scratch_loss = part + B * chunks_of(S) * DSTAT;      // (the local loss value is of no use: the first word of the stats area of the workspace)
+    launch_dice_sums(logits, labels, part, stats, scratch_loss, B, n, S, stride_b, stride_c, stride_s, 1.0f, 1.0f, dtype, (hipStream_t)stream);
     UCF_LAUNCH_CHECK("ucfvit_dice_ce_stats");
     return UCFVIT_OK;
 }
@@ -834,13 +749,8 @@ extern "C" int ucfvit_dice_ce_from_stats(const void* logits, const int64_t* labe
     hipStream_t s = (hipStream_t)stream;
     // one "chunk" per batch element = the global sums themselves: the fold rewrites them in place and evaluates the loss
     hipLaunchKernelGGL(dice_final, dim3(1), dim3(64), 0, s, (const float*)stats, stats, loss, (int)B, (int)n, S_total, 1, smooth_nr, smooth_dr);
-    if (dlogits) {
-        IN_DISPATCH(T, {
-            const dim3 g(apply_grid(S * 4, B), (unsigned)B);
-            hipLaunchKernelGGL((dice_bwd<T>), g, dim3(NT), 0, s, (const T*)logits, labels, (const float*)stats, (T*)dlogits, (int)B, (int)n, S,
-                               smooth_nr, smooth_dr, grad_scale, stride_b, stride_c, stride_s, S_total);
-        });
-    }
+    if (dlogits)
+        launch_dice_bwd(logits, labels, stats, dlogits, B, n, S, S_total, stride_b, stride_c, stride_s, smooth_nr, smooth_dr, grad_scale, dtype, s);
     UCF_LAUNCH_CHECK("ucfvit_dice_ce_from_stats");
     return UCFVIT_OK;
 }
@@ -875,7 +785,7 @@ extern "C" int ucfvit_instnorm_cl_bwd_sums(const void* dy, const void* y, const 
     const auto partial = had_res ? incl_bwd_partial<true> : incl_bwd_partial<false>;
     hipLaunchKernelGGL(partial, dim3(ch, (unsigned)B), dim3(NT), 0, s, (const bf16*)dy, (const bf16*)y, (const bf16*)x, mean, rstd, part, S, (int)C,
                        ch, slope, ld_dy / 8);
-    hipLaunchKernelGGL(incl_bwd_final, dim3((unsigned)(B * C)), dim3(64), 0, s, part, m1, m2, S, (int)C, ch);
+    hipLaunchKernelGGL(bwd_means<2>, dim3((unsigned)(B * C)), dim3(64), 0, s, part, Means<2>{{m1, m2}}, S, (int)C, ch);
     UCF_LAUNCH_CHECK("ucfvit_instnorm_cl_bwd_sums");
     return UCFVIT_OK;
 }
@@ -935,7 +845,7 @@ extern "C" int ucfvit_instnorm_cl_bwd2(const void* dy, const void* y, const void
     float* mm = part + B * ch * 3 * C;
     hipLaunchKernelGGL(incl_bwd2_partial, dim3(ch, (unsigned)B), dim3(NT), 0, s, (const bf16*)dy, (const bf16*)y, (const bf16*)x, mean, rstd,
                        (const bf16*)x2, mean2, rstd2, part, S, (int)C, ch, slope, ldg8);
-    hipLaunchKernelGGL(incl_bwd2_final, dim3((unsigned)(B * C)), dim3(64), 0, s, part, mm, S, (int)C, ch, (int)(B * C));
+    hipLaunchKernelGGL(bwd_means<3>, dim3((unsigned)(B * C)), dim3(64), 0, s, part, Means<3>{{mm, mm + B * C, mm + 2 * B * C}}, S, (int)C, ch);
     const dim3 g(cl_apply_grid(S, C, B), (unsigned)B);
     hipLaunchKernelGGL(incl_bwd2_apply, g, dim3(NT), 0, s, (const bf16*)dy, (const bf16*)y, (const bf16*)x, mean, rstd, (const bf16*)x2, mean2, rstd2, mm,
                        (bf16*)dx, (bf16*)dx2, S, (int)C, slope, ldg8, (int)(B * C));
@@ -967,12 +877,9 @@ extern "C" int ucfvit_instnorm_cl_apply(const void* x, const void* res, void* y,
                                         float slope, void* stream) {
     if (int rc = incl_check("ucfvit_instnorm_cl_apply", x, B, S, C)) return rc;
     UCF_CHECK_ARG(y && mean && rstd && ucf_is_aligned16(y) && (!res || ucf_is_aligned16(res)), "ucfvit_instnorm_cl_apply: bad pointer");
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 g(cl_apply_grid(S, C, B), (unsigned)B);
-    if (res)
-        hipLaunchKernelGGL((incl_apply<true>), g, dim3(NT), 0, s, (const bf16*)x, mean, rstd, (const bf16*)res, (bf16*)y, S, (int)C, slope);
-    else
-        hipLaunchKernelGGL((incl_apply<false>), g, dim3(NT), 0, s, (const bf16*)x, mean, rstd, (const bf16*)x, (bf16*)y, S, (int)C, slope);
+    const auto apply = res ? incl_apply<true> : incl_apply<false>;
+    hipLaunchKernelGGL(apply, dim3(cl_apply_grid(S, C, B), (unsigned)B), dim3(NT), 0, (hipStream_t)stream, (const bf16*)x, mean, rstd,
+                       (const bf16*)(res ? res : x), (bf16*)y, S, (int)C, slope);      // without res: a valid pointer that is never read
     UCF_LAUNCH_CHECK("ucfvit_instnorm_cl_apply");
     return UCFVIT_OK;
 }
