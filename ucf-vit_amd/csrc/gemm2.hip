@@ -112,8 +112,8 @@ template <int BR> __device__ __forceinline__ bf16x8 load_frag_ks(const char* lds
 struct KsFrag {
     u32x2 lo, hi;
 };
-template <int BR, int C> __device__ __forceinline__ void load_frag_ks_asm(KsFrag& f, unsigned img, int lane_base, int rbase) {
-    const unsigned a = img + (unsigned)(lane_base ^ (2 * rbase));
+// a = LDS address of the image + (ks_lane_base ^ 2 rbase)
+template <int BR, int C> __device__ __forceinline__ void load_frag_ks_asm(KsFrag& f, unsigned a) {
     asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(f.lo) : "v"(a), "i"(C * 64 * BR));
     asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(f.hi) : "v"(a), "i"(C * 64 * BR + 8 * BR));
 }
@@ -477,6 +477,13 @@ template <int NP> struct GroupsT {
 
 typedef GroupsT<GROUP_MAX> Groups3;
 
+// Which instantiations of gemm3_kernel run the bulk of a tile's K loop in the tight loop (see there): every one that was not slower
+// with it in both alternations of tools/block_gemm_bench.py at the ViT-L/16 batch-665 shapes (profiles/gemm3_bulk_loop.md).  The
+// plain epilogue with column sums (the projection's data gradient, K = 1024) was, by 1 %: it keeps the general step throughout.
+template <int LA, int LB, typename OutT, int EPI, bool CS> struct Gemm3Bulk {
+    static constexpr bool value = !(EPI == EPI_PLAIN && CS);
+};
+
 template <int LA, int LB, typename OutT, int EPI = EPI_GENERIC, bool CS = false, int NP = GROUP_MAX>
 __global__ __launch_bounds__(512) void gemm3_kernel(GroupsT<NP> gt, int K, Epi2 ep, int k_per_split) {
     constexpr int BM = 256, BN = 256, WN = 4, TM = 128, TN = 64, FM = 8, FN = 4;
@@ -587,14 +594,14 @@ __global__ __launch_bounds__(512) void gemm3_kernel(GroupsT<NP> gt, int K, Epi2 
 #pragma unroll
             for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-#define PP_READ(bufA_, bufB_, c_)                                                              \
+#define PP_READ(bufA_, bufB_, c_, KSA_, KSB_)                                                  \
     do {                                                                                       \
         _Pragma("unroll") for (int j = 0; j < FN; ++j) {                                       \
-            if constexpr (LB == UCFVIT_LAYOUT_KS) load_frag_ks_asm<BN, c_>(kb[j], lds_addr(bufB_), ksB, wn + 16 * j); \
+            if constexpr (LB == UCFVIT_LAYOUT_KS) load_frag_ks_asm<BN, c_>(kb[j], KSB_(bufB_, j)); \
             else fb[j] = load_frag2<LB, BN>(bufB_, wn + 16 * j, c_, lane);                     \
         }                                                                                      \
         _Pragma("unroll") for (int i = 0; i < FM; ++i) {                                       \
-            if constexpr (LA == UCFVIT_LAYOUT_KS) load_frag_ks_asm<BM, c_>(ka[i], lds_addr(bufA_), ksA, wm + 16 * i); \
+            if constexpr (LA == UCFVIT_LAYOUT_KS) load_frag_ks_asm<BM, c_>(ka[i], KSA_(bufA_, i)); \
             else fa[i] = load_frag2<LA, BM>(bufA_, wm + 16 * i, c_, lane);                     \
         }                                                                                      \
         if constexpr (LA == UCFVIT_LAYOUT_KS || LB == UCFVIT_LAYOUT_KS) {                      \
@@ -636,10 +643,79 @@ __global__ __launch_bounds__(512) void gemm3_kernel(GroupsT<NP> gt, int K, Epi2 
 #define PP_ISSUE_B(kt_) PP_ISSUE_ONE(LB, BN, Bb, ldb, offB, nBb, nldb, nn0, nN, A_BYTES, kt_)
 #define PP_ISSUE_A(kt_) PP_ISSUE_ONE(LA, BM, Ab, lda, offA, nAb, nlda, nm0, nM, 0, kt_)
 
-        // One program for both groups; G1 runs it one barrier interval behind G0 (extra barrier before / after the loop).
+        // One program for both groups; G1 runs it one barrier interval behind G0 (extra barrier before / after the loops).
         if (grp == 1) PP_BARRIER();
+        int kt = 0;
+        // ---- the bulk of the tile: steps 0 .. nk-3.  K-tile kt+1 is a whole tile of the CURRENT output tile, so nothing is decided
+        // per step: the DMA issue comes first (SGPR base + the loop-invariant 32-bit lane offsets; the bases advance by a constant),
+        // then the same READ / BARRIER / COMPUTE sequence as the general step below.  (Kept apart from it for the reason gemm5_kernel
+        // keeps its bulk loop apart: the general step's bookkeeping is scalar work in front of the DMA issue that paces the K step,
+        // and the next tile's offsets and addresses stayed live in 32 VGPRs across every step.)  nk is workgroup-uniform: all 8 waves
+        // take the same trip counts, and both loops have four barriers per step.
+        if constexpr (Gemm3Bulk<LA, LB, OutT, EPI, CS>::value) {
+            const char* kB = Bb + k_byte_off<LB>(k_begin + BK2, ldb);
+            const char* kA = Ab + k_byte_off<LA>(k_begin + BK2, lda);
+            const int64_t stepB = k_byte_off<LB>(BK2, ldb), stepA = k_byte_off<LA>(BK2, lda);
+            // KS operands: the fragment addresses (ks_lane_base ^ 2 rbase, + the image of the buffer being read) stay in registers and
+            // move to the other buffer at the end of a step
+            unsigned ksFA[FM], ksFB[FN];
+            int ks_flip = (it & 1) ? -BUF : BUF;
+            if constexpr (LA == UCFVIT_LAYOUT_KS) {
+#pragma unroll
+                for (int i = 0; i < FM; ++i) ksFA[i] = lds_addr(smem + (it & 1) * BUF) + (unsigned)(ksA0 ^ (2 * (wm + 16 * i)));
+            }
+            if constexpr (LB == UCFVIT_LAYOUT_KS) {
+#pragma unroll
+                for (int j = 0; j < FN; ++j) ksFB[j] = lds_addr(smem + (it & 1) * BUF + A_BYTES) + (unsigned)(ksB0 ^ (2 * (wn + 16 * j)));
+            }
+#define KS_AT_A(bufA_, i_) ksFA[i_]
+#define KS_AT_B(bufB_, j_) ksFB[j_]
+            // One copy of the loop per wave group, so that G1's wait for its B half is not a branch inside the step.  The lane offsets
+            // pass through an empty asm in the step: the address is then formed as SGPR base + zero-extended 32-bit VGPR where the
+            // instruction is selected (saddr form), not as a 64-bit VGPR pair kept across the loop.
+#define PP_BULK_LOOP(WAIT_B_)                                                                  \
+    _Pragma("clang loop unroll(disable)") for (; kt < nk - 2; ++kt, ++it) {                    \
+        const char* bufA = smem + (it & 1) * BUF;                                              \
+        const char* bufB = bufA + A_BYTES;                                                     \
+        char* nb = smem + ((it + 1) & 1) * BUF;                                                \
+        _Pragma("unroll") for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(offB[i]), "+v"(offA[i])); \
+        issue_half<BN>(kB, offB, nb + A_BYTES, grp, w4);                                       \
+        issue_half<BM>(kA, offA, nb, grp, w4);                                                 \
+        kB += stepB;                                                                           \
+        kA += stepA;                                                                           \
+        PP_READ(bufA, bufB, 0, KS_AT_A, KS_AT_B);                                              \
+        PP_BARRIER();                                                                          \
+        PP_COMPUTE();                                                                          \
+        PP_BARRIER();                                                                          \
+        PP_READ(bufA, bufB, 1, KS_AT_A, KS_AT_B);                                              \
+        WAIT_B_;                                                                               \
+        PP_BARRIER();                                                                          \
+        PP_COMPUTE();                                                                          \
+        if constexpr (LA == UCFVIT_LAYOUT_KS) {                                                \
+            _Pragma("unroll") for (int i = 0; i < FM; ++i) ksFA[i] += ks_flip;                 \
+        }                                                                                      \
+        if constexpr (LB == UCFVIT_LAYOUT_KS) {                                                \
+            _Pragma("unroll") for (int j = 0; j < FN; ++j) ksFB[j] += ks_flip;                 \
+        }                                                                                      \
+        ks_flip = -ks_flip;                                                                    \
+        PP_WAIT_DMA();                                                                         \
+        PP_BARRIER();                                                                          \
+    }
+            if (grp == 1) {
+                PP_BULK_LOOP(PP_WAIT_B());
+            } else {
+                PP_BULK_LOOP((void)0);
+            }
+#undef PP_BULK_LOOP
+#undef KS_AT_A
+#undef KS_AT_B
+        }
+        // ---- the last two steps of the tile (all of it when the bulk loop is off): the ragged last K-tile, the prefetch of the next
+        // tile's first K-tile with that tile's offsets, the general addressing
+#define KS_XOR_A(bufA_, i_) (lds_addr(bufA_) + (unsigned)(ksA ^ (2 * (wm + 16 * (i_)))))
+#define KS_XOR_B(bufB_, j_) (lds_addr(bufB_) + (unsigned)(ksB ^ (2 * (wn + 16 * (j_)))))
 #pragma clang loop unroll(disable)
-        for (int kt = 0; kt < nk; ++kt, ++it) {
+        for (; kt < nk; ++kt, ++it) {
             const char* bufA = smem + (it & 1) * BUF;
             const char* bufB = bufA + A_BYTES;
             int ksA = ksA0, ksB = ksB0;
@@ -647,11 +723,11 @@ __global__ __launch_bounds__(512) void gemm3_kernel(GroupsT<NP> gt, int K, Epi2 
             if constexpr (LB == UCFVIT_LAYOUT_KS) asm volatile("" : "+v"(ksB));   // recomputed, not hoisted into 12 live VGPRs
             PP_ISSUE_B(kt);                 // MEM(c0): DMA of this group's half of the next B tile (read by BOTH groups) ...
             PP_ISSUE_A(kt);                 // ... and of its OWN rows of the next A tile (that region was last read in MEM(c1) of the tile before)
-            PP_READ(bufA, bufB, 0);
+            PP_READ(bufA, bufB, 0, KS_XOR_A, KS_XOR_B);
             PP_BARRIER();
             PP_COMPUTE();                   // COMPUTE(c0)
             PP_BARRIER();
-            PP_READ(bufA, bufB, 1);         // MEM(c1): fragment reads only
+            PP_READ(bufA, bufB, 1, KS_XOR_A, KS_XOR_B);         // MEM(c1): fragment reads only
             if (grp == 1) PP_WAIT_B();      // G1's B half (issued 2 intervals ago) must be visible before G0's next MEM(c0); its A pieces stay in flight
             PP_BARRIER();
             PP_COMPUTE();                   // COMPUTE(c1)
@@ -659,6 +735,8 @@ __global__ __launch_bounds__(512) void gemm3_kernel(GroupsT<NP> gt, int K, Epi2 
             PP_BARRIER();
         }
         if (grp == 0) PP_BARRIER();
+#undef KS_XOR_A
+#undef KS_XOR_B
 #undef PP_READ
 #undef PP_COMPUTE
 #undef PP_SELECT
