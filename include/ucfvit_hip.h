@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define UCFVIT_ABI_VERSION 20
+#define UCFVIT_ABI_VERSION 21
 
 #define UCFVIT_OK 0
 #define UCFVIT_ERR_INVALID_ARGUMENT (-1)
@@ -440,6 +440,25 @@ int ucfvit_dice_ce_stats(const void* logits, const int64_t* labels, float* stats
 int ucfvit_dice_ce_from_stats(const void* logits, const int64_t* labels, float* stats, float* loss, void* dlogits, int64_t B, int64_t n, int64_t S,
                               int64_t S_total, int64_t stride_b, int64_t stride_c, int64_t stride_s, float smooth_nr, float smooth_dr,
                               float grad_scale, int dtype, void* stream);
+
+/* Segmentation and Dice-accuracy counts of logits [B][n][S] (2 <= n <= 8) against int64 labels [B][S] in one pass (csrc/seg_metric.hip;
+ * reference train_unetr_simple.py:399-401,453-460 and inference_unetr_simple.py: torch.argmax, one_hot, monai DiceMetric):
+ *   pred   uint8 [B][S] dense (may be NULL): argmax over the classes as torch.argmax(dim = 1) takes it: the FIRST maximal class wins a
+ *          tie, a NaN counts as maximal and the first NaN wins, +-inf are ordinary values;
+ *   counts int64 [B][3][8]: per batch element and class c  TP[c] = #voxels with argmax == c and label == c, PRED[c] = #voxels with
+ *          argmax == c, LAB[c] = #voxels with label == c; classes >= n hold exact zeros.
+ * A label outside [0, n) adds to no LAB and no TP entry; its voxel still gets a prediction and a PRED count (the reference's one_hot
+ * would raise, which needs a host synchronisation).  All counts are integers: no floating point, no atomics, the same bits on every call.
+ * Addressing, dtype (fp32 or bf16) and limits (B in 1..65535) are ucfvit_dice_ce's: element (b, c, i) at logits[b stride_b + c stride_c +
+ * i stride_s].  Channels-last (stride_c == 1, rows ld >= n apart) and N C (D) H W (stride_s == 1) have kernels that load and store whole
+ * vectors where base and strides are aligned for them; everything else runs one voxel per lane.  ucfvit_seg_counts_route writes the name of
+ * the kernel a call would take ("cl nv<2|4|8> ...", "ncs vpt8 ...", "scalar ...") and its constants to out (at most cap bytes with the
+ * terminator) and returns the length of the whole name.  workspace: ucfvit_seg_counts_workspace(B, S) bytes. */
+int64_t ucfvit_seg_counts_workspace(int64_t B, int64_t S);
+int ucfvit_seg_counts(const void* logits, const int64_t* labels, uint8_t* pred, int64_t* counts, int64_t B, int64_t n, int64_t S, int64_t stride_b,
+                      int64_t stride_c, int64_t stride_s, void* workspace, int dtype, void* stream);
+int ucfvit_seg_counts_route(const void* logits, const int64_t* labels, const uint8_t* pred, int64_t B, int64_t n, int64_t S, int64_t stride_b,
+                            int64_t stride_c, int64_t stride_s, int dtype, char* out, int64_t cap);
 
 /* ------------------------------------------------------------------------------------------------------
  * SAP segmentation head (reference simple/arch.py:491-536): ConvTranspose{2,3}d(D -> K, kernel = stride = p, no bias) followed by a 1x1

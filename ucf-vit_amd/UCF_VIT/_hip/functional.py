@@ -988,6 +988,14 @@ def dice_ce(logits, labels, smooth_nr=1e-5, smooth_dr=1e-5):
     return DiceCEFn.apply(logits, labels, smooth_nr, smooth_dr)
 
 
+def segment(logits, labels):
+    """logits [B, n, *spatial], labels int64 [B, *spatial] or [B, 1, *spatial] -> (pred uint8 [B, *spatial], counts int64 [B, 3, n]): the argmax
+    label map and the per-(batch element, class) TP / PRED / LAB counts of a Dice accuracy (utils.metrics.dice_from_counts), one HIP pass
+    (ops.seg_counts).  No gradient flows through either result; the inputs need none."""
+    with torch.no_grad():
+        return ops.seg_counts(logits.detach(), labels.detach(), want_pred=True)
+
+
 def dice_bce(logits, targets, weight=0.5, smooth=1.0):
     return DiceBCEFn.apply(logits, targets, float(weight), float(smooth))
 

@@ -14,7 +14,7 @@ GEMM_SCHED_BYTES = 1024
 # loss-scaler state block (UCFVIT_GS_* of include/ucfvit_hip.h)
 GS_SCALE, GS_INV_SCALE, GS_FOUND_INF, GS_GROWTH_TRACKER, GS_APPLIED_STEPS, GS_SKIPPED_STEPS = 0, 1, 2, 3, 4, 5
 GS_GROWTH_FACTOR, GS_BACKOFF_FACTOR, GS_GROWTH_INTERVAL, GS_MIN_SCALE, GS_STATE_FLOATS = 6, 7, 8, 9, 16
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))  # .../ucf-vit_amd
 # UCFVIT_HIP_LIB: an alternative build of the same library (A/B measurements of kernel variants); never a non-HIP fallback
@@ -89,6 +89,9 @@ SIGNATURES = {
     "ucfvit_dice_ce_stats_floats": (c_int, []),
     "ucfvit_dice_ce_stats": (c_int, [_P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _I, _P]),
     "ucfvit_dice_ce_from_stats": (c_int, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _F, _F, _F, _I, _P]),
+    "ucfvit_seg_counts_workspace": (_I64, [_I64, _I64]),
+    "ucfvit_seg_counts": (c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _I, _P]),
+    "ucfvit_seg_counts_route": (c_int, [_P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I, c_char_p, _I64]),
     "ucfvit_sap_fold": (c_int, [_P, _P, _P, _I64, _I64, _I64, _I64, _I, _P]),
     "ucfvit_sap_unfold_workspace": (_I64, [_I64, _I64, _I64]),
     "ucfvit_sap_unfold": (c_int, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P]),

@@ -700,6 +700,51 @@ def dice_ce_from_stats(logits, labels, stats, S_total, smooth_nr=1e-5, smooth_dr
     return loss, dl
 
 
+def _seg_args(logits, labels):
+    """the operands of ucfvit_seg_counts: logits read in place where dice_strides knows their layout (at storage offset 0, as DiceCEFn.forward
+    takes them), else a dense copy; labels [B, *spatial] or [B, 1, *spatial] -> (logits, labels, B, n, S, strides)"""
+    if logits.dim() < 3:
+        raise ValueError("seg_counts: logits must be [B, n, *spatial]")
+    if not (logits.is_contiguous() or (logits.storage_offset() == 0 and dice_strides(logits) is not None)):
+        logits = logits.contiguous()
+    if labels.dim() == logits.dim() and labels.shape[1] == 1:
+        labels = labels.view(labels.shape[0], *labels.shape[2:])
+    if tuple(labels.shape) != (logits.shape[0], *logits.shape[2:]):
+        raise ValueError("seg_counts: labels must be [B, *spatial] or [B, 1, *spatial] of the logits' volume")
+    if not labels.is_contiguous():
+        labels = labels.contiguous()
+    _dice_labels(logits, labels, "seg_counts")
+    B, n, S, strides = _dice_layout(logits)
+    return logits, labels, B, n, S, strides
+
+
+def seg_counts(logits, labels, want_pred=True):
+    """logits [B, n, *spatial] fp32 or bf16 (2 <= n <= 8), labels int64 [B, *spatial] or [B, 1, *spatial] ->
+    (pred uint8 [B, *spatial] = torch.argmax(logits, 1), or None; counts int64 [B, 3, n] = (TP, PRED, LAB) per batch element and class).
+    One pass (ucfvit_seg_counts); the HIP decoder's padded channels-last view is read in place.  A label outside [0, n) is in no LAB / TP count."""
+    L = _l.load()
+    logits, labels, B, n, S, (sb, sc, ss) = _seg_args(logits, labels)
+    pred = torch.empty((B, *logits.shape[2:]), dtype=torch.uint8, device=logits.device) if want_pred else None
+    counts = torch.empty((B, 3, 8), dtype=torch.int64, device=logits.device)
+    ws = workspace(L.ucfvit_seg_counts_workspace(B, S), logits.device)
+    _l.check(L.ucfvit_seg_counts(logits.data_ptr(), labels.data_ptr(), _p(pred), counts.data_ptr(), B, n, S, sb, sc, ss, ws.data_ptr(), dt(logits),
+                                 _stream()), "ucfvit_seg_counts")
+    return pred, counts[:, :, :n]
+
+
+def seg_counts_route(logits, labels, want_pred=True):
+    """the name of the kernel seg_counts takes for these operands (ucfvit_seg_counts_route); the prediction buffer is taken as torch allocates it"""
+    import ctypes
+    L = _l.load()
+    logits, labels, B, n, S, (sb, sc, ss) = _seg_args(logits, labels)
+    pred = torch.empty((B, *logits.shape[2:]), dtype=torch.uint8, device=logits.device) if want_pred else None
+    buf = ctypes.create_string_buffer(96)
+    rc = L.ucfvit_seg_counts_route(logits.data_ptr(), labels.data_ptr(), _p(pred), B, n, S, sb, sc, ss, dt(logits), buf, len(buf))
+    if rc < 0:
+        _l.check(rc, "ucfvit_seg_counts_route")
+    return buf.value.decode()
+
+
 # ------------------------------------------------------------------------------------------------ SAP head and Dice + BCE
 def _sap_dims(p, s, nd):
     if nd not in (2, 3) or p < 1 or s < 1:

@@ -139,9 +139,9 @@ class SyntheticSeqLoader:
             yield seq.to(dev, non_blocking=True), torch.cat([size, pos], dim=-1).to(dev, non_blocking=True), label.to(dev, non_blocking=True)
 
 
-def save_checkpoint(conf, epoch, model, optimizer, scheduler, loss_list, rank, scaler=None):
+def save_checkpoint(conf, epoch, model, optimizer, scheduler, loss_list, rank, scaler=None, extra=None):
     """alternating <name>_even.ckpt / _odd.ckpt on rank 0 (reference :364-388), same dictionary keys; with an active loss scaler also
-    `scaler_state_dict`"""
+    `scaler_state_dict`; `extra`: further entries of one script (train_unetr_simple.py's `dice_list`)"""
     t = conf["trainer"]
     if rank == 0:
         os.makedirs(t["checkpoint_path"], exist_ok=True)
@@ -149,6 +149,8 @@ def save_checkpoint(conf, epoch, model, optimizer, scheduler, loss_list, rank, s
               "scheduler_state_dict": scheduler.state_dict(), "loss_list": loss_list}
         if scaler is not None and scaler.is_enabled():
             ck["scaler_state_dict"] = scaler.state_dict()
+        if extra:
+            ck.update(extra)
         torch.save(ck,
                    os.path.join(t["checkpoint_path"], f"{t['checkpoint_filename']}_{'even' if epoch % 2 == 0 else 'odd'}.ckpt"))
     dist.barrier()
@@ -189,8 +191,9 @@ def load_pretrained_mae_encoder(model, mae_state_dict):
     return copied
 
 
-def maybe_resume(conf, model, optimizer, scheduler, scaler=None):
-    """a checkpoint written without a loss scaler resumes under one with the scaler's initial scale"""
+def maybe_resume(conf, model, optimizer, scheduler, scaler=None, extras=None):
+    """a checkpoint written without a loss scaler resumes under one with the scaler's initial scale; `extras`: a dict whose keys are read from
+    the checkpoint where it has them (save_checkpoint's `extra`), its values being the defaults"""
     t = conf["trainer"]
     if not t.get("resume_from_checkpoint", False):
         return 0, []
@@ -200,6 +203,8 @@ def maybe_resume(conf, model, optimizer, scheduler, scaler=None):
     scheduler.load_state_dict(ck["scheduler_state_dict"])
     if scaler is not None and scaler.is_enabled() and ck.get("scaler_state_dict"):
         scaler.load_state_dict(ck["scaler_state_dict"])
+    for k in (extras or {}):
+        extras[k] = ck.get(k, extras[k])
     return ck["epoch"] + 1, ck["loss_list"]
 
 
