@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define UCFVIT_ABI_VERSION 21
+#define UCFVIT_ABI_VERSION 22
 
 #define UCFVIT_OK 0
 #define UCFVIT_ERR_INVALID_ARGUMENT (-1)
@@ -296,6 +296,49 @@ int ucfvit_octree_build(const uint8_t* domain, int32_t* nodes, int32_t* values, 
                         int norm_factor, void* workspace, void* stream);
 int ucfvit_octree_serialize(const float* img, const int32_t* nodes, const int32_t* count, float* seq, int64_t B, int64_t N, int64_t C,
                             int64_t L, int64_t p, void* stream);
+
+/* Label serializers and tree deserializers: the two tree operations between the patcher and a segmentation loss / metric (reference
+ * quadtree.py:176-221 + Rect.set_area, octree.py:152-213 + Cube.set_area; one image and one Python loop per call there).  nodes / count as the
+ * builders above leave them.  Padding rows (s >= count[b]), empty leaves (any extent <= 0) and nodes whose box leaves the image read nothing:
+ * the serializers give them class 0 (the reference's zero patch followed by F.one_hot), the deserializers write nothing for them.
+ * Limits as above: H, W < 32768; N <= 256; 1 <= num_classes <= 255; 1 <= C <= 255; a request outside them returns an error and launches nothing.
+ *
+ * ucfvit_quadtree_serialize_labels: labels [B][H][W], uint8 or int64 by `label_dtype`; every leaf's region resampled to p x p by the
+ *     cv2.resize(INTER_NEAREST) rule: source column = min((px * w) / p, w - 1) in integer arithmetic, rows alike.
+ *     idx int64 [B][L][p][p] (class indices) and / or onehot fp32 [B][num_classes][L * p * p] (the memory order of the reference's collate
+ *     output, datamodule.py:40-51, that training_step_adaptive reshapes plainly); a null pointer skips one of them.  A label >= num_classes or
+ *     < 0 is written unchanged to idx and gives an all-zero one-hot column.
+ * ucfvit_octree_serialize_labels: labels [B][N][N][N] ([z][y][x]), nodes [B][L][6], idx [B][L][p][p][p], onehot [B][num_classes][L * p^3].
+ *     Rule per axis: scipy RegularGridInterpolator(method='nearest') on linspace(0, n, n) queried at linspace(0, n, p): position
+ *     f = j (n-1) / (p-1), cell i = min(floor(f), n-2), take i if the fraction is <= 1/2, else i+1, evaluated in exact integer arithmetic
+ *     (2 (j (n-1) - i (p-1)) <= p-1); p = 1 and n = 1 take voxel 0.  TIES GO TO THE LOWER INDEX: an even p has no ties and equals scipy on
+ *     every sample; for an odd p scipy's double arithmetic sends some exact midpoints up (n = 4, p = 3: scipy [0, 2, 3], this rule [0, 1, 3]).
+ * ucfvit_quadtree_deserialize: seq fp32 read in place, element (b, c, s, e = py * p + px) at b stride_b + c stride_c + s stride_s + e stride_e
+ *     (the reference's patch list [B][L][p][p][C] and the model's [B][C][L][p*p] both without a copy); out fp32, element (b, c, pixel = y W + x)
+ *     at b out_b + c out_c + pixel out_pixel, which must be dense [B][C][H][W] or dense [B][H][W][C].  The output is zero-filled first; then
+ *     every valid leaf region is its p x p patch resized to (w, h): mode UCFVIT_RESAMPLE_SMOOTH by the rule of ucfvit_quadtree_serialize
+ *     (A = -0.75, half-pixel centres, taps clamped to the patch, no anti-aliasing), with `trunc` != 0 after truncf of every tap (the
+ *     reference's seq.astype(int), quadtree.py:213); mode UCFVIT_RESAMPLE_NEAREST by patch column = min((x * p) / w, p - 1), which keeps class
+ *     maps and one-hot planes exact.  Overlapping leaves are outside the contract (a tree never produces them).
+ * ucfvit_octree_deserialize: the same for [p][p][p] patches (e = (pz * p + py) * p + px) into [B][C][N][N][N] or [B][N][N][N][C]:
+ *     UCFVIT_RESAMPLE_SMOOTH is aligned-corner trilinear (Cube.set_area: linspace(0, p, p) onto linspace(0, p, n)), UCFVIT_RESAMPLE_NEAREST the
+ *     integer grid rule above with patch and leaf exchanged.  No trunc (the reference commented it out in 3-D).
+ * Parity: the 3-D rules are pinned against the reference with scipy (tests/golden/tree_labels.npz); the 2-D rules are parity UNPINNED, like
+ *     ucfvit_quadtree_serialize (no cv2 to record from); the nearest rules coincide with any implementation whenever w / p or p / w is whole. */
+#define UCFVIT_LABEL_U8 0
+#define UCFVIT_LABEL_I64 1
+#define UCFVIT_RESAMPLE_SMOOTH 0
+#define UCFVIT_RESAMPLE_NEAREST 1
+int ucfvit_quadtree_serialize_labels(const void* labels, const int32_t* nodes, const int32_t* count, int64_t* idx, float* onehot, int64_t B,
+                                     int64_t H, int64_t W, int64_t L, int64_t p, int64_t num_classes, int label_dtype, void* stream);
+int ucfvit_octree_serialize_labels(const void* labels, const int32_t* nodes, const int32_t* count, int64_t* idx, float* onehot, int64_t B,
+                                   int64_t N, int64_t L, int64_t p, int64_t num_classes, int label_dtype, void* stream);
+int ucfvit_quadtree_deserialize(const float* seq, const int32_t* nodes, const int32_t* count, float* out, int64_t B, int64_t H, int64_t W,
+                                int64_t C, int64_t L, int64_t p, int64_t stride_b, int64_t stride_c, int64_t stride_s, int64_t stride_e,
+                                int64_t out_b, int64_t out_c, int64_t out_pixel, int mode, int trunc, void* stream);
+int ucfvit_octree_deserialize(const float* seq, const int32_t* nodes, const int32_t* count, float* out, int64_t B, int64_t N, int64_t C,
+                              int64_t L, int64_t p, int64_t stride_b, int64_t stride_c, int64_t stride_s, int64_t stride_e, int64_t out_b,
+                              int64_t out_c, int64_t out_pixel, int mode, void* stream);
 
 /* Variable aggregation (VariableMapping_Attention, simple/building_blocks.py:301-373, called by VIT.aggregate_variables,
  * simple/arch.py:414-432) with one aggregated variable: for every token row r and head h,

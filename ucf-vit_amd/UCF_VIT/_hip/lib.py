@@ -14,7 +14,10 @@ GEMM_SCHED_BYTES = 1024
 # loss-scaler state block (UCFVIT_GS_* of include/ucfvit_hip.h)
 GS_SCALE, GS_INV_SCALE, GS_FOUND_INF, GS_GROWTH_TRACKER, GS_APPLIED_STEPS, GS_SKIPPED_STEPS = 0, 1, 2, 3, 4, 5
 GS_GROWTH_FACTOR, GS_BACKOFF_FACTOR, GS_GROWTH_INTERVAL, GS_MIN_SCALE, GS_STATE_FLOATS = 6, 7, 8, 9, 16
-ABI_VERSION = 21
+# label dtypes and resampling modes of the label serializers / tree deserializers (UCFVIT_LABEL_*, UCFVIT_RESAMPLE_*)
+LABEL_U8, LABEL_I64 = 0, 1
+RESAMPLE_SMOOTH, RESAMPLE_NEAREST = 0, 1
+ABI_VERSION = 22
 
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))  # .../ucf-vit_amd
 # UCFVIT_HIP_LIB: an alternative build of the same library (A/B measurements of kernel variants); never a non-HIP fallback
@@ -78,6 +81,10 @@ SIGNATURES = {
     "ucfvit_octree_serialize": (c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _P]),
     "ucfvit_quadtree_build": (c_int, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P]),
     "ucfvit_quadtree_serialize": (c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P]),
+    "ucfvit_quadtree_serialize_labels": (c_int, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I, _P]),
+    "ucfvit_octree_serialize_labels": (c_int, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I, _P]),
+    "ucfvit_quadtree_deserialize": (c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I, _I, _P]),
+    "ucfvit_octree_deserialize": (c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I, _P]),
     "ucfvit_adaptive_pos_fwd": (c_int, [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I, _I, _I, _P]),
     "ucfvit_adaptive_pos_bwd_workspace": (_I64, [_I64, _I64, _I64, _I, _I, _I]),
     "ucfvit_adaptive_pos_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I, _I, _I, _P, _I, _P]),

@@ -557,6 +557,113 @@ def octree_serialize(img, nodes, count, patch, flat=True):
     return seq.view(B, C, S, patch ** 3) if flat else seq
 
 
+_LABEL_DT = {torch.uint8: _l.LABEL_U8, torch.int64: _l.LABEL_I64}
+
+
+def _serialize_labels(name, nd, labels, nodes, count, patch, num_classes, want_idx, want_onehot):
+    L = _l.load()
+    _chk(labels, f"{name}.labels"), _chk(nodes, f"{name}.nodes"), _chk(count, f"{name}.count")
+    if labels.dtype not in _LABEL_DT or labels.dim() != nd + 1 or nodes.dtype != torch.int32 or nodes.dim() != 3 or \
+            nodes.shape[2] != 2 * nd or count.dtype != torch.int32 or count.dim() != 1:
+        raise TypeError(f"{name}: labels uint8 or int64 [B, {', '.join('HW' if nd == 2 else 'NNN')}], nodes int32 [B, L, {2 * nd}], count int32 [B]")
+    if nd == 3 and not (labels.shape[1] == labels.shape[2] == labels.shape[3]):
+        raise TypeError(f"{name}: labels must be a batch of cubic volumes [B, N, N, N]")
+    if nodes.shape[0] != labels.shape[0] or count.shape[0] != labels.shape[0]:
+        raise ValueError(f"{name}: labels, nodes and count must share the batch size")
+    if not (want_idx or want_onehot):
+        raise ValueError(f"{name}: nothing to compute (want_idx and want_onehot are both False)")
+    B, S = labels.shape[0], nodes.shape[1]
+    patch, num_classes = int(patch), int(num_classes)
+    if patch < 1 or not 1 <= num_classes <= 255:
+        raise ValueError(f"{name}: need patch >= 1 and 1 <= num_classes <= 255 (got {patch}, {num_classes})")
+    P = patch ** nd
+    idx = torch.empty((B, S) + (patch,) * nd, dtype=torch.int64, device=labels.device) if want_idx else None
+    onehot = torch.empty((B, num_classes, S * P), dtype=torch.float32, device=labels.device) if want_onehot else None
+    dims = labels.shape[1:3] if nd == 2 else labels.shape[1:2]
+    fn = L.ucfvit_quadtree_serialize_labels if nd == 2 else L.ucfvit_octree_serialize_labels
+    _l.check(fn(labels.data_ptr(), nodes.data_ptr(), count.data_ptr(), _p(idx), _p(onehot), B, *dims, S, patch, num_classes,
+                _LABEL_DT[labels.dtype], _stream()), fn.__name__)
+    return idx, onehot
+
+
+def quadtree_serialize_labels(labels, nodes, count, patch, num_classes, want_idx=True, want_onehot=True):
+    """labels uint8 or int64 [B, H, W], nodes / count from quadtree_build -> (idx int64 [B, L, p, p] or None, onehot fp32 [B, nc, L * p * p] or
+    None): every leaf's label region resampled to p x p with the nearest-neighbour rule (ucfvit_quadtree_serialize_labels); padding rows are class 0;
+    the one-hot block is the reference's collated seq_label in the memory order training_step_adaptive reshapes"""
+    return _serialize_labels("quadtree_serialize_labels", 2, labels, nodes, count, patch, num_classes, want_idx, want_onehot)
+
+
+def octree_serialize_labels(labels, nodes, count, patch, num_classes, want_idx=True, want_onehot=True):
+    """labels uint8 or int64 [B, N, N, N], nodes / count from octree_build -> (idx int64 [B, L, p, p, p] or None, onehot fp32 [B, nc, L * p^3] or None)"""
+    return _serialize_labels("octree_serialize_labels", 3, labels, nodes, count, patch, num_classes, want_idx, want_onehot)
+
+
+def _seq_strides(name, nd, seq, patch):
+    """(C, L, element strides (b, c, s, e)) of a token sequence read in place: the patch list [B, L, p, .., p, C] (any strides whose patch axes are
+    jointly regular, e.g. contiguous) or the model layout [B, C, L, p^nd]"""
+    P = patch ** nd
+    if seq.dim() == 4 and seq.shape[3] == P:                                # [B, C, L, P]
+        return seq.shape[1], seq.shape[2], (seq.stride(0), seq.stride(1), seq.stride(2), seq.stride(3))
+    if seq.dim() == nd + 3 and tuple(seq.shape[2:2 + nd]) == (patch,) * nd:  # [B, L, p, .., p, C]
+        st = seq.stride()
+        se = st[1 + nd]
+        if all(st[2 + k] == se * patch ** (nd - 1 - k) for k in range(nd)):
+            return seq.shape[-1], seq.shape[1], (st[0], st[-1], st[1], se)
+        raise RuntimeError(f"{name}: the patch axes of seq must be regularly strided (p * stride of the next axis)")
+    raise TypeError(f"{name}: seq must be [B, C, L, {P}] or [B, L, {', '.join(['p'] * nd)}, C] with p = {patch}")
+
+
+def _deserialize(name, nd, seq, nodes, count, size, patch, mode, truncate, channels_last):
+    L = _l.load()
+    if not seq.is_cuda:
+        raise RuntimeError(f"{name}.seq: expected a tensor on the MI355X (cuda) device, got {seq.device}")
+    _chk(nodes, f"{name}.nodes"), _chk(count, f"{name}.count")
+    if seq.dtype != torch.float32 or nodes.dtype != torch.int32 or nodes.dim() != 3 or nodes.shape[2] != 2 * nd or \
+            count.dtype != torch.int32 or count.dim() != 1:
+        raise TypeError(f"{name}: seq fp32, nodes int32 [B, L, {2 * nd}], count int32 [B]")
+    smooth = "bicubic" if nd == 2 else "trilinear"
+    if mode not in (smooth, "nearest"):
+        raise ValueError(f"{name}: mode must be '{smooth}' or 'nearest', got {mode!r}")
+    patch = int(patch)
+    if patch < 1:
+        raise ValueError(f"{name}: need patch >= 1")
+    C, S, strides = _seq_strides(name, nd, seq, patch)
+    B = seq.shape[0]
+    if nodes.shape[0] != B or nodes.shape[1] != S or count.shape[0] != B:
+        raise ValueError(f"{name}: seq, nodes and count disagree on batch size or sequence length")
+    if min(strides[1:]) <= 0 or (B > 1 and strides[0] <= 0):
+        raise RuntimeError(f"{name}: seq must not be an expanded (zero-stride) view")
+    size = (int(size),) * nd if isinstance(size, int) else tuple(int(v) for v in size)
+    if len(size) != nd or (nd == 3 and len(set(size)) != 1):
+        raise ValueError(f"{name}: size must be (H, W)" if nd == 2 else f"{name}: size must be one side N or (N, N, N)")
+    npix = math.prod(size)
+    out = torch.empty((B, *size, C) if channels_last else (B, C, *size), dtype=torch.float32, device=seq.device)
+    ostr = (npix * C, 1, C) if channels_last else (npix * C, npix, 1)
+    m = _l.RESAMPLE_NEAREST if mode == "nearest" else _l.RESAMPLE_SMOOTH
+    if nd == 2:
+        _l.check(L.ucfvit_quadtree_deserialize(seq.data_ptr(), nodes.data_ptr(), count.data_ptr(), out.data_ptr(), B, size[0], size[1], C, S, patch,
+                                               *strides, *ostr, m, int(bool(truncate)), _stream()), "ucfvit_quadtree_deserialize")
+    else:
+        if truncate:
+            raise ValueError(f"{name}: the 3-D rule has no truncation")
+        _l.check(L.ucfvit_octree_deserialize(seq.data_ptr(), nodes.data_ptr(), count.data_ptr(), out.data_ptr(), B, size[0], C, S, patch, *strides,
+                                             *ostr, m, _stream()), "ucfvit_octree_deserialize")
+    return out
+
+
+def quadtree_deserialize(seq, nodes, count, size, patch, mode="bicubic", truncate=False, channels_last=True):
+    """seq fp32, read in place: the patch list [B, L, p, p, C] or the model layout [B, C, L, p * p] (SAP logits per class); nodes / count from
+    quadtree_build; size = (H, W) -> the image fp32 [B, H, W, C] (channels_last) or [B, C, H, W]: every leaf region is its patch resized to the
+    leaf (ucfvit_quadtree_deserialize: 'bicubic', optionally after truncation of the tokens, or 'nearest'); pixels no leaf covers are 0"""
+    return _deserialize("quadtree_deserialize", 2, seq, nodes, count, size, patch, mode, truncate, channels_last)
+
+
+def octree_deserialize(seq, nodes, count, size, patch, mode="trilinear", channels_last=True):
+    """seq fp32 [B, L, p, p, p, C] or [B, C, L, p^3], nodes / count from octree_build, size = N -> fp32 [B, N, N, N, C] or [B, C, N, N, N]
+    (ucfvit_octree_deserialize: aligned-corner 'trilinear' or 'nearest')"""
+    return _deserialize("octree_deserialize", 3, seq, nodes, count, size, patch, mode, False, channels_last)
+
+
 def cross_entropy(logits, labels, grad_scale=1.0, want_grad=True):
     """returns (loss fp32 scalar tensor, dlogits or None, row_loss)"""
     L = _l.load()

@@ -38,6 +38,22 @@ class Patchify(torch.nn.Module):
         seq_img = ops.quadtree_serialize(img, nodes, count, self.patch_size)
         return seq_img, seq_ps[..., 0], seq_ps[..., 1:], nodes, count
 
+    @torch.no_grad()
+    def serialize_labels(self, labels, nodes, count, num_classes, one_hot=True):
+        """labels uint8 or int64 [B, H, W] through the tree `forward` built (reference quadtree.py:176-207, nearest neighbour per leaf) ->
+        one_hot: fp32 [B, num_classes, fixed_length * patch_size**2], the collated `seq_label` training_step_adaptive reshapes
+        (datamodule.py:40-51); else the class indices int64 [B, fixed_length, patch_size, patch_size].  Padding rows are class 0."""
+        labels = labels if labels.is_contiguous() else labels.contiguous()
+        idx, onehot = ops.quadtree_serialize_labels(labels, nodes, count, self.patch_size, num_classes, want_idx=not one_hot, want_onehot=one_hot)
+        return onehot if one_hot else idx
+
+    @torch.no_grad()
+    def deserialize(self, seq, nodes, count, size, mode="bicubic", truncate=False, channels_last=True):
+        """a token sequence painted back into the image plane (reference quadtree.py:209-221 + Rect.set_area): seq fp32 [B, L, p, p, C] or the
+        model layout [B, C, L, p*p], read in place; size = (H, W) -> fp32 [B, H, W, C] (channels_last) or [B, C, H, W].  mode 'bicubic' is the
+        reference's resize (truncate=True applies its seq.astype(int) first), 'nearest' keeps class maps exact; uncovered pixels are 0."""
+        return ops.quadtree_deserialize(seq, nodes, count, size, self.patch_size, mode=mode, truncate=truncate, channels_last=channels_last)
+
 
 class Patchify_3D(torch.nn.Module):
     """3-D counterpart (reference transform.py:57-132 + octree.py:66-151): forward(vol, domain) -> (seq_img, seq_size, seq_pos, nodes, count)
@@ -63,3 +79,19 @@ class Patchify_3D(torch.nn.Module):
         nodes, _, count, seq_ps = ops.octree_build(domain, self.fixed_length, self.norm_factor)
         seq_img = ops.octree_serialize(vol, nodes, count, self.patch_size)
         return seq_img, seq_ps[..., 0], seq_ps[..., 1:], nodes, count
+
+    @torch.no_grad()
+    def serialize_labels(self, labels, nodes, count, num_classes, one_hot=True):
+        """labels uint8 or int64 [B, N, N, N] through the tree `forward` built (reference octree.py:152-199; scipy's nearest rule, ties to the
+        lower index) -> one_hot: fp32 [B, num_classes, fixed_length * patch_size**3]; else int64 [B, fixed_length, p, p, p]"""
+        labels = labels if labels.is_contiguous() else labels.contiguous()
+        idx, onehot = ops.octree_serialize_labels(labels, nodes, count, self.patch_size, num_classes, want_idx=not one_hot, want_onehot=one_hot)
+        return onehot if one_hot else idx
+
+    @torch.no_grad()
+    def deserialize(self, seq, nodes, count, size, mode="trilinear", truncate=False, channels_last=True):
+        """reference octree.py:201-213 + Cube.set_area: seq fp32 [B, L, p, p, p, C] or [B, C, L, p**3], size = N -> fp32 [B, N, N, N, C] or
+        [B, C, N, N, N]; mode 'trilinear' (aligned corners) or 'nearest'.  The 3-D rule has no truncation (commented out in the reference)."""
+        if truncate:
+            raise ValueError("Patchify_3D.deserialize: the 3-D rule has no truncation")
+        return ops.octree_deserialize(seq, nodes, count, size, self.patch_size, mode=mode, channels_last=channels_last)

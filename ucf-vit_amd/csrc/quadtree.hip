@@ -8,6 +8,7 @@
 // One workgroup per image (build) / per node (serialize); the greedy loop is sequential by definition, the batch supplies the
 // parallelism (166 images = 166 workgroups).  Edge detection (cv2.Canny) is not part of this file: the edge map is an input.
 #include "common.h"
+#include "resample_rules.h"          // cubic_coeffs
 
 namespace {
 
@@ -144,16 +145,6 @@ __global__ __launch_bounds__(256) void quadtree_build_kernel(const unsigned char
             sp[2] = -1.f;
         }
     }
-}
-
-// cubic convolution coefficients, A = -0.75 (cv2.INTER_CUBIC, torch upsample_bicubic2d)
-__device__ __forceinline__ void cubic_coeffs(float t, float (&w)[4]) {
-    constexpr float A = -0.75f;
-    const float x0 = t + 1.f, x1 = t, x2 = 1.f - t, x3 = 2.f - t;
-    w[0] = ((A * x0 - 5.f * A) * x0 + 8.f * A) * x0 - 4.f * A;
-    w[1] = ((A + 2.f) * x1 - (A + 3.f)) * x1 * x1 + 1.f;
-    w[2] = ((A + 2.f) * x2 - (A + 3.f)) * x2 * x2 + 1.f;
-    w[3] = ((A * x3 - 5.f * A) * x3 + 8.f * A) * x3 - 4.f * A;
 }
 
 __global__ __launch_bounds__(256) void quadtree_serialize_kernel(const float* __restrict__ img, const int* __restrict__ nodes,

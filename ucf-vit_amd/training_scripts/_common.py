@@ -99,12 +99,36 @@ class SyntheticSeqLoader:
     label.  When fixed_length fits the tree rule (3n+1 / 7n+1) and the images are square, synthetic images and synthetic edge maps
     go through the GPU quadtree / octree patcher (UCF_VIT.dataloaders.transform); otherwise the sequences are drawn directly."""
 
-    def __init__(self, batch_size, in_chans, img_size, patch_size, fixed_length, num_classes, iters, device, seed):
+    def __init__(self, batch_size, in_chans, img_size, patch_size, fixed_length, num_classes, iters, device, seed, labels_from_image=False):
         nd = len(img_size)
         self.shape = (batch_size, in_chans, fixed_length, patch_size ** nd)
         self.nd, self.img = nd, min(img_size)
         self.square = len(set(img_size)) == 1          # the quadtree / octree patchers work on square images / cubic volumes
         self.num_classes, self.iters, self.device, self.seed = num_classes, iters, device, seed
+        self.labels_from_image = labels_from_image
+        if labels_from_image and not (self.square and fixed_length % (3 if nd == 2 else 7) == 1 and (nd == 2 or self.img <= 256)):
+            raise ValueError("labels_from_image needs the tree patcher: square images / cubic volumes (side <= 256 in 3-D) and a fixed_length of 3n+1 / 7n+1")
+
+    def _patchified_with_labels(self, g):
+        """labels_from_image: a piecewise-constant synthetic image (blocks of side/16), a full-resolution label map = brightness bands of the
+        image BEFORE patching, and both through the same tree: the image by `Patchify.forward`, the label map by `serialize_labels` (the
+        reference's dataset.py:655-716 + collate datamodule.py:40-51).  Yields (seq, seq_ps, (seq_label one-hot [B, nc, S * P], label map
+        int64 [B, *img], nodes, count))"""
+        from UCF_VIT.dataloaders.transform import Patchify, Patchify_3D
+        B, C, S, P = self.shape
+        n, p, nc = self.img, round(P ** (1.0 / self.nd)), self.num_classes
+        dev = self.device
+        blk = max(1, n // 16)
+        coarse = torch.randint(0, 256, (B,) + (-(-n // blk),) * self.nd + (C,), generator=g).float()
+        for ax in range(1, self.nd + 1):
+            coarse = coarse.repeat_interleave(blk, dim=ax).narrow(ax, 0, n)
+        img = coarse.contiguous().to(dev)
+        edges = ((torch.rand((B,) + (n,) * self.nd, generator=g) < 0.02).to(torch.uint8) * 255).to(dev)
+        label_map = torch.clamp((img.mean(dim=-1) / 256.0 * nc).long(), 0, nc - 1)
+        patcher = Patchify(S, p, C) if self.nd == 2 else Patchify_3D(S, p, C)
+        seq, size, pos, nodes, count = patcher(img, edges)
+        seq_label = patcher.serialize_labels(label_map, nodes, count, nc)
+        return seq, torch.cat([size.unsqueeze(-1), pos], dim=-1), (seq_label, label_map, nodes, count)
 
     def _patchified(self, g):
         """synthetic images + synthetic edge maps through the GPU patcher (UCF_VIT.dataloaders.transform, the device-side counterpart
@@ -126,6 +150,9 @@ class SyntheticSeqLoader:
         B, _, S, _ = self.shape
         tree_ok = S % (3 if self.nd == 2 else 7) == 1 and (self.nd == 2 or self.img <= 256)
         for _ in range(self.iters):
+            if self.labels_from_image:
+                yield self._patchified_with_labels(g)
+                continue
             if tree_ok and self.square:
                 seq, seq_ps = self._patchified(g)
                 label = torch.randint(0, max(self.num_classes, 1), (B,), generator=g)

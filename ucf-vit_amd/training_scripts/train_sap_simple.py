@@ -23,7 +23,24 @@ def training_step_adaptive(seq, seq_label, variables, net, patch_size, twoD, num
     seq = torch.reshape(seq, (-1, in_chans) + side)
     seq_label = torch.reshape(seq_label, (-1, num_classes) + side)
     output = net(seq, variables, seq_ps)
-    return DiceBLoss(num_class=num_classes)(output, seq_label)
+    return DiceBLoss(num_class=num_classes)(output, seq_label), output
+
+
+def full_resolution_dice(output, label_map, nodes, count, patch_size, num_classes, fixed_length, twoD):
+    """Dice of a SAP prediction against the label map in the image plane: the pseudo image's plain memory is the logits per class in
+    sequence layout [B, nc, S, P]; the tree paints them back (read in place) into [B, nc, *img] and one HIP pass takes argmax and counts"""
+    from UCF_VIT.dataloaders.transform import Patchify, Patchify_3D
+    from UCF_VIT.utils.metrics import DiceMetric
+    from UCF_VIT._hip import functional as HF
+    with torch.no_grad():
+        logits = output.detach().float().reshape(output.shape[0], num_classes, fixed_length, -1)
+        patcher = (Patchify if twoD else Patchify_3D)(fixed_length, patch_size, num_classes)
+        size = tuple(label_map.shape[1:]) if twoD else label_map.shape[1]
+        full = patcher.deserialize(logits, nodes, count, size, channels_last=False)
+        pred, counts = HF.segment(full, label_map)
+        metric = DiceMetric(include_background=False)
+        metric.update(counts)
+        return metric.aggregate()[0], pred
 
 
 def main(device, local_rank, rank, world):
@@ -42,18 +59,24 @@ def main(device, local_rank, rank, world):
     scheduler = configure_scheduler(optimizer, int(m["warmup_steps"]), int(m["max_steps"]), float(m["warmup_start_lr"]), float(m["eta_min"]))
     epoch_start, loss_list = maybe_resume(conf, net, optimizer, scheduler)
     variables = d["dict_in_variables"][d["dataset"]]
+    # data: labels_from_image: True -- the label map lives in the image plane and reaches the sequence through the image's own tree
+    # (Patchify.serialize_labels), and the epoch line reports the full-resolution Dice of the last batch (deserialize + segment)
+    from_image = bool(d.get("labels_from_image", False))
     loader = SyntheticSeqLoader(d["batch_size"], margs["in_chans"], margs["img_size"], margs["patch_size"], margs["fixed_length"], nc,
-                                iters_per_epoch(conf), device, 1234 + rank)
+                                iters_per_epoch(conf), device, 1234 + rank, labels_from_image=from_image)
     for epoch in range(epoch_start, conf["trainer"]["max_epochs"]):
         model.train()
         epoch_loss = torch.zeros((), device=device)
         timer = StepTimer()
-        for seq, seq_ps, _ in loader:
-            # synthetic per-pixel labels from the data itself (brightness bands), one-hot over the classes, in sequence layout
-            band = torch.clamp((seq.mean(dim=1, keepdim=True) / 256.0 * nc).long(), 0, nc - 1)
-            seq_label = torch.zeros(seq.shape[0], nc, *seq.shape[2:], device=device).scatter_(1, band, 1.0)
-            loss = training_step_adaptive(seq / 255.0, seq_label, variables, net, margs["patch_size"], margs["twoD"], nc, sqrt_len, seq_ps,
-                                          margs["in_chans"])
+        for seq, seq_ps, extra in loader:
+            if from_image:
+                seq_label, label_map, nodes, count = extra
+            else:
+                # synthetic per-pixel labels from the data itself (brightness bands), one-hot over the classes, in sequence layout
+                band = torch.clamp((seq.mean(dim=1, keepdim=True) / 256.0 * nc).long(), 0, nc - 1)
+                seq_label = torch.zeros(seq.shape[0], nc, *seq.shape[2:], device=device).scatter_(1, band, 1.0)
+            loss, output = training_step_adaptive(seq / 255.0, seq_label, variables, net, margs["patch_size"], margs["twoD"], nc, sqrt_len, seq_ps,
+                                                  margs["in_chans"])
             epoch_loss += loss.detach()
             loss.backward()
             optimizer.step()
@@ -61,8 +84,12 @@ def main(device, local_rank, rank, world):
             scheduler.step()
             timer.tick(seq.shape[0] * world)
         loss_list.append(epoch_loss)
+        dice = ""
+        if from_image:
+            mean, _ = full_resolution_dice(output, label_map, nodes, count, margs["patch_size"], nc, margs["fixed_length"], margs["twoD"])
+            dice = f" dice {mean.item():.4f}"
         if rank == 0:
-            print(f"epoch: {epoch} epoch_loss {epoch_loss.item():.4f} images/s {timer.rate():.1f}", flush=True)
+            print(f"epoch: {epoch} epoch_loss {epoch_loss.item():.4f} images/s {timer.rate():.1f}{dice}", flush=True)
         save_checkpoint(conf, epoch, net, optimizer, scheduler, loss_list, rank)
 
 
