@@ -1,4 +1,5 @@
-"""The four kernels of csrc/patcher_labels.hip (label serializers and tree deserializers of the adaptive patcher) element by element, through
+"""The kernels of csrc/patcher_labels.hip (labels_kernel<ND, T> for ND = 2, 3: the label serializers; quadtree_ / octree_deserialize_kernel over one
+leaf walker: the tree deserializers; every case family below exists in both dimensions) element by element, through
 UCF_VIT._hip.ops and, into outputs carved from sentinel-filled allocations, through UCF_VIT._hip.lib.  The references are numpy integer /
 float64 code written here (restating the rules of csrc/resample_rules.h); they never call the project's kernels.  B >= 2 throughout.  U = 2^-24.
 

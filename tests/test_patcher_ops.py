@@ -6,7 +6,9 @@ float64 / Python ints written here; they never call the project's kernels.  The 
 table, so that L = 6394 takes milliseconds.  The oracle's serialize (fp32, square only) is not used.  All inputs are drawn on the CPU from
 seeds; B >= 2 throughout, so a batch-stride error lands in the other image.  U = 2^-24.
 
-Kernels and the cases that reach them (test_tables_reach_every_branch asserts this list from the restated host rules smem_q / smem_o):
+Kernels and the cases that reach them (test_tables_reach_every_branch asserts this list from the restated host rules smem_q / smem_o).  The
+two builders are csrc/patcher_tree.h's tree_refine<ND> / tree_write<ND> for ND = 2 and 3: every branch of that one refinement is reached in
+both dimensions by the q-* and the o-* cases below.
     quadtree_build_kernel      test_tree_build[q-*]: 12x20, 20x12, 7x5, 28x28, 96x160, 3x3, 2x2, 1x1 at L = 1, 4 and an L that stops early,
                                224x224 at L = 1024, 128x128 dense at L = 2728 (65,568 B of LDS: the first L above 64 KiB, hipFuncSetAttribute),
                                256x256 at L = 6394 (153,552 B: the largest accepted L); maps: all 0 (every step a tie), all 255, random 0 / 255,
@@ -122,7 +124,7 @@ def _lib():
 
 # ---- csrc/quadtree.hip restated: node sizes, the LDS rule, the thread count ----------------------------------------------------------------
 NT = 256
-QNODE, ONODE = 12, 16                      # sizeof(QNode) = 4 shorts + int, sizeof(ONode) = 6 shorts + int
+QNODE, ONODE = 12, 16                      # csrc/patcher_tree.h: sizeof(Node<2>) = 4 shorts + int, sizeof(Node<3>) = 6 shorts + int
 
 
 def smem_q(L):

@@ -3,7 +3,8 @@
 
     python tools/asm_diff.py OLD_TREE NEW_TREE --units gemm gemm2 gemm_stagger [--keep DIR]
 
-Compiles ucf-vit_amd/csrc/<unit>.hip of both trees to gfx950 assembly (device side only, the flags of the Makefile) and compares,
+Compiles ucf-vit_amd/csrc/<unit>.hip of both trees to gfx950 assembly (device side only; the Makefile's common flags plus
+the `FLAGS_<unit>` line of each tree's own Makefile, e.g. -ffp-contract=off for patcher_labels, the MFMA form for attention) and compares,
 kernel by kernel, the instruction stream and the .amdhsa_* resource directives (VGPR / AGPR / SGPR counts, LDS size, scratch size).
 What a pure move of code between files legitimately changes is normalised away: the index of the function in the numbers of local
 labels, comments, .file / .ident / .loc directives and the order of the kernels in the file (a device-only compilation spells an
@@ -22,10 +23,19 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=f
 LABEL = re.compile(r"\.L(BB|func_begin|func_end|tmp|JTI)\d+(_\d+)?")
 
 
+def unit_flags(tree, unit):
+    """the unit's own flags: the tree's Makefile line `FLAGS_<unit> := ...`, which the build rule puts behind the common ones"""
+    for line in open(os.path.join(tree, "ucf-vit_amd", "Makefile")):
+        m = re.match(rf"FLAGS_{re.escape(unit)}\s*:?=\s*(.*)", line)
+        if m:
+            return m.group(1).split()
+    return []
+
+
 def compile_unit(tree, unit, out):
     src = os.path.join(tree, "ucf-vit_amd", "csrc", unit + ".hip")
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    subprocess.run([hipcc] + FLAGS + ["-o", out, src], check=True, stderr=subprocess.DEVNULL)
+    subprocess.run([hipcc] + FLAGS + unit_flags(tree, unit) + ["-o", out, src], check=True, stderr=subprocess.DEVNULL)
     return out
 
 

@@ -490,71 +490,64 @@ def varagg_bwd(kv, q, out, lse, dout, V, R, D, head_dim, scale):
 
 
 # ------------------------------------------------------------------------------------------------ quadtree patcher
+def _tree_build(name, nd, domain, fixed_length, *rule):
+    """the builder of a 2^nd-ary tree: domain uint8 [B, H, W] or cubic [B, N, N, N]; rule: what the 3-D entry point takes beside the shape"""
+    L = _l.load()
+    what = "edges" if nd == 2 else "domain"
+    _chk(domain, f"{name}.{what}")
+    if domain.dtype != torch.uint8 or domain.dim() != nd + 1 or (nd == 3 and len(set(domain.shape[1:])) != 1):
+        raise TypeError(f"{name}: edges must be uint8 [B, H, W]" if nd == 2 else
+                        f"{name}: domain must be a batch of cubic uint8 volumes [B, N, N, N]")
+    B, dev = domain.shape[0], domain.device
+    dims = tuple(domain.shape[1:3]) if nd == 2 else (domain.shape[1],)
+    nodes = torch.empty((B, fixed_length, 2 * nd), dtype=torch.int32, device=dev)
+    values = torch.empty((B, fixed_length), dtype=torch.int32, device=dev)
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    seq_ps = torch.empty((B, fixed_length, nd + 1), dtype=torch.float32, device=dev)
+    size, fn = (L.ucfvit_quadtree_workspace, L.ucfvit_quadtree_build) if nd == 2 else (L.ucfvit_octree_workspace, L.ucfvit_octree_build)
+    ws = workspace(size(B, *dims), dev)
+    _l.check(fn(domain.data_ptr(), nodes.data_ptr(), values.data_ptr(), count.data_ptr(), seq_ps.data_ptr(), B, *dims, fixed_length, *rule,
+                ws.data_ptr(), _stream()), fn.__name__)
+    return nodes, values, count, seq_ps
+
+
+def _serialize(name, nd, img, nodes, count, patch):
+    """img fp32 [B, H, W, C] or [B, N, N, N, C] -> the patch list [B, L, p, .., p, C]"""
+    L = _l.load()
+    _chk(img, f"{name}.img"), _chk(nodes, f"{name}.nodes"), _chk(count, f"{name}.count")
+    if img.dtype != torch.float32 or img.dim() != nd + 2 or nodes.dtype != torch.int32 or count.dtype != torch.int32:
+        raise TypeError(f"{name}: img fp32 [B, {'H, W' if nd == 2 else 'N, N, N'}, C], nodes int32 [B, L, {2 * nd}], count int32 [B]")
+    B, C, S = img.shape[0], img.shape[-1], nodes.shape[1]
+    dims = tuple(img.shape[1:3]) if nd == 2 else (img.shape[1],)
+    seq = torch.empty((B, S) + (patch,) * nd + (C,), dtype=torch.float32, device=img.device)
+    fn = L.ucfvit_quadtree_serialize if nd == 2 else L.ucfvit_octree_serialize
+    _l.check(fn(img.data_ptr(), nodes.data_ptr(), count.data_ptr(), seq.data_ptr(), B, *dims, C, S, patch, _stream()), fn.__name__)
+    return seq
+
+
 def quadtree_build(edges, fixed_length):
     """edges uint8 [B, H, W] (0 / 255) -> (nodes int32 [B, L, 4] = (x1, x2, y1, y2), values int32 [B, L], count int32 [B],
     seq_ps fp32 [B, L, 3] = (size, centre x, centre y))"""
-    L = _l.load()
-    _chk(edges, "quadtree_build.edges")
-    if edges.dtype != torch.uint8 or edges.dim() != 3:
-        raise TypeError("quadtree_build: edges must be uint8 [B, H, W]")
-    B, H, W = edges.shape
-    dev = edges.device
-    nodes = torch.empty((B, fixed_length, 4), dtype=torch.int32, device=dev)
-    values = torch.empty((B, fixed_length), dtype=torch.int32, device=dev)
-    count = torch.empty(B, dtype=torch.int32, device=dev)
-    seq_ps = torch.empty((B, fixed_length, 3), dtype=torch.float32, device=dev)
-    ws = workspace(L.ucfvit_quadtree_workspace(B, H, W), dev)
-    _l.check(L.ucfvit_quadtree_build(edges.data_ptr(), nodes.data_ptr(), values.data_ptr(), count.data_ptr(), seq_ps.data_ptr(), B, H, W,
-                                     fixed_length, ws.data_ptr(), _stream()), "ucfvit_quadtree_build")
-    return nodes, values, count, seq_ps
+    return _tree_build("quadtree_build", 2, edges, fixed_length)
 
 
 def quadtree_serialize(img, nodes, count, patch):
     """img fp32 [B, H, W, C], nodes / count from quadtree_build -> x [B, C, L, patch*patch] (the reference's plain reshape of the
     [L, p, p, C] patch list, transform.py:42-48) = the model input of adaptive_patching=True"""
-    L = _l.load()
-    _chk(img, "quadtree_serialize.img"), _chk(nodes, "quadtree_serialize.nodes"), _chk(count, "quadtree_serialize.count")
-    if img.dtype != torch.float32 or img.dim() != 4 or nodes.dtype != torch.int32 or count.dtype != torch.int32:
-        raise TypeError("quadtree_serialize: img fp32 [B, H, W, C], nodes int32 [B, L, 4], count int32 [B]")
-    B, H, W, C = img.shape
-    S = nodes.shape[1]
-    seq = torch.empty((B, S, patch, patch, C), dtype=torch.float32, device=img.device)
-    _l.check(L.ucfvit_quadtree_serialize(img.data_ptr(), nodes.data_ptr(), count.data_ptr(), seq.data_ptr(), B, H, W, C, S, patch, _stream()),
-             "ucfvit_quadtree_serialize")
-    return seq.view(B, C, S, patch * patch)
+    seq = _serialize("quadtree_serialize", 2, img, nodes, count, patch)
+    return seq.view(seq.shape[0], seq.shape[-1], seq.shape[1], patch * patch)
 
 
 def octree_build(domain, fixed_length, norm_factor=255):
     """domain uint8 [B, N, N, N] ([z][y][x]) -> (nodes int32 [B, L, 6], values int32 [B, L], count int32 [B], seq_ps fp32 [B, L, 4])"""
-    L = _l.load()
-    _chk(domain, "octree_build.domain")
-    if domain.dtype != torch.uint8 or domain.dim() != 4 or not (domain.shape[1] == domain.shape[2] == domain.shape[3]):
-        raise TypeError("octree_build: domain must be a batch of cubic uint8 volumes [B, N, N, N]")
-    B, N = domain.shape[0], domain.shape[1]
-    dev = domain.device
-    nodes = torch.empty((B, fixed_length, 6), dtype=torch.int32, device=dev)
-    values = torch.empty((B, fixed_length), dtype=torch.int32, device=dev)
-    count = torch.empty(B, dtype=torch.int32, device=dev)
-    seq_ps = torch.empty((B, fixed_length, 4), dtype=torch.float32, device=dev)
-    ws = workspace(L.ucfvit_octree_workspace(B, N), dev)
-    _l.check(L.ucfvit_octree_build(domain.data_ptr(), nodes.data_ptr(), values.data_ptr(), count.data_ptr(), seq_ps.data_ptr(), B, N,
-                                   fixed_length, int(norm_factor), ws.data_ptr(), _stream()), "ucfvit_octree_build")
-    return nodes, values, count, seq_ps
+    return _tree_build("octree_build", 3, domain, fixed_length, int(norm_factor))
 
 
 def octree_serialize(img, nodes, count, patch, flat=True):
     """img fp32 [B, N, N, N, C] -> x [B, C, L, patch**3] (Patchify_3D's plain reshape, transform.py:123-126) or, flat=False, the patch list
     [B, L, p, p, p, C]"""
-    L = _l.load()
-    _chk(img, "octree_serialize.img"), _chk(nodes, "octree_serialize.nodes"), _chk(count, "octree_serialize.count")
-    if img.dtype != torch.float32 or img.dim() != 5 or nodes.dtype != torch.int32 or count.dtype != torch.int32:
-        raise TypeError("octree_serialize: img fp32 [B, N, N, N, C], nodes int32 [B, L, 6], count int32 [B]")
-    B, N, _, _, C = img.shape
-    S = nodes.shape[1]
-    seq = torch.empty((B, S, patch, patch, patch, C), dtype=torch.float32, device=img.device)
-    _l.check(L.ucfvit_octree_serialize(img.data_ptr(), nodes.data_ptr(), count.data_ptr(), seq.data_ptr(), B, N, C, S, patch, _stream()),
-             "ucfvit_octree_serialize")
-    return seq.view(B, C, S, patch ** 3) if flat else seq
+    seq = _serialize("octree_serialize", 3, img, nodes, count, patch)
+    return seq.view(seq.shape[0], seq.shape[-1], seq.shape[1], patch ** 3) if flat else seq
 
 
 _LABEL_DT = {torch.uint8: _l.LABEL_U8, torch.int64: _l.LABEL_I64}

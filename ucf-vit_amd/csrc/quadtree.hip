@@ -7,15 +7,13 @@
 //                        centres aligned, replicated border), written in the reference's [S][p][p][C] order.
 // One workgroup per image (build) / per node (serialize); the greedy loop is sequential by definition, the batch supplies the
 // parallelism (166 images = 166 workgroups).  Edge detection (cv2.Canny) is not part of this file: the edge map is an input.
+// The tree logic (integers) is patcher_tree.h's, once for both dimensions.  The serializers' sampling loops stay written out per kernel: this
+// unit is built with -ffp-contract=fast, and moving such a loop into a helper changed which product is fused into which sum.
 #include "common.h"
+#include "patcher_tree.h"            // Node, tree_refine, tree_write
 #include "resample_rules.h"          // cubic_coeffs
 
 namespace {
-
-struct QNode {
-    short x1, x2, y1, y2;
-    int v;
-};
 
 __device__ __forceinline__ unsigned sat_sum(const unsigned* __restrict__ sat, int W1, int x1, int x2, int y1, int y2) {
     return sat[y2 * W1 + x2] - sat[y1 * W1 + x2] - sat[y2 * W1 + x1] + sat[y1 * W1 + x1];
@@ -25,12 +23,7 @@ __global__ __launch_bounds__(256) void quadtree_build_kernel(const unsigned char
                                                              int* __restrict__ values_out, int* __restrict__ count_out,
                                                              float* __restrict__ seq_ps, unsigned* __restrict__ sat_all, int H, int W, int L) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    QNode* bufA = reinterpret_cast<QNode*>(smem_raw);
-    QNode* bufB = bufA + (L + 4);
-    __shared__ int red_v[4], red_i[4];
-    __shared__ int s_idx, s_stop;
-    __shared__ QNode s_kids[4];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.x, tid = threadIdx.x;
     const int W1 = W + 1;
     const unsigned char* e = edges + (int64_t)b * H * W;
     unsigned* sat = sat_all + (int64_t)b * (H + 1) * W1;
@@ -56,95 +49,10 @@ __global__ __launch_bounds__(256) void quadtree_build_kernel(const unsigned char
     }
     __syncthreads();
 
-    // ---- greedy refinement (quadtree.py:115-140)
-    QNode* cur = bufA;
-    QNode* nxt = bufB;
-    int n = 1;
-    if (tid == 0) {
-        cur[0] = QNode{0, (short)W, 0, (short)H, (int)(sat_sum(sat, W1, 0, W, 0, H) / 255u)};
-        s_stop = 0;
-    }
-    __syncthreads();
-    while (n < L) {
-        // first index of the maximum value: max over (v, -i)
-        int bv = -1, bi = 0x7fffffff;
-        for (int i = tid; i < n; i += blockDim.x) {
-            const int v = cur[i].v;
-            if (v > bv) {          // i ascends per thread: the first maximum of this thread's subsequence is kept
-                bv = v;
-                bi = i;
-            }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const int ov = __shfl_xor(bv, o, 64), oi = __shfl_xor(bi, o, 64);
-            if (ov > bv || (ov == bv && oi < bi)) {
-                bv = ov;
-                bi = oi;
-            }
-        }
-        if (lane == 0) {
-            red_v[wave] = bv;
-            red_i[wave] = bi;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            int v = red_v[0], i = red_i[0];
-            for (int w = 1; w < 4; ++w)
-                if (red_v[w] > v || (red_v[w] == v && red_i[w] < i)) {
-                    v = red_v[w];
-                    i = red_i[w];
-                }
-            s_idx = i;
-            if (cur[i].x2 - cur[i].x1 == 2) s_stop = 1;            // :121-122
-        }
-        __syncthreads();
-        if (s_stop) break;
-        const int idx = s_idx;
-        if (tid < 4) {
-            const QNode q = cur[idx];
-            const int mx = (q.x1 + q.x2) >> 1, my = (q.y1 + q.y2) >> 1;      // int((a + b) / 2) for non-negative ints
-            QNode k;
-            if (tid == 0) k = QNode{q.x1, (short)mx, (short)my, q.y2, 0};            // lt (:125)
-            else if (tid == 1) k = QNode{(short)mx, q.x2, (short)my, q.y2, 0};       // rt
-            else if (tid == 2) k = QNode{q.x1, (short)mx, q.y1, (short)my, 0};       // lb
-            else k = QNode{(short)mx, q.x2, q.y1, (short)my, 0};                     // rb
-            k.v = (int)(sat_sum(sat, W1, k.x1, k.x2, k.y1, k.y2) / 255u);
-            s_kids[tid] = k;
-        }
-        __syncthreads();
-        // nodes = nodes[:idx] + kids + nodes[idx+1:]   (:134), written into the other buffer
-        for (int j = tid; j < n + 3; j += blockDim.x) nxt[j] = j < idx ? cur[j] : (j < idx + 4 ? s_kids[j - idx] : cur[j - 3]);
-        __syncthreads();
-        QNode* t = cur;
-        cur = nxt;
-        nxt = t;
-        n += 3;
-    }
-    // ---- outputs: the first min(n, L) nodes (n == L whenever fixed_length = 3k + 1), padding as serialize() pads (:160-168)
-    const int nv = n < L ? n : L;
-    if (tid == 0) count_out[b] = nv;
-    for (int i = tid; i < L; i += blockDim.x) {
-        int* no = nodes_out + ((int64_t)b * L + i) * 4;
-        float* sp = seq_ps + ((int64_t)b * L + i) * 3;
-        if (i < nv) {
-            const QNode q = cur[i];
-            no[0] = q.x1;
-            no[1] = q.x2;
-            no[2] = q.y1;
-            no[3] = q.y2;
-            values_out[(int64_t)b * L + i] = q.v;
-            sp[0] = (float)(q.x2 - q.x1);                       // seq_size: the width (:151)
-            sp[1] = (float)(q.x2 + q.x1) * 0.5f;                // seq_pos: centre (:152, Rect.get_center)
-            sp[2] = (float)(q.y2 + q.y1) * 0.5f;
-        } else {
-            no[0] = no[1] = no[2] = no[3] = 0;
-            values_out[(int64_t)b * L + i] = 0;
-            sp[0] = 0.f;
-            sp[1] = -1.f;
-            sp[2] = -1.f;
-        }
-    }
+    Node<2>* cur = reinterpret_cast<Node<2>*>(smem_raw);
+    const int n = tree_refine<2>(cur, cur + (L + 4), L, Node<2>{{0, (short)W, 0, (short)H}, 0},
+                                 [&](const Node<2>& k) { return (int)(sat_sum(sat, W1, k.c[0], k.c[1], k.c[2], k.c[3]) / 255u); });
+    tree_write<2>(cur, n, L, b, nodes_out, values_out, count_out, seq_ps);
 }
 
 __global__ __launch_bounds__(256) void quadtree_serialize_kernel(const float* __restrict__ img, const int* __restrict__ nodes,
@@ -195,11 +103,6 @@ __global__ __launch_bounds__(256) void quadtree_serialize_kernel(const float* __
 // Octree (3-D volumes): dataloaders/octree.py:66-151 FixedOctTree.  domain[z][y][x] uint8, cubic; value = sum / norm_factor;
 // children n1..n8 = x fastest, then y, then z (:83-103); stop when the first maximum node is 2 wide in x; 7 nodes added per step.
 // ---------------------------------------------------------------------------------------------------------------------
-struct ONode {
-    short x1, x2, y1, y2, z1, z2;
-    int v;
-};
-
 // summed-volume table sat[z][y][x] = sum of dom[0..z)[0..y)[0..x), (N+1)^3 entries per volume, zero-initialised by the caller
 __global__ void sat3_x_kernel(const unsigned char* __restrict__ dom, unsigned* __restrict__ sat, int B, int N) {
     const int64_t line = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;     // (b, z, y)
@@ -251,97 +154,13 @@ __global__ __launch_bounds__(256) void octree_build_kernel(int* __restrict__ nod
                                                            float* __restrict__ seq_ps, const unsigned* __restrict__ sat_all, int N, int L,
                                                            unsigned norm) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    ONode* cur = reinterpret_cast<ONode*>(smem_raw);
-    ONode* nxt = cur + (L + 8);
-    __shared__ int red_v[4], red_i[4];
-    __shared__ int s_idx, s_stop;
-    __shared__ ONode s_kids[8];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.x;
     const int N1 = N + 1;
     const unsigned* sat = sat_all + (int64_t)b * N1 * N1 * N1;
-    int n = 1;
-    if (tid == 0) {
-        cur[0] = ONode{0, (short)N, 0, (short)N, 0, (short)N, (int)(sat3_sum(sat, N1, 0, N, 0, N, 0, N) / norm)};
-        s_stop = 0;
-    }
-    __syncthreads();
-    while (n < L) {
-        int bv = -1, bi = 0x7fffffff;
-        for (int i = tid; i < n; i += blockDim.x) {
-            const int v = cur[i].v;
-            if (v > bv) {
-                bv = v;
-                bi = i;
-            }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const int ov = __shfl_xor(bv, o, 64), oi = __shfl_xor(bi, o, 64);
-            if (ov > bv || (ov == bv && oi < bi)) {
-                bv = ov;
-                bi = oi;
-            }
-        }
-        if (lane == 0) {
-            red_v[wave] = bv;
-            red_i[wave] = bi;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            int v = red_v[0], i = red_i[0];
-            for (int w = 1; w < 4; ++w)
-                if (red_v[w] > v || (red_v[w] == v && red_i[w] < i)) {
-                    v = red_v[w];
-                    i = red_i[w];
-                }
-            s_idx = i;
-            if (cur[i].x2 - cur[i].x1 == 2) s_stop = 1;            // octree.py:79-80
-        }
-        __syncthreads();
-        if (s_stop) break;
-        const int idx = s_idx;
-        if (tid < 8) {
-            const ONode q = cur[idx];
-            const int mx = (q.x1 + q.x2) >> 1, my = (q.y1 + q.y2) >> 1, mz = (q.z1 + q.z2) >> 1;
-            ONode k;
-            k.x1 = (tid & 1) ? (short)mx : q.x1;
-            k.x2 = (tid & 1) ? q.x2 : (short)mx;
-            k.y1 = (tid & 2) ? (short)my : q.y1;
-            k.y2 = (tid & 2) ? q.y2 : (short)my;
-            k.z1 = (tid & 4) ? (short)mz : q.z1;
-            k.z2 = (tid & 4) ? q.z2 : (short)mz;
-            k.v = (int)(sat3_sum(sat, N1, k.x1, k.x2, k.y1, k.y2, k.z1, k.z2) / norm);
-            s_kids[tid] = k;
-        }
-        __syncthreads();
-        for (int j = tid; j < n + 7; j += blockDim.x) nxt[j] = j < idx ? cur[j] : (j < idx + 8 ? s_kids[j - idx] : cur[j - 7]);
-        __syncthreads();
-        ONode* t = cur;
-        cur = nxt;
-        nxt = t;
-        n += 7;
-    }
-    const int nv = n < L ? n : L;
-    if (tid == 0) count_out[b] = nv;
-    for (int i = tid; i < L; i += blockDim.x) {
-        int* no = nodes_out + ((int64_t)b * L + i) * 6;
-        float* sp = seq_ps + ((int64_t)b * L + i) * 4;
-        if (i < nv) {
-            const ONode q = cur[i];
-            no[0] = q.x1; no[1] = q.x2; no[2] = q.y1; no[3] = q.y2; no[4] = q.z1; no[5] = q.z2;
-            values_out[(int64_t)b * L + i] = q.v;
-            sp[0] = (float)(q.x2 - q.x1);
-            sp[1] = (float)(q.x2 + q.x1) * 0.5f;
-            sp[2] = (float)(q.y2 + q.y1) * 0.5f;
-            sp[3] = (float)(q.z2 + q.z1) * 0.5f;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 6; ++k) no[k] = 0;
-            values_out[(int64_t)b * L + i] = 0;
-            sp[0] = 0.f;
-            sp[1] = sp[2] = sp[3] = -1.f;
-        }
-    }
+    Node<3>* cur = reinterpret_cast<Node<3>*>(smem_raw);
+    const int n = tree_refine<3>(cur, cur + (L + 8), L, Node<3>{{0, (short)N, 0, (short)N, 0, (short)N}, 0},
+                                 [&](const Node<3>& k) { return (int)(sat3_sum(sat, N1, k.c[0], k.c[1], k.c[2], k.c[3], k.c[4], k.c[5]) / norm); });
+    tree_write<3>(cur, n, L, b, nodes_out, values_out, count_out, seq_ps);
 }
 
 // leaf img[z1:z2, y1:y2, x1:x2, :] -> p^3 by linear interpolation with aligned corners (octree.py:120-141), out [S][p][p][p][C]
@@ -384,6 +203,28 @@ __global__ __launch_bounds__(256) void octree_serialize_kernel(const float* __re
     }
 }
 
+// One launch of a builder, one workgroup per image: the length rule of a 2^ND-ary tree and the two LDS node lists of L + 2^ND nodes (150 KiB at
+// most; above 64 KiB the kernel has to opt in); `before` queues what the builder reads, once every check has passed.
+template <int ND, typename Before, typename... P, typename... A>
+int launch_build(const char* who, void (*kern)(P...), int64_t B, int64_t L, hipStream_t s, Before before, A... args) {
+    constexpr int K = 1 << ND;
+    UCF_CHECK_ARG(L >= 1 && L % (K - 1) == 1, "%s: fixed_length=%lld must be %dn+1 (every refinement adds %s nodes)", who, (long long)L, K - 1,
+                  ND == 2 ? "three" : "seven");
+    const size_t smem = 2 * (size_t)(L + K) * sizeof(Node<ND>);
+    UCF_CHECK_ARG(smem <= 150 * 1024, "%s: fixed_length=%lld does not fit the LDS node lists", who, (long long)L);
+    if (smem > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        if (e != hipSuccess) {
+            ucfvit_set_error("%s: cannot raise dynamic LDS to %zu bytes: %s", who, smem, hipGetErrorString(e));
+            return UCFVIT_ERR_HIP;
+        }
+    }
+    if (int rc = before()) return rc;
+    hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(256), smem, s, args...);
+    UCF_LAUNCH_CHECK(who);
+    return UCFVIT_OK;
+}
+
 }  // namespace
 
 extern "C" int64_t ucfvit_octree_workspace(int64_t B, int64_t N) {
@@ -396,38 +237,29 @@ extern "C" int ucfvit_octree_build(const uint8_t* domain, int32_t* nodes, int32_
     if (B == 0) return UCFVIT_OK;
     UCF_CHECK_ARG(domain && nodes && values && count && seq_ps && workspace, "ucfvit_octree_build: null pointer");
     UCF_CHECK_ARG(N > 0 && N <= 256, "ucfvit_octree_build: cubic volumes of side 1..256 (got %lld)", (long long)N);
-    UCF_CHECK_ARG(L >= 1 && L % 7 == 1, "ucfvit_octree_build: fixed_length=%lld must be 7n+1 (every refinement adds seven nodes)", (long long)L);
     UCF_CHECK_ARG(norm_factor >= 1 && norm_factor <= 255, "ucfvit_octree_build: norm_factor=%d out of range", norm_factor);
     // node values are int32 (kernel and `values` output): a dense volume's root value N^3 * 255 / norm_factor must stay below 2^31, or the
     // maximum search (which starts at -1) finds no node and indexes the node list out of bounds
     UCF_CHECK_ARG(N * N * N * 255 / norm_factor < (1ll << 31),
                   "ucfvit_octree_build: N=%lld with norm_factor=%d: node values up to N^3 * 255 / norm_factor do not fit int32", (long long)N,
                   norm_factor);
-    const size_t smem = 2 * (size_t)(L + 8) * sizeof(ONode);
-    UCF_CHECK_ARG(smem <= 150 * 1024, "ucfvit_octree_build: fixed_length=%lld does not fit the LDS node lists", (long long)L);
     hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(workspace, 0, (size_t)ucfvit_octree_workspace(B, N), s) != hipSuccess) {
-        ucfvit_set_error("ucfvit_octree_build: hipMemsetAsync failed");
-        return UCFVIT_ERR_HIP;
-    }
-    const int64_t lines = B * N * N;
-    const unsigned g = (unsigned)((lines + 255) / 256);
-    hipLaunchKernelGGL(sat3_x_kernel, dim3(g), dim3(256), 0, s, domain, (unsigned*)workspace, (int)B, (int)N);
-    hipLaunchKernelGGL(sat3_y_kernel, dim3(g), dim3(256), 0, s, (unsigned*)workspace, (int)B, (int)N);
-    hipLaunchKernelGGL(sat3_z_kernel, dim3(g), dim3(256), 0, s, (unsigned*)workspace, (int)B, (int)N);
-    UCF_LAUNCH_CHECK("ucfvit_octree_build(sat)");
-    auto kern = octree_build_kernel;
-    if (smem > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) {
-            ucfvit_set_error("ucfvit_octree_build: cannot raise dynamic LDS to %zu bytes: %s", smem, hipGetErrorString(e));
+    // the summed-volume table: three passes over the zeroed workspace
+    auto table = [&]() -> int {
+        if (hipMemsetAsync(workspace, 0, (size_t)ucfvit_octree_workspace(B, N), s) != hipSuccess) {
+            ucfvit_set_error("ucfvit_octree_build: hipMemsetAsync failed");
             return UCFVIT_ERR_HIP;
         }
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(256), smem, s, nodes, values, count, seq_ps, (const unsigned*)workspace, (int)N, (int)L,
-                       (unsigned)norm_factor);
-    UCF_LAUNCH_CHECK("ucfvit_octree_build");
-    return UCFVIT_OK;
+        const int64_t lines = B * N * N;
+        const unsigned g = (unsigned)((lines + 255) / 256);
+        hipLaunchKernelGGL(sat3_x_kernel, dim3(g), dim3(256), 0, s, domain, (unsigned*)workspace, (int)B, (int)N);
+        hipLaunchKernelGGL(sat3_y_kernel, dim3(g), dim3(256), 0, s, (unsigned*)workspace, (int)B, (int)N);
+        hipLaunchKernelGGL(sat3_z_kernel, dim3(g), dim3(256), 0, s, (unsigned*)workspace, (int)B, (int)N);
+        UCF_LAUNCH_CHECK("ucfvit_octree_build(sat)");
+        return UCFVIT_OK;
+    };
+    return launch_build<3>("ucfvit_octree_build", octree_build_kernel, B, L, s, table, nodes, values, count, seq_ps, (const unsigned*)workspace, (int)N,
+                           (int)L, (unsigned)norm_factor);
 }
 
 extern "C" int ucfvit_octree_serialize(const float* img, const int32_t* nodes, const int32_t* count, float* seq, int64_t B, int64_t N, int64_t C,
@@ -452,21 +284,8 @@ extern "C" int ucfvit_quadtree_build(const uint8_t* edges, int32_t* nodes, int32
     UCF_CHECK_ARG(edges && nodes && values && count && seq_ps && workspace, "ucfvit_quadtree_build: null pointer");
     UCF_CHECK_ARG(H > 0 && W > 0 && H < 32768 && W < 32768 && H * W * 255 < (1ll << 32), "ucfvit_quadtree_build: image %lld x %lld out of range",
                   (long long)H, (long long)W);
-    UCF_CHECK_ARG(L >= 1 && L % 3 == 1, "ucfvit_quadtree_build: fixed_length=%lld must be 3n+1 (every refinement adds three nodes)", (long long)L);
-    const size_t smem = 2 * (size_t)(L + 4) * sizeof(QNode);
-    UCF_CHECK_ARG(smem <= 150 * 1024, "ucfvit_quadtree_build: fixed_length=%lld does not fit the LDS node lists", (long long)L);
-    auto kern = quadtree_build_kernel;
-    if (smem > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) {
-            ucfvit_set_error("ucfvit_quadtree_build: cannot raise dynamic LDS to %zu bytes: %s", smem, hipGetErrorString(e));
-            return UCFVIT_ERR_HIP;
-        }
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(256), smem, (hipStream_t)stream, edges, nodes, values, count, seq_ps, (unsigned*)workspace,
-                       (int)H, (int)W, (int)L);
-    UCF_LAUNCH_CHECK("ucfvit_quadtree_build");
-    return UCFVIT_OK;
+    return launch_build<2>("ucfvit_quadtree_build", quadtree_build_kernel, B, L, (hipStream_t)stream, [] { return (int)UCFVIT_OK; }, edges, nodes, values,
+                           count, seq_ps, (unsigned*)workspace, (int)H, (int)W, (int)L);
 }
 
 extern "C" int ucfvit_quadtree_serialize(const float* img, const int32_t* nodes, const int32_t* count, float* seq, int64_t B, int64_t H, int64_t W,
