@@ -16,6 +16,7 @@
 //   16-byte aligned base pointers, leading dimensions and the contiguous extent of each operand multiples of 16 bytes.
 #include <stdlib.h>
 
+#include "gemm_epi.h"
 #include "gemm_route.h"
 #include "gemm_tile.h"
 
@@ -218,34 +219,7 @@ __global__ __launch_bounds__(NTHREADS) void gemm_mfma_kernel(const T* __restrict
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] += b.get(r);
             }
-            if (ep.act == UCFVIT_ACT_GELU) {
-                if (auxo) {
-                    Vec4<T> o;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) o.set(r, v[r]);
-                    *reinterpret_cast<Vec4<T>*>(auxo + (int64_t)m * ep.ldaux + n) = o;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = o.get(r);  // activation sees the stored (rounded) pre-activation
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = gelu_f(v[r]);
-            } else if (ep.act == UCFVIT_ACT_GELU_GRAD) {
-                Vec4<T> h = *reinterpret_cast<const Vec4<T>*>(auxi + (int64_t)m * ep.ldaux + n);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] *= gelu_grad_f(h.get(r));
-            } else if (ep.act == UCFVIT_ACT_GELU_SAVE_DERIV) {
-                Vec4<T> o;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    o.set(r, gelu_grad_f(v[r]));
-                    v[r] = gelu_f(v[r]);
-                }
-                *reinterpret_cast<Vec4<T>*>(auxo + (int64_t)m * ep.ldaux + n) = o;
-            } else if (ep.act == UCFVIT_ACT_MUL_AUX) {
-                Vec4<T> h = *reinterpret_cast<const Vec4<T>*>(auxi + (int64_t)m * ep.ldaux + n);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] *= h.get(r);
-            }
+            EPI_V1_ACT(4, Vec4<T>, ep.act, v, auxi, auxo, ep.ldaux, m, n);
             if (res) {
                 Vec4<T> rr = *reinterpret_cast<const Vec4<T>*>(res + (int64_t)m * ep.ldr + n);
 #pragma unroll
@@ -280,21 +254,7 @@ __global__ void gemm_scalar_kernel(const T* __restrict__ A, const T* __restrict_
     }
     float v = ep.alpha * acc;
     if (ep.bias) v += to_f32<T>(((const T*)ep.bias)[n]);
-    if (ep.act == UCFVIT_ACT_GELU) {
-        if (ep.aux_out) {
-            T h = from_f32<T>(v);
-            ((T*)ep.aux_out)[m * ep.ldaux + n] = h;
-            v = to_f32<T>(h);
-        }
-        v = gelu_f(v);
-    } else if (ep.act == UCFVIT_ACT_GELU_GRAD) {
-        v *= gelu_grad_f(to_f32<T>(((const T*)ep.aux_in)[m * ep.ldaux + n]));
-    } else if (ep.act == UCFVIT_ACT_GELU_SAVE_DERIV) {
-        ((T*)ep.aux_out)[m * ep.ldaux + n] = from_f32<T>(gelu_grad_f(v));
-        v = gelu_f(v);
-    } else if (ep.act == UCFVIT_ACT_MUL_AUX) {
-        v *= to_f32<T>(((const T*)ep.aux_in)[m * ep.ldaux + n]);
-    }
+    EPI_V1_ACT(1, Vec1<T>, ep.act, (&v), (const T*)ep.aux_in, (T*)ep.aux_out, ep.ldaux, m, n);
     if (ep.residual) v += to_f32<T>(((const T*)ep.residual)[m * ep.ldr + n]);
     OutT* cp = C + m * ep.ldc + n;
     if (ep.accumulate) v += to_f32<OutT>(*cp);
@@ -316,10 +276,9 @@ int launch_v1(const ucfvit_gemm_desc* d, bool mfma, hipStream_t s) {
     const EpiArgs ep = {d->bias, d->residual, d->aux_in, d->aux_out, d->ldc, d->ldr, d->ldaux, d->act, d->accumulate, d->alpha};
     const int la = d->a_layout, lb = d->b_layout;
     if (mfma) {
-        if (la == UCFVIT_LAYOUT_KC && lb == UCFVIT_LAYOUT_KC) return launch_mfma<T, OutT, 0, 0>(d, ep, s);
-        if (la == UCFVIT_LAYOUT_KC && lb == UCFVIT_LAYOUT_KS) return launch_mfma<T, OutT, 0, 1>(d, ep, s);
-        if (la == UCFVIT_LAYOUT_KS && lb == UCFVIT_LAYOUT_KS) return launch_mfma<T, OutT, 1, 1>(d, ep, s);
-        return launch_mfma<T, OutT, 1, 0>(d, ep, s);
+        return gemm_with_layouts(la, lb, [&](auto la_c, auto lb_c) {
+            return launch_mfma<T, OutT, decltype(la_c)::value, decltype(lb_c)::value>(d, ep, s);
+        });
     }
     const int64_t total = d->M * d->N;
     const int64_t blocks = (total + 255) / 256;

@@ -14,19 +14,11 @@
 //               order (deterministic) and applies accumulate.  Used when the output has too few tiles to fill 256 CUs.
 #include <stdlib.h>
 
+#include "gemm_epi.h"
 #include "gemm_route.h"
 #include "gemm_tile.h"
 
 namespace {
-
-// C / aux tiles are written once and not read again by this kernel: stored with the non-temporal hint, the dirty lines leave L2 as the
-// K loop's fills need the ways instead of in one write-back burst one L2 turnover later (4 MB of C per XCD and tile round).
-#ifndef UCFVIT_GEMM_STORE_TEMPORAL
-__device__ __forceinline__ void store_out16(bf16* p, const Vec16<bf16>& o) { __builtin_nontemporal_store(o.v, reinterpret_cast<bf16x8*>(p)); }
-#else
-__device__ __forceinline__ void store_out16(bf16* p, const Vec16<bf16>& o) { *reinterpret_cast<Vec16<bf16>*>(p) = o; }
-#endif
-
 
 constexpr int BK2 = 64;
 
@@ -122,19 +114,6 @@ __device__ __forceinline__ bf16x8 ks_frag_value(const KsFrag& f) {
     return __builtin_bit_cast(bf16x8, r);
 }
 __device__ __forceinline__ unsigned lds_addr(const char* p) { return (unsigned)(uintptr_t)LDS_PTR(const char, p); }
-
-struct Epi2 {
-    const bf16* bias;
-    const bf16* residual;
-    const bf16* aux_in;
-    bf16* aux_out;
-    int64_t ldc, ldr, ldaux;
-    int act, accumulate;
-    float alpha;
-    float* slab;       // split-K: fp32 partial matrices [splits][M][N] (ld = N); NULL when gridDim.y == 1
-    float* cs_partial; // column sums of the output per 128-row block: [2 * tiles_m][N] (CS instantiations only), or NULL
-    unsigned* sched;   // dynamic tile schedule of the persistent 256x256 kernel (desc->sched_state), or NULL: static round-robin
-};
 
 // ---- dynamic tile schedule (gemm3_kernel) ------------------------------------------------------------------------------------------
 // A persistent grid with a STATIC tile list assumes every workgroup is resident from the start.  When another kernel holds some CUs —
@@ -284,9 +263,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm2_kernel(const bf16* __restri
             }
         }
 
-        // ---- epilogue through LDS so every global access is a full 128-B line ---------------------------------------
-        //   phase A: v = alpha*acc + bias (fp32) of a 16-row x TN-col strip -> wave-private LDS rows
-        //   phase B: each lane owns 8 consecutive columns of a row: activation / aux / residual / accumulate, 16-B loads+stores
+        // ---- epilogue through LDS so every global access is a full 128-B line (gemm_epi.h) ---------------------------
         // The staging area is the pipeline buffer of the K-tile just consumed; the other buffer is receiving the next tile's
         // first K-tile, so only LDS reads (not the DMA) are waited for here: raw barrier, no vmcnt.
         __builtin_amdgcn_sched_barrier(0);
@@ -296,99 +273,17 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm2_kernel(const bf16* __restri
         float* stage = reinterpret_cast<float*>(smem + ((it - 1) & 1) * BUF) + wave * (16 * PADW);
 #pragma unroll
         for (int i = 0; i < FM; ++i) {
-#pragma unroll
-            for (int j = 0; j < FN; ++j) {
-                f32x4 v = acc[i][j];
-                if (!slab) {
-                    const int n = n0 + wn + 16 * j + 4 * g;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] *= ep.alpha;
-                    if (ep.bias && n < N) {
-                        const Vec4<bf16> b = *reinterpret_cast<const Vec4<bf16>*>(ep.bias + n);
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) v[r] += b.get(r);
-                    }
-                }
-                *reinterpret_cast<f32x4*>(stage + li * PADW + 16 * j + 4 * g) = v;
-            }
+            EPI_STAGE_STRIP(acc[i], stage, ep, slab, n0 + wn);
             // wave-private region: LDS executes one wave's DS instructions in order (writes above, reads below, next pass's writes after)
 #pragma unroll
             for (int rr = 0; rr < 16; rr += RPI) {
                 const int row = rr + prow;
                 const int m = m0 + wm + 16 * i + row;
                 const int n = n0 + wn + pcol;
-                float v[8];
                 const f32x4 lo = *reinterpret_cast<const f32x4*>(stage + row * PADW + pcol);
                 const f32x4 hi = *reinterpret_cast<const f32x4*>(stage + row * PADW + pcol + 4);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    v[r] = lo[r];
-                    v[4 + r] = hi[r];
-                }
                 if (m >= M || n >= N) continue;     // N % 8 == 0 on this path: the 8 columns are all in or all out
-                if (slab) {
-                    *reinterpret_cast<f32x4*>(slab + (int64_t)m * N + n) = lo;
-                    *reinterpret_cast<f32x4*>(slab + (int64_t)m * N + n + 4) = hi;
-                    continue;
-                }
-                if (ep.act == UCFVIT_ACT_GELU) {
-                    if (ep.aux_out) {
-                        Vec16<bf16> o;
-#pragma unroll
-                        for (int r = 0; r < 8; ++r) o.set(r, v[r]);
-                        store_out16(ep.aux_out + (int64_t)m * ep.ldaux + n, o);
-#pragma unroll
-                        for (int r = 0; r < 8; ++r) v[r] = o.get(r);   // activation sees the stored (rounded) pre-activation
-                    }
-                    gelu_fast8(v);
-                } else if (ep.act == UCFVIT_ACT_GELU_GRAD) {
-                    const Vec16<bf16> h = *reinterpret_cast<const Vec16<bf16>*>(ep.aux_in + (int64_t)m * ep.ldaux + n);
-                    float hf[8];
-#pragma unroll
-                    for (int r = 0; r < 8; ++r) hf[r] = h.get(r);
-                    gelu_grad_fast8(v, hf);
-                } else if (ep.act == UCFVIT_ACT_GELU_SAVE_DERIV) {
-                    float df[8];
-                    gelu_and_grad_fast8(v, df);
-                    Vec16<bf16> o;
-#pragma unroll
-                    for (int r = 0; r < 8; ++r) o.set(r, df[r]);
-                    store_out16(ep.aux_out + (int64_t)m * ep.ldaux + n, o);
-                } else if (ep.act == UCFVIT_ACT_MUL_AUX) {
-                    const Vec16<bf16> h = *reinterpret_cast<const Vec16<bf16>*>(ep.aux_in + (int64_t)m * ep.ldaux + n);
-#pragma unroll
-                    for (int r = 0; r < 8; ++r) v[r] *= h.get(r);
-                }
-                if (ep.residual) {
-                    const Vec16<bf16> rv = *reinterpret_cast<const Vec16<bf16>*>(ep.residual + (int64_t)m * ep.ldr + n);
-#pragma unroll
-                    for (int r = 0; r < 8; ++r) v[r] += rv.get(r);
-                }
-                OutT* cp = C + (int64_t)m * ep.ldc + n;
-                if constexpr (sizeof(OutT) == 2) {
-                    if (ep.accumulate) {
-                        const Vec16<bf16> old = *reinterpret_cast<const Vec16<bf16>*>(cp);
-#pragma unroll
-                        for (int r = 0; r < 8; ++r) v[r] += old.get(r);
-                    }
-                    Vec16<bf16> o;
-#pragma unroll
-                    for (int r = 0; r < 8; ++r) o.set(r, v[r]);
-                    store_out16(cp, o);
-                } else {
-                    f32x4 o0, o1;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        o0[r] = v[r];
-                        o1[r] = v[4 + r];
-                    }
-                    if (ep.accumulate) {
-                        o0 += *reinterpret_cast<const f32x4*>(cp);
-                        o1 += *reinterpret_cast<const f32x4*>(cp + 4);
-                    }
-                    *reinterpret_cast<f32x4*>(cp) = o0;
-                    *reinterpret_cast<f32x4*>(cp + 4) = o1;
-                }
+                epi_finish8<OutT>(lo, hi, ep, C, ep.ldc, ep.accumulate, slab, m, n, N);
             }
         }
         if (!has_next) break;
@@ -861,127 +756,28 @@ __global__ __launch_bounds__(512) void gemm3_kernel(GroupsT<NP> gt, int K, Epi2 
                     }
                 }
             }
-            if constexpr (CS) {
-                // lanes l, l+8, ..., l+56 hold the same 8 columns for different rows: xor-shuffle over lane bits 3..5, then lanes 0-7
-                // write the 64 column sums of this wave's 128 x 64 sub-tile (every [row block][column] entry is written exactly once)
-#pragma unroll
-                for (int r = 0; r < 8; ++r) {
-                    float t = csum[r];
-                    t += __shfl_xor(t, 8, 64);
-                    t += __shfl_xor(t, 16, 64);
-                    t += __shfl_xor(t, 32, 64);
-                    csum[r] = t;
-                }
-                const int n = n0 + wn + pcol;
-                if (prow == 0 && n < N) {
-                    float* cp = ep.cs_partial + (int64_t)((m0 >> 7) + grp) * N + n;
-                    *reinterpret_cast<f32x4*>(cp) = f32x4{csum[0], csum[1], csum[2], csum[3]};
-                    *reinterpret_cast<f32x4*>(cp + 4) = f32x4{csum[4], csum[5], csum[6], csum[7]};
-                }
-            }
+            if constexpr (CS) EPI_COLSUM_FOLD(csum, ep.cs_partial, (m0 >> 7) + grp, n0 + wn + pcol, N, prow);
 #undef EPI_LOAD
         } else {
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_sched_barrier(0);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int i = 0; i < FM; ++i) {
+            for (int i = 0; i < FM; ++i) {
+                EPI_STAGE_STRIP(acc[i], stage, ep, slab, n0 + wn);
 #pragma unroll
-            for (int j = 0; j < FN; ++j) {
-                f32x4 v = acc[i][j];
-                if (!slab) {
-                    const int n = n0 + wn + 16 * j + 4 * g;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] *= ep.alpha;
-                    if (ep.bias && n < N) {
-                        const Vec4<bf16> b = *reinterpret_cast<const Vec4<bf16>*>(ep.bias + n);
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) v[r] += b.get(r);
-                    }
-                }
-                *reinterpret_cast<f32x4*>(stage + li * PADW + 16 * j + 4 * g) = v;
-            }
-#pragma unroll
-            for (int rr = 0; rr < 16; rr += RPI) {
-                const int row = rr + prow;
-                const int m = m0 + wm + 16 * i + row;
-                const int n = n0 + wn + pcol;
-                float v[8];
-                const f32x4 lo = *reinterpret_cast<const f32x4*>(stage + row * PADW + pcol);
-                const f32x4 hi = *reinterpret_cast<const f32x4*>(stage + row * PADW + pcol + 4);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    v[r] = lo[r];
-                    v[4 + r] = hi[r];
-                }
-                if (m >= M || n >= N) continue;
-                if (slab) {
-                    *reinterpret_cast<f32x4*>(slab + (int64_t)m * N + n) = lo;
-                    *reinterpret_cast<f32x4*>(slab + (int64_t)m * N + n + 4) = hi;
-                    continue;
-                }
-                if (ep.act == UCFVIT_ACT_GELU) {
-                    if (ep.aux_out) {
-                        Vec16<bf16> o;
-#pragma unroll
-                        for (int r = 0; r < 8; ++r) o.set(r, v[r]);
-                        store_out16(ep.aux_out + (int64_t)m * ep.ldaux + n, o);
-#pragma unroll
-                        for (int r = 0; r < 8; ++r) v[r] = o.get(r);
-                    }
-                    gelu_fast8(v);
-                } else if (ep.act == UCFVIT_ACT_GELU_GRAD) {
-                    const Vec16<bf16> h = *reinterpret_cast<const Vec16<bf16>*>(ep.aux_in + (int64_t)m * ep.ldaux + n);
-                    float hf[8];
-#pragma unroll
-                    for (int r = 0; r < 8; ++r) hf[r] = h.get(r);
-                    gelu_grad_fast8(v, hf);
-                } else if (ep.act == UCFVIT_ACT_GELU_SAVE_DERIV) {
-                    float df[8];
-                    gelu_and_grad_fast8(v, df);
-                    Vec16<bf16> o;
-#pragma unroll
-                    for (int r = 0; r < 8; ++r) o.set(r, df[r]);
-                    store_out16(ep.aux_out + (int64_t)m * ep.ldaux + n, o);
-                } else if (ep.act == UCFVIT_ACT_MUL_AUX) {
-                    const Vec16<bf16> h = *reinterpret_cast<const Vec16<bf16>*>(ep.aux_in + (int64_t)m * ep.ldaux + n);
-#pragma unroll
-                    for (int r = 0; r < 8; ++r) v[r] *= h.get(r);
-                }
-                if (ep.residual) {
-                    const Vec16<bf16> rv = *reinterpret_cast<const Vec16<bf16>*>(ep.residual + (int64_t)m * ep.ldr + n);
-#pragma unroll
-                    for (int r = 0; r < 8; ++r) v[r] += rv.get(r);
-                }
-                OutT* cp = C + (int64_t)m * ldc + n;
-                if constexpr (sizeof(OutT) == 2) {
-                    if (accum) {
-                        const Vec16<bf16> old = *reinterpret_cast<const Vec16<bf16>*>(cp);
-#pragma unroll
-                        for (int r = 0; r < 8; ++r) v[r] += old.get(r);
-                    }
-                    Vec16<bf16> o;
-#pragma unroll
-                    for (int r = 0; r < 8; ++r) o.set(r, v[r]);
-                    store_out16(cp, o);
-                } else {
-                    f32x4 o0, o1;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        o0[r] = v[r];
-                        o1[r] = v[4 + r];
-                    }
-                    if (accum) {
-                        o0 += *reinterpret_cast<const f32x4*>(cp);
-                        o1 += *reinterpret_cast<const f32x4*>(cp + 4);
-                    }
-                    *reinterpret_cast<f32x4*>(cp) = o0;
-                    *reinterpret_cast<f32x4*>(cp + 4) = o1;
+                for (int rr = 0; rr < 16; rr += RPI) {
+                    const int row = rr + prow;
+                    const int m = m0 + wm + 16 * i + row;
+                    const int n = n0 + wn + pcol;
+                    const f32x4 lo = *reinterpret_cast<const f32x4*>(stage + row * PADW + pcol);
+                    const f32x4 hi = *reinterpret_cast<const f32x4*>(stage + row * PADW + pcol + 4);
+                    if (m >= M || n >= N) continue;
+                    epi_finish8<OutT>(lo, hi, ep, C, ldc, accum, slab, m, n, N);
                 }
             }
         }
-        }   // EPI_GENERIC
         if (!has_next) break;
         m0 = nm0;
         n0 = nn0;
@@ -1055,17 +851,9 @@ template <int LA, int LB, int BM, int BN, int WM, int WN, typename OutT>
 int launch2(const ucfvit_gemm_desc* d, const GemmRoute& p, const Epi2& ep, hipStream_t s) {
     const int tiles_m = (int)((d->M + BM - 1) / BM), tiles_n = (int)((d->N + BN - 1) / BN);
     constexpr size_t smem = 2 * (size_t)(BM + BN) * 128;
-    auto kern = gemm2_kernel<LA, LB, BM, BN, WM, WN, OutT>;
-    if (smem > 64 * 1024) {
-        static bool done = false;  // per instantiation
-        if (!done) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-            if (e != hipSuccess) {
-                ucfvit_set_error("ucfvit_gemm: cannot raise dynamic LDS to %zu bytes: %s", smem, hipGetErrorString(e));
-                return UCFVIT_ERR_HIP;
-            }
-            done = true;
-        }
+    constexpr auto kern = gemm2_kernel<LA, LB, BM, BN, WM, WN, OutT>;
+    if constexpr (smem > 64 * 1024) {
+        if (const int rc = gemm_raise_lds<kern>(smem)) return rc;
     }
     // persistent grid: 8 XCDs x `slots` workgroups; one workgroup per CU for the 128-KiB-LDS tile, two for the 64-KiB one
     const Sched2 sc = make_sched2(tiles_m, tiles_n, p.splits, p.k_per_split, BM == 256 ? 32 : 64);
@@ -1087,16 +875,8 @@ int launch2(const ucfvit_gemm_desc* d, const GemmRoute& p, const Epi2& ep, hipSt
 template <int LA, int LB, typename OutT, int EPI = EPI_GENERIC, bool CS = false, int NP = GROUP_MAX>
 int launch3g(const GroupsT<NP>& gt, int K, const Epi2& ep, int splits, int k_per_split, hipStream_t s) {
     constexpr size_t smem = 2 * (size_t)(256 + 256) * 128 + 16;      // + the two schedule words
-    auto kern = gemm3_kernel<LA, LB, OutT, EPI, CS, NP>;
-    static bool done = false;
-    if (!done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) {
-            ucfvit_set_error("ucfvit_gemm: cannot raise dynamic LDS to %zu bytes: %s", smem, hipGetErrorString(e));
-            return UCFVIT_ERR_HIP;
-        }
-        done = true;
-    }
+    constexpr auto kern = gemm3_kernel<LA, LB, OutT, EPI, CS, NP>;
+    if (const int rc = gemm_raise_lds<kern>(smem)) return rc;
     // persistent grid = the CUs this launch may count on.  One 512-thread workgroup fills a CU's register file, so a CU that hosts a
     // wave of another kernel (an RCCL all-reduce overlapping backward) cannot take one: a grid larger than the free CUs leaves
     // workgroups waiting for a whole tile list.  UCFVIT_GEMM_CUS (default 256) lets a multi-GPU job reserve the CUs RCCL uses.
@@ -1163,11 +943,9 @@ int launch_tile(const ucfvit_gemm_desc* d, const GemmRoute& r, const Epi2& ep, h
 
 template <typename OutT>
 int launch_layout(const ucfvit_gemm_desc* d, const GemmRoute& r, const Epi2& ep, hipStream_t s) {
-    const int la = d->a_layout, lb = d->b_layout;
-    if (la == 0 && lb == 0) return launch_tile<0, 0, OutT>(d, r, ep, s);
-    if (la == 0 && lb == 1) return launch_tile<0, 1, OutT>(d, r, ep, s);
-    if (la == 1 && lb == 1) return launch_tile<1, 1, OutT>(d, r, ep, s);
-    return launch_tile<1, 0, OutT>(d, r, ep, s);
+    return gemm_with_layouts(d->a_layout, d->b_layout, [&](auto la, auto lb) {
+        return launch_tile<decltype(la)::value, decltype(lb)::value, OutT>(d, r, ep, s);
+    });
 }
 
 }  // namespace
@@ -1217,12 +995,8 @@ extern "C" int ucfvit_gemm_grouped(const ucfvit_gemm_desc* descs, int64_t n, voi
     ep.sched = (unsigned*)d0.sched_state;
     const int K = (int)d0.K;
     const int kps = ((K + BK2 - 1) / BK2) * BK2;
-    const int la = d0.a_layout, lb = d0.b_layout;
-#define G3(LA_, LB_)                                                                                            \
-    (d0.out_dtype == UCFVIT_F32 ? launch3g<LA_, LB_, float>(gt, K, ep, 1, kps, s) : launch3g<LA_, LB_, bf16>(gt, K, ep, 1, kps, s))
-    if (la == 0 && lb == 0) return G3(0, 0);
-    if (la == 0 && lb == 1) return G3(0, 1);
-    if (la == 1 && lb == 1) return G3(1, 1);
-    return G3(1, 0);
-#undef G3
+    return gemm_with_layouts(d0.a_layout, d0.b_layout, [&](auto la, auto lb) {
+        constexpr int LA = decltype(la)::value, LB = decltype(lb)::value;
+        return d0.out_dtype == UCFVIT_F32 ? launch3g<LA, LB, float>(gt, K, ep, 1, kps, s) : launch3g<LA, LB, bf16>(gt, K, ep, 1, kps, s);
+    });
 }

@@ -25,11 +25,12 @@
 // that nobody needs at the very end of the tile list are issued anyway), so every wait is an exact count.
 #include <stdlib.h>
 
+#include "gemm_epi.h"
 #include "gemm_route.h"
 #include "gemm_tile.h"
 
 #ifndef S5_ST_MOD
-#define S5_ST_MOD " nt"      // C / aux are written once: non-temporal, so the dirty lines leave L2 gradually (see gemm2.hip:store_out16)
+#define S5_ST_MOD " nt"      // C / aux are written once: non-temporal, so the dirty lines leave L2 gradually (see gemm_epi.h:store_out16)
 #endif
 
 namespace {
@@ -350,21 +351,7 @@ __global__ __launch_bounds__(512) void gemm5_kernel(StaggerArgs a) {
             }
             if constexpr (r == 3 && (EpiLog<EPI, E>::OWN_B || J == E - 1)) s5_wait_vm<kLog<EPI, E>.wait_all(J)>();
             if constexpr (CS && u == 4 * E - 1) {
-                // lanes l, l + 8, ..., l + 56 hold the same 8 columns for different rows
-#pragma unroll
-                for (int r2 = 0; r2 < 8; ++r2) {
-                    float t = csum[r2];
-                    t += __shfl_xor(t, 8, 64);
-                    t += __shfl_xor(t, 16, 64);
-                    t += __shfl_xor(t, 32, 64);
-                    csum[r2] = t;
-                }
-                const int n = etn0 + wn + pcol;
-                if (prow == 0 && n < a.N) {
-                    float* cp = a.cs_partial + (int64_t)((etm0 >> 7) + grp) * a.N + n;
-                    *reinterpret_cast<f32x4*>(cp) = f32x4{csum[0], csum[1], csum[2], csum[3]};
-                    *reinterpret_cast<f32x4*>(cp + 4) = f32x4{csum[4], csum[5], csum[6], csum[7]};
-                }
+                EPI_COLSUM_FOLD(csum, a.cs_partial, (etm0 >> 7) + grp, etn0 + wn + pcol, a.N, prow);
             }
             s5_barrier();
         });
@@ -531,16 +518,8 @@ __global__ __launch_bounds__(512) void gemm5_kernel(StaggerArgs a) {
 template <int EPI, bool CS, int E> int s5_launch(const StaggerArgs& a, hipStream_t s) {
     constexpr size_t smem = 2 * (size_t)(256 + 256) * 128 + 4 * 16 * 68 * 4 + 4 * 3 * 1024;
     static_assert(EpiLog<EPI, E>::PD == 2, "the input ring is sized for a prefetch distance of 2 passes");
-    auto kern = gemm5_kernel<EPI, CS, E>;
-    static bool done = false;
-    if (!done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) {
-            ucfvit_set_error("ucfvit_gemm: cannot raise dynamic LDS to %zu bytes: %s", smem, hipGetErrorString(e));
-            return UCFVIT_ERR_HIP;
-        }
-        done = true;
-    }
+    constexpr auto kern = gemm5_kernel<EPI, CS, E>;
+    if (const int rc = gemm_raise_lds<kern>(smem)) return rc;
     const int gx = a.total_tiles < 256 ? a.total_tiles : 256;
     hipLaunchKernelGGL(kern, dim3(gx), dim3(512), smem, s, a);
     UCF_LAUNCH_CHECK("ucfvit_gemm(staggered ping-pong)");
