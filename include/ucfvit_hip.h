@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define UCFVIT_ABI_VERSION 22
+#define UCFVIT_ABI_VERSION 23
 
 #define UCFVIT_OK 0
 #define UCFVIT_ERR_INVALID_ARGUMENT (-1)
@@ -323,6 +323,17 @@ int ucfvit_octree_serialize(const float* img, const int32_t* nodes, const int32_
  * ucfvit_octree_deserialize: the same for [p][p][p] patches (e = (pz * p + py) * p + px) into [B][C][N][N][N] or [B][N][N][N][C]:
  *     UCFVIT_RESAMPLE_SMOOTH is aligned-corner trilinear (Cube.set_area: linspace(0, p, p) onto linspace(0, p, n)), UCFVIT_RESAMPLE_NEAREST the
  *     integer grid rule above with patch and leaf exchanged.  No trunc (the reference commented it out in 3-D).
+ * ucfvit_quadtree_deserialize_bwd / ucfvit_octree_deserialize_bwd: the adjoints (the gradient of a loss taken in the image plane).  With the
+ *     forward's weights, out[c][x] = sum_k w(x, k) seq[c][k] per leaf, they give dseq[c][k] = sum over the leaf's pixels of w(x, k) dout[c][x].
+ *     dout fp32 is read through (out_b, out_c, out_pixel), which must be one of the two dense layouts the forward writes; dseq fp32 is written
+ *     through (stride_b, stride_c, stride_s, stride_e) as the forward reads seq (stride_b > 0 unless B = 1), so the gradient lands in
+ *     [B][C][L][p^d] or in the patch list [B][L][p]..[C] without a copy.  EVERY element of every row is written: padding rows, empty leaves and
+ *     leaves whose box leaves the image get 0; pixels no leaf covers contribute nothing.  No trunc: truncation has no gradient.
+ *     Deterministic, no atomics: a leaf is cut along its slowest axis into at most 16 slices of at least 1024 pixels, a rule of the leaf's
+ *     extents alone; a leaf of one slice is summed by one thread per element, the slices of a larger leaf leave partial tiles in the workspace
+ *     ([B * L][16][C * p^d] fp32, *_bwd_workspace bytes; 0 for images of at most 1024 pixels, then NULL is accepted; -1 with
+ *     ucfvit_last_error for arguments the op refuses) and a second kernel adds them in slice order.  The same bits on every call and for
+ *     either layout of dout.
  * Parity: the 3-D rules are pinned against the reference with scipy (tests/golden/tree_labels.npz); the 2-D rules are parity UNPINNED, like
  *     ucfvit_quadtree_serialize (no cv2 to record from); the nearest rules coincide with any implementation whenever w / p or p / w is whole. */
 #define UCFVIT_LABEL_U8 0
@@ -339,6 +350,14 @@ int ucfvit_quadtree_deserialize(const float* seq, const int32_t* nodes, const in
 int ucfvit_octree_deserialize(const float* seq, const int32_t* nodes, const int32_t* count, float* out, int64_t B, int64_t N, int64_t C,
                               int64_t L, int64_t p, int64_t stride_b, int64_t stride_c, int64_t stride_s, int64_t stride_e, int64_t out_b,
                               int64_t out_c, int64_t out_pixel, int mode, void* stream);
+int64_t ucfvit_quadtree_deserialize_bwd_workspace(int64_t B, int64_t H, int64_t W, int64_t C, int64_t L, int64_t p);
+int64_t ucfvit_octree_deserialize_bwd_workspace(int64_t B, int64_t N, int64_t C, int64_t L, int64_t p);
+int ucfvit_quadtree_deserialize_bwd(const float* dout, const int32_t* nodes, const int32_t* count, float* dseq, int64_t B, int64_t H, int64_t W,
+                                    int64_t C, int64_t L, int64_t p, int64_t stride_b, int64_t stride_c, int64_t stride_s, int64_t stride_e,
+                                    int64_t out_b, int64_t out_c, int64_t out_pixel, int mode, void* workspace, void* stream);
+int ucfvit_octree_deserialize_bwd(const float* dout, const int32_t* nodes, const int32_t* count, float* dseq, int64_t B, int64_t N, int64_t C,
+                                  int64_t L, int64_t p, int64_t stride_b, int64_t stride_c, int64_t stride_s, int64_t stride_e, int64_t out_b,
+                                  int64_t out_c, int64_t out_pixel, int mode, void* workspace, void* stream);
 
 /* Variable aggregation (VariableMapping_Attention, simple/building_blocks.py:301-373, called by VIT.aggregate_variables,
  * simple/arch.py:414-432) with one aggregated variable: for every token row r and head h,

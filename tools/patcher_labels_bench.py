@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Label serializers and tree deserializers (csrc/patcher_labels.hip) on the GPU: each of the four ops at two shapes,
+"""Label serializers, tree deserializers (csrc/patcher_labels.hip) and the deserializers' adjoints (csrc/patcher_labels_bwd.hip) on the GPU: each
+op at two shapes,
     3-D  the basic_ct/sap shape: B = 2, 64^3, fixed_length 512, p = 4, 4 classes
     2-D  B = 8, 512^2, fixed_length 1024, p = 8, 4 classes
 against (a) a per-leaf torch statement of the same rule on the same GPU (the reference's loop shape: one leaf per iteration) and (b) the bytes
@@ -8,6 +9,10 @@ the op must move at the measured HBM copy rate (6.29 TB/s).  The trees come from
 Timing: device events around `reps` back-to-back calls after warm-up, three windows per op (min and max are printed: the spread); the torch
 loop is timed once over the whole batch (host clock around a device synchronise).  The deserializers' zero fill is stated separately, twice: the
 same call with count = 0 (the fill and a grid whose workgroups all return at once) and a fill of the output's bytes alone (tensor.zero_()).  One JSON line per op and shape.
+Each adjoint (ops.*_deserialize_bwd, planar dout into the model layout) is stated against the forward call of the same shape, against
+backward() of the per-leaf F.interpolate loop (the graph is built outside the clock) and against its bytes at the copy rate.  Last, the whole
+SAP training step (forward, loss, backward, optimizer) of the smoke configuration (64 x 64, patch 8, fixed_length 16, 3 classes, batch 4) with
+the loss on the token grid and with `loss_at_full_resolution`.
 
     python tools/patcher_labels_bench.py [--reps 50]
 """
@@ -125,6 +130,58 @@ def torch_deserialize(dim, seq, nodes, count, size, p):
     return out
 
 
+def torch_backward_ms(dim, seq, nodes, count, shape, p, g):
+    """backward() of the per-leaf loop alone, ms: the second of two runs, each on a graph built before the clock starts"""
+    ms = None
+    for _ in range(2):
+        leaf = seq.clone().requires_grad_(True)
+        full = torch_deserialize(dim, leaf, nodes, count, shape, p)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        full.backward(g)
+        torch.cuda.synchronize()
+        ms = (time.perf_counter() - t0) * 1e3
+    return ms, leaf.grad
+
+
+def sap_step(reps):
+    """ms per training step of the tiny SAP of the smoke configuration, loss on the token grid / at full resolution"""
+    import yaml
+    sys.path.insert(0, os.path.join(ROOT, "ucf-vit_amd", "training_scripts"))
+    import _common
+    import train_sap_simple as T
+    from UCF_VIT.simple.arch import SAP
+    from UCF_VIT.utils.fused_attn import FusedAttn
+    from UCF_VIT.utils.misc import configure_optimizer
+    conf = yaml.safe_load(open(os.path.join(ROOT, "ucf-vit_amd", "configs", "catsdogs_vit_tiny_smoke.yaml")))
+    conf["model"]["net"]["init_args"].update(tile_size=[64, 64], patch_size=8, embed_dim=96, depth=2, num_heads=3, adaptive_patching=True, fixed_length=16,
+                                             use_adaptive_pos_emb=True)
+    conf["data"].update(num_classes=3, batch_size=4)
+    margs, a, d = _common.model_args(conf)
+    nc, L, m = d["num_classes"], margs["fixed_length"], conf["model"]
+    sqrt_len = _common.sqrt_len_of(L, margs["twoD"])
+    torch.manual_seed(0)
+    model = SAP(num_classes=nc, sqrt_len=sqrt_len, sqrt_len_method=True, class_token=False, weight_init='skip', FusedAttn_option=FusedAttn.HIP,
+                **margs).to(DEV)
+    model.set_compute_dtype(torch.float32)
+    opt = configure_optimizer(model, 1e-3, float(m["beta_1"]), float(m["beta_2"]), float(m["weight_decay"]))
+    loader = _common.SyntheticSeqLoader(d["batch_size"], margs["in_chans"], margs["img_size"], margs["patch_size"], L, nc, 1, DEV, 1234, labels_from_image=True)
+    seq, seq_ps, (seq_label, label_map, nodes, count) = next(iter(loader))
+    seq = seq / 255.0
+    common = (d["dict_in_variables"][d["dataset"]], model, margs["patch_size"], margs["twoD"], nc, sqrt_len, seq_ps, margs["in_chans"])
+
+    def step(full):
+        loss, _ = T.training_step_full_resolution(seq, label_map, nodes, count, *common, L) if full else T.training_step_adaptive(seq, seq_label, *common)
+        loss.backward()
+        opt.step()
+        opt.zero_grad()
+    out = {"op": "sap_training_step", "shape": "B=4 64^2 L=16 p=8 nc=3 embed 96 depth 2, fp32"}
+    for name, full in (("token_grid_loss", False), ("loss_at_full_resolution", True)):
+        ms = timed(lambda: step(full), reps)
+        out[name + "_ms"], out[name + "_ms_min_max"] = round(ms[0], 4), [round(ms[1], 4), round(ms[2], 4)]
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
@@ -168,6 +225,22 @@ def main():
                 t_ms, t_full = once(lambda: torch_deserialize(dim, seq, nodes, count, shape, p))
                 rec.update(torch_per_leaf_ms=round(t_ms, 2), speedup=round(t_ms / ms[0], 1), max_abs_diff_to_torch=float((full - t_full).abs().max().item()))
             print(json.dumps(rec), flush=True)
+            # ---- its adjoint: planar gradient of the image plane -> the model layout
+            bwd = ops.quadtree_deserialize_bwd if dim == 2 else ops.octree_deserialize_bwd
+            g = torch.randn_like(full)
+            dseq = bwd(g, nodes, count, seq, p, mode=mode, channels_last=False)
+            bms = timed(lambda: bwd(g, nodes, count, seq, p, mode=mode, channels_last=False), reps)
+            must = B * nc * (L * P + npix) * 4 + nodes.numel() * 4
+            rec = {"op": f"{'quadtree' if dim == 2 else 'octree'}_deserialize_bwd[{mode}]", **tag, "ms": round(bms[0], 4),
+                   "ms_min_max": [round(bms[1], 4), round(bms[2], 4)], "forward_ms": round(ms[0], 4), "over_forward": round(bms[0] / ms[0], 2),
+                   "bytes_must_move": must, "ms_at_hbm_rate": round(must / HBM * 1e3, 5),
+                   "same_bits_twice": bool(torch.equal(dseq, bwd(g, nodes, count, seq, p, mode=mode, channels_last=False)))}
+            if mode != "nearest":
+                t_ms, t_grad = torch_backward_ms(dim, seq, nodes, count, shape, p, g)
+                rec.update(torch_per_leaf_backward_ms=round(t_ms, 2), speedup=round(t_ms / bms[0], 1),
+                           max_abs_diff_to_torch=float((dseq - t_grad).abs().max().item()))
+            print(json.dumps(rec), flush=True)
+    sap_step(reps)
 
 
 if __name__ == "__main__":

@@ -979,6 +979,33 @@ class DiceBCEFn(torch.autograd.Function):
         return _ret_grad(dl, lg.dtype), None, None, None
 
 
+class DeserializeFn(torch.autograd.Function):
+    """Patchify.deserialize / Patchify_3D.deserialize with a gradient: a token sequence fp32 (the patch list [B, L, p, .., p, C] or the model
+    layout [B, C, L, p^nd], read in place) painted into the image plane through the tree (ops.quadtree_deserialize / octree_deserialize); backward
+    is the adjoint gather (ops.*_deserialize_bwd), deterministic, written in seq's own layout.  nodes / count carry no gradient.  Truncated
+    tokens have none either, so there is no `truncate` here."""
+
+    @staticmethod
+    def forward(ctx, seq, nodes, count, size, patch, nd, mode, channels_last):
+        if seq.dtype != torch.float32:
+            raise TypeError(f"DeserializeFn: seq must be fp32, got {seq.dtype} (HF.deserialize casts under autograd)")
+        fwd = ops.quadtree_deserialize if nd == 2 else ops.octree_deserialize
+        out = fwd(seq, nodes, count, size, patch, mode=mode, channels_last=channels_last)
+        ctx.save_for_backward(nodes, count)
+        ctx.like = torch.empty_like(seq, device="meta")                     # shape and strides of seq, no memory
+        ctx.args = (patch, nd, mode, channels_last)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        nodes, count = ctx.saved_tensors
+        patch, nd, mode, channels_last = ctx.args
+        d = dout if dout.dtype == torch.float32 else dout.float()
+        bwd = ops.quadtree_deserialize_bwd if nd == 2 else ops.octree_deserialize_bwd
+        dseq = bwd(d if d.is_contiguous() else d.contiguous(), nodes, count, ctx.like, patch, mode=mode, channels_last=channels_last)
+        return dseq, None, None, None, None, None, None, None
+
+
 # ---------------------------------------------------------------------------------------------- public helpers
 def instnorm_act(x, res=None, eps=1e-5, slope=0.01):
     return InstNormActFn.apply(x, res, eps, slope)
@@ -998,6 +1025,17 @@ def segment(logits, labels):
 
 def dice_bce(logits, targets, weight=0.5, smooth=1.0):
     return DiceBCEFn.apply(logits, targets, float(weight), float(smooth))
+
+
+def deserialize(seq, nodes, count, size, patch, nd, mode=None, channels_last=True):
+    """seq [B, L, p, .., p, C] or [B, C, L, p^nd] -> the image plane [B, *size, C] (channels_last) or [B, C, *size], differentiable in seq;
+    nd = 2: size (H, W), mode 'bicubic' (default) or 'nearest'; nd = 3: size N, 'trilinear' or 'nearest'.  A seq that is not fp32 (SAP's bf16
+    output) is cast here, under autograd, so its gradient comes back in its own dtype."""
+    if nd not in (2, 3):
+        raise ValueError(f"deserialize: nd must be 2 or 3, got {nd}")
+    mode = ("bicubic" if nd == 2 else "trilinear") if mode is None else mode
+    seq = seq if seq.dtype == torch.float32 else seq.float()
+    return DeserializeFn.apply(seq, nodes, count, size, int(patch), nd, mode, bool(channels_last))
 
 
 def cross_entropy(logits, labels):

@@ -17,7 +17,7 @@ GS_GROWTH_FACTOR, GS_BACKOFF_FACTOR, GS_GROWTH_INTERVAL, GS_MIN_SCALE, GS_STATE_
 # label dtypes and resampling modes of the label serializers / tree deserializers (UCFVIT_LABEL_*, UCFVIT_RESAMPLE_*)
 LABEL_U8, LABEL_I64 = 0, 1
 RESAMPLE_SMOOTH, RESAMPLE_NEAREST = 0, 1
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))  # .../ucf-vit_amd
 # UCFVIT_HIP_LIB: an alternative build of the same library (A/B measurements of kernel variants); never a non-HIP fallback
@@ -85,6 +85,10 @@ SIGNATURES = {
     "ucfvit_octree_serialize_labels": (c_int, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I, _P]),
     "ucfvit_quadtree_deserialize": (c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I, _I, _P]),
     "ucfvit_octree_deserialize": (c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I, _P]),
+    "ucfvit_quadtree_deserialize_bwd_workspace": (_I64, [_I64, _I64, _I64, _I64, _I64, _I64]),
+    "ucfvit_octree_deserialize_bwd_workspace": (_I64, [_I64, _I64, _I64, _I64, _I64]),
+    "ucfvit_quadtree_deserialize_bwd": (c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I, _P, _P]),
+    "ucfvit_octree_deserialize_bwd": (c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I, _P, _P]),
     "ucfvit_adaptive_pos_fwd": (c_int, [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I, _I, _I, _P]),
     "ucfvit_adaptive_pos_bwd_workspace": (_I64, [_I64, _I64, _I64, _I, _I, _I]),
     "ucfvit_adaptive_pos_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I, _I, _I, _P, _I, _P]),

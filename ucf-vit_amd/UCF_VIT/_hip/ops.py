@@ -657,6 +657,68 @@ def octree_deserialize(seq, nodes, count, size, patch, mode="trilinear", channel
     return _deserialize("octree_deserialize", 3, seq, nodes, count, size, patch, mode, False, channels_last)
 
 
+def _deserialize_bwd(name, nd, dout, nodes, count, seq_like_or_shape, patch, mode, channels_last):
+    L = _l.load()
+    if not isinstance(dout, torch.Tensor) or not dout.is_cuda:
+        raise RuntimeError(f"{name}.dout: expected a tensor on the MI355X (cuda) device, got {getattr(dout, 'device', type(dout))}")
+    _chk(nodes, f"{name}.nodes"), _chk(count, f"{name}.count")
+    if dout.dtype != torch.float32 or dout.dim() != nd + 2 or nodes.dtype != torch.int32 or nodes.dim() != 3 or nodes.shape[2] != 2 * nd or \
+            count.dtype != torch.int32 or count.dim() != 1:
+        raise TypeError(f"{name}: dout fp32 [B, {'H, W' if nd == 2 else 'N, N, N'}, C] or [B, C, ..], nodes int32 [B, L, {2 * nd}], count int32 [B]")
+    smooth = "bicubic" if nd == 2 else "trilinear"
+    if mode not in (smooth, "nearest"):
+        raise ValueError(f"{name}: mode must be '{smooth}' or 'nearest', got {mode!r}")
+    patch = int(patch)
+    if patch < 1:
+        raise ValueError(f"{name}: need patch >= 1")
+    if isinstance(seq_like_or_shape, torch.Tensor):
+        like = seq_like_or_shape
+        if like.dtype != torch.float32:
+            raise TypeError(f"{name}: the sequence the gradient is shaped like must be fp32, got {like.dtype}")
+        dseq = torch.empty_like(like, device=dout.device)               # the strides of a dense seq, contiguous otherwise
+    else:
+        dseq = torch.empty(tuple(int(v) for v in seq_like_or_shape), dtype=torch.float32, device=dout.device)
+    C, S, strides = _seq_strides(name, nd, dseq, patch)
+    B = dseq.shape[0]
+    size = tuple(dout.shape[1:1 + nd]) if channels_last else tuple(dout.shape[2:])
+    if nd == 3 and len(set(size)) != 1:
+        raise ValueError(f"{name}: dout must hold cubic volumes, got {size}")
+    if dout.shape[0] != B or (dout.shape[-1] if channels_last else dout.shape[1]) != C or nodes.shape[0] != B or nodes.shape[1] != S or \
+            count.shape[0] != B:
+        raise ValueError(f"{name}: dout, the sequence shape, nodes and count disagree on batch size, channels or sequence length")
+    if not dout.is_contiguous():
+        raise RuntimeError(f"{name}: dout must be dense ({'[B, .., C]' if channels_last else '[B, C, ..]'} contiguous)")
+    if min(strides[1:]) <= 0 or (B > 1 and strides[0] <= 0):
+        raise RuntimeError(f"{name}: the gradient cannot be written into an expanded (zero-stride) view")
+    npix = math.prod(size)
+    ostr = (npix * C, 1, C) if channels_last else (npix * C, npix, 1)
+    m = _l.RESAMPLE_NEAREST if mode == "nearest" else _l.RESAMPLE_SMOOTH
+    dims = (size[0], size[1]) if nd == 2 else (size[0],)
+    query = L.ucfvit_quadtree_deserialize_bwd_workspace if nd == 2 else L.ucfvit_octree_deserialize_bwd_workspace
+    nbytes = query(B, *dims, C, S, patch)
+    if nbytes < 0:
+        _l.check(-1, query.__name__)
+    ws = workspace(nbytes, dout.device) if nbytes else None
+    fn = L.ucfvit_quadtree_deserialize_bwd if nd == 2 else L.ucfvit_octree_deserialize_bwd
+    _l.check(fn(dout.data_ptr(), nodes.data_ptr(), count.data_ptr(), dseq.data_ptr(), B, *dims, C, S, patch, *strides, *ostr, m, _p(ws), _stream()),
+             fn.__name__)
+    return dseq
+
+
+def quadtree_deserialize_bwd(dout, nodes, count, seq_like_or_shape, patch, mode="bicubic", channels_last=True):
+    """the adjoint of quadtree_deserialize: dout fp32 dense [B, H, W, C] (channels_last) or [B, C, H, W] -> dseq fp32 with the shape and strides
+    of the forward's seq (a tensor to be shaped like, or a shape: [B, L, p, p, C] or [B, C, L, p * p]); dseq[c, k] = sum over the leaf's pixels of
+    w(x, k) dout[c, x] with the forward's weights; every row is written, padding rows and empty leaves with 0; deterministic
+    (ucfvit_quadtree_deserialize_bwd).  Truncation has no gradient."""
+    return _deserialize_bwd("quadtree_deserialize_bwd", 2, dout, nodes, count, seq_like_or_shape, patch, mode, channels_last)
+
+
+def octree_deserialize_bwd(dout, nodes, count, seq_like_or_shape, patch, mode="trilinear", channels_last=True):
+    """the adjoint of octree_deserialize: dout fp32 dense [B, N, N, N, C] or [B, C, N, N, N] -> dseq fp32 [B, L, p, p, p, C] or [B, C, L, p^3]
+    (ucfvit_octree_deserialize_bwd)"""
+    return _deserialize_bwd("octree_deserialize_bwd", 3, dout, nodes, count, seq_like_or_shape, patch, mode, channels_last)
+
+
 def cross_entropy(logits, labels, grad_scale=1.0, want_grad=True):
     """returns (loss fp32 scalar tensor, dlogits or None, row_loss)"""
     L = _l.load()

@@ -8,6 +8,7 @@ passes the edge maps, e.g. computed by the reference's own transform on the host
 """
 import torch
 
+from .._hip import functional as HF
 from .._hip import ops
 
 
@@ -49,7 +50,6 @@ class _TreePatchify(torch.nn.Module):
         idx, onehot = fn(labels, nodes, count, self.patch_size, num_classes, want_idx=not one_hot, want_onehot=one_hot)
         return onehot if one_hot else idx
 
-    @torch.no_grad()
     def deserialize(self, seq, nodes, count, size, mode, truncate, channels_last):
         """a token sequence painted back into the image plane, read in place, uncovered pixels 0.
         2-D (reference quadtree.py:209-221 + Rect.set_area): seq fp32 [B, L, p, p, C] or the model layout [B, C, L, p*p], size = (H, W) -> fp32
@@ -57,11 +57,18 @@ class _TreePatchify(torch.nn.Module):
         first), 'nearest' keeps class maps exact.
         3-D (octree.py:201-213 + Cube.set_area): seq fp32 [B, L, p, p, p, C] or [B, C, L, p**3], size = N -> fp32 [B, N, N, N, C] or
         [B, C, N, N, N]; mode 'trilinear' (aligned corners) or 'nearest'; no truncation (commented out in the reference)."""
-        if self.nd == 2:
-            return ops.quadtree_deserialize(seq, nodes, count, size, self.patch_size, mode=mode, truncate=truncate, channels_last=channels_last)
-        if truncate:
-            raise ValueError("Patchify_3D.deserialize: the 3-D rule has no truncation")
-        return ops.octree_deserialize(seq, nodes, count, size, self.patch_size, mode=mode, channels_last=channels_last)
+        if torch.is_grad_enabled() and seq.requires_grad:
+            # a loss at full resolution: the differentiable path (HF.deserialize, backward = the adjoint gather)
+            if truncate:
+                raise ValueError(f"{type(self).__name__}.deserialize: truncate=True has no gradient (truncf is flat almost everywhere), but seq "
+                                 "requires grad; detach seq or drop truncate")
+            return HF.deserialize(seq, nodes, count, size, self.patch_size, self.nd, mode=mode, channels_last=channels_last)
+        with torch.no_grad():
+            if self.nd == 2:
+                return ops.quadtree_deserialize(seq, nodes, count, size, self.patch_size, mode=mode, truncate=truncate, channels_last=channels_last)
+            if truncate:
+                raise ValueError("Patchify_3D.deserialize: the 3-D rule has no truncation")
+            return ops.octree_deserialize(seq, nodes, count, size, self.patch_size, mode=mode, channels_last=channels_last)
 
 
 class Patchify(_TreePatchify):

@@ -15,6 +15,7 @@
 // Without it a result depends on the source alone and equals a plain fp32 evaluation of the same expressions, so the sampling expressions
 // below can move between functions without changing a bit (quadtree.hip's serializers, built with contraction, cannot: see there).
 #include "patcher_tree.h"            // Leaf, leaf_index
+#include "patcher_leaf.h"            // BlockLeaf, pixel_of, Dims, out_layout, check_image, max_patch
 #include "resample_rules.h"
 
 namespace {
@@ -32,29 +33,6 @@ __device__ __forceinline__ void put_label(long long v, int64_t* idx_out, float* 
     if (onehot)
         for (int c = 0; c < nc; ++c) onehot[(int64_t)c * plane] = (v == (long long)c) ? 1.f : 0.f;
 }
-
-// the leaf of workgroup blockIdx.x = b * L + s; `live`: a row below count[b] whose box is not empty and lies in the image
-template <int ND>
-struct BlockLeaf {
-    int b, s;
-    Leaf<ND> leaf;
-    bool live;
-    __device__ __forceinline__ BlockLeaf(const int* __restrict__ nodes, const int* __restrict__ count, int L, const int (&dims)[ND])
-        : b((int)(blockIdx.x / (unsigned)L)), s((int)(blockIdx.x - (unsigned)b * (unsigned)L)), leaf(nodes + (int64_t)blockIdx.x * (2 * ND)) {
-        live = s < count[b] && !leaf.empty() && leaf.inside(dims);
-    }
-};
-
-// pixel number of leaf-local position x in an image of dims[a] pixels along axis a (x fastest)
-template <int ND>
-__device__ __forceinline__ int64_t pixel_of(const Leaf<ND>& lf, const int (&x)[ND], const int (&dims)[ND]) {
-    int64_t pix = lf.o[ND - 1] + x[ND - 1];
-#pragma unroll
-    for (int a = ND - 2; a >= 0; --a) pix = pix * dims[a] + (lf.o[a] + x[a]);
-    return pix;
-}
-
-template <int ND> struct Dims { int n[ND]; };              // pixels per axis, x first: (W, H) or (N, N, N)
 
 // labels [B][dims, x fastest] -> p^ND resampled labels per leaf, patch axis 0 the slowest image axis (octree.py: img[z1:z2, y1:y2, x1:x2]).
 // Per axis the 2-D rule is cv2's nearest_floor, the 3-D rule scipy's nearest_grid.
@@ -124,7 +102,9 @@ __global__ __launch_bounds__(DES_THREADS) void quadtree_deserialize_kernel(const
         if (NEAREST) {
             acc = src[(int64_t)(nearest_floor(y, p, h) * p + nearest_floor(x, p, w)) * se];
         } else {
-            const float fy = ((float)y + 0.5f) * sy - 0.5f, fx = ((float)x + 0.5f) * sx - 0.5f;
+            // positions and coefficients are resample_rules.h's, as the adjoint (patcher_labels_bwd.hip) evaluates them; the integer clamps of the
+            // taps stay written out here (tap_clamp there): calling them moved this kernel's register allocation
+            const float fy = half_pixel_pos(y, sy), fx = half_pixel_pos(x, sx);
             const float fyf = floorf(fy), fxf = floorf(fx);
             const int iy = (int)fyf, ix = (int)fxf;
             float wy[4], wx[4];
@@ -161,8 +141,7 @@ __global__ __launch_bounds__(DES_THREADS) void octree_deserialize_kernel(const f
     const BlockLeaf<3> bl(nodes, count, L, dims);
     if (!bl.live) return;
     const int nx = bl.leaf.n[0], ny = bl.leaf.n[1], nz = bl.leaf.n[2];
-    const float invx = nx > 1 ? 1.f / (float)(nx - 1) : 0.f, invy = ny > 1 ? 1.f / (float)(ny - 1) : 0.f,
-                invz = nz > 1 ? 1.f / (float)(nz - 1) : 0.f;
+    const float invx = linear_inv(nx), invy = linear_inv(ny), invz = linear_inv(nz);
     const float* src_s = seq + (int64_t)bl.b * sb + (int64_t)bl.s * ss;
     paint_leaf<3>(bl.leaf, dims, C, c_fast, out + (int64_t)bl.b * ob, oc, op, [&](int c, const int (&xyz)[3]) {
         const int x = xyz[0], y = xyz[1], z = xyz[2];
@@ -172,7 +151,8 @@ __global__ __launch_bounds__(DES_THREADS) void octree_deserialize_kernel(const f
         if (NEAREST) {
             acc = at(nearest_grid(z, p, nz), nearest_grid(y, p, ny), nearest_grid(x, p, nx));
         } else {
-            const float fz = (float)z * (float)(p - 1) * invz, fy = (float)y * (float)(p - 1) * invy, fx = (float)x * (float)(p - 1) * invx;
+            // as above: linear_cell / linear_upper written out
+            const float fz = corner_pos(z, p, invz), fy = corner_pos(y, p, invy), fx = corner_pos(x, p, invx);
             int z0 = (int)fz, y0 = (int)fy, x0 = (int)fx;
             z0 = z0 > p - 1 ? p - 1 : z0;
             y0 = y0 > p - 1 ? p - 1 : y0;
@@ -190,20 +170,6 @@ __global__ __launch_bounds__(DES_THREADS) void octree_deserialize_kernel(const f
     });
 }
 
-// the output must be one of the two dense layouts of B images of S pixels and C channels: planar [B][C][S] or channels-last [B][S][C]
-int out_layout(int64_t S, int64_t C, int64_t ob, int64_t oc, int64_t op, int* c_fast) {
-    if (ob != S * C) return 0;
-    if (oc == S && op == 1) {
-        *c_fast = 0;
-        return 1;
-    }
-    if (oc == 1 && op == C) {
-        *c_fast = 1;
-        return 1;
-    }
-    return 0;
-}
-
 // grid.y: the workgroups that share one leaf; a workgroup walks its leaf in steps of grid.y chunks.  The host cannot see the largest leaf, so
 // the rows are a fixed number: 16 where leaves are many (a workgroup whose first chunk lies past its leaf returns at once, but 131072 of them
 // still cost 45 us on an MI355X, measured: more rows lost at 1024 leaves of 64^3, fewer lost at 8192 leaves of 512^2, where the 256^2 leaf
@@ -217,18 +183,6 @@ unsigned chunk_rows(int64_t leaves, int64_t max_leaf_outputs) {
     gy = gy > max_chunks ? max_chunks : gy;
     return (unsigned)(gy > 65535 ? 65535 : gy);
 }
-
-// the image of an op, dims x first: 2-D H x W with sides below 32768, 3-D cubic of side 1..256
-template <int ND>
-int check_image(const char* who, int64_t B, const int64_t (&dims)[ND]) {
-    if (ND == 2)
-        UCF_CHECK_ARG(B >= 0 && dims[1] > 0 && dims[0] > 0 && dims[1] < 32768 && dims[0] < 32768, "%s: image %lld x %lld out of range", who,
-                      (long long)dims[1], (long long)dims[0]);
-    else
-        UCF_CHECK_ARG(B >= 0 && dims[0] > 0 && dims[0] <= 256, "%s: cubic volumes of side 1..256 (got %lld)", who, (long long)dims[0]);
-    return UCFVIT_OK;
-}
-constexpr int64_t max_patch(int nd) { return nd == 2 ? 1024 : 256; }
 
 template <int ND>
 int serialize_labels(const char* who, const void* labels, const int32_t* nodes, const int32_t* count, int64_t* idx, float* onehot, int64_t B,
@@ -257,17 +211,9 @@ template <int ND, typename Launch>
 int deserialize(const char* who, const float* seq, const int32_t* nodes, const int32_t* count, float* out, int64_t B, const int64_t (&dims)[ND],
                 int64_t C, int64_t L, int64_t p, int64_t stride_b, int64_t stride_c, int64_t stride_s, int64_t stride_e, int64_t out_b, int64_t out_c,
                 int64_t out_pixel, int mode, hipStream_t s, Launch launch) {
-    UCF_CHECK_ARG(mode == UCFVIT_RESAMPLE_SMOOTH || mode == UCFVIT_RESAMPLE_NEAREST, "%s: unknown mode %d", who, mode);
-    if (int rc = check_image<ND>(who, B, dims)) return rc;
-    UCF_CHECK_ARG(C > 0 && C <= 255 && L > 0 && p > 0 && p <= max_patch(ND) && B * L < (1ll << 31), "%s: bad shape (C=%lld, L=%lld, p=%lld)", who,
-                  (long long)C, (long long)L, (long long)p);
-    UCF_CHECK_ARG(stride_b >= 0 && stride_c > 0 && stride_s > 0 && stride_e > 0, "%s: sequence strides must be positive", who);
-    int64_t S = 1;
-    for (int a = 0; a < ND; ++a) S *= dims[a];
+    int64_t S = 0;
     int c_fast = 0;
-    const char* px = ND == 2 ? "[H][W]" : "[N][N][N]";
-    UCF_CHECK_ARG(out_layout(S, C, out_b, out_c, out_pixel, &c_fast), "%s: output strides (%lld, %lld, %lld) are neither dense [B][C]%s nor dense [B]%s[C]",
-                  who, (long long)out_b, (long long)out_c, (long long)out_pixel, px, px);
+    if (int rc = check_deserialize<ND>(who, B, dims, C, L, p, stride_b, stride_c, stride_s, stride_e, out_b, out_c, out_pixel, mode, &S, &c_fast)) return rc;
     if (B == 0) return UCFVIT_OK;
     UCF_CHECK_ARG(seq && nodes && count && out, "%s: null pointer", who);
     if (hipMemsetAsync(out, 0, (size_t)(B * S * C) * sizeof(float), s) != hipSuccess) {

@@ -26,6 +26,22 @@ def training_step_adaptive(seq, seq_label, variables, net, patch_size, twoD, num
     return DiceBLoss(num_class=num_classes)(output, seq_label), output
 
 
+def training_step_full_resolution(seq, label_map, nodes, count, variables, net, patch_size, twoD, num_classes, sqrt_len, seq_ps, in_chans,
+                                  fixed_length):
+    """data: loss_at_full_resolution: the logits per class [B, nc, S, P] (the pseudo image's plain memory) are painted through the image's tree
+    into [B, nc, *img] under autograd (HF.deserialize) and the Dice+BCE loss is taken there against the one-hot of the label map, so that a
+    leaf weighs what it covers; the gradient comes back through the tree (ops.*_deserialize_bwd) into the head"""
+    from UCF_VIT.dataloaders.transform import Patchify, Patchify_3D
+    side = (patch_size * sqrt_len,) * (2 if twoD else 3)
+    output = net(torch.reshape(seq, (-1, in_chans) + side), variables, seq_ps)
+    logits = output.reshape(output.shape[0], num_classes, fixed_length, -1)
+    patcher = (Patchify if twoD else Patchify_3D)(fixed_length, patch_size, num_classes)
+    size = tuple(label_map.shape[1:]) if twoD else label_map.shape[1]
+    full = patcher.deserialize(logits, nodes, count, size, channels_last=False)
+    target = torch.nn.functional.one_hot(label_map.long(), num_classes).movedim(-1, 1).float().contiguous()
+    return DiceBLoss(num_class=num_classes)(full, target), output
+
+
 def full_resolution_dice(output, label_map, nodes, count, patch_size, num_classes, fixed_length, twoD):
     """Dice of a SAP prediction against the label map in the image plane: the pseudo image's plain memory is the logits per class in
     sequence layout [B, nc, S, P]; the tree paints them back (read in place) into [B, nc, *img] and one HIP pass takes argmax and counts"""
@@ -62,6 +78,10 @@ def main(device, local_rank, rank, world):
     # data: labels_from_image: True -- the label map lives in the image plane and reaches the sequence through the image's own tree
     # (Patchify.serialize_labels), and the epoch line reports the full-resolution Dice of the last batch (deserialize + segment)
     from_image = bool(d.get("labels_from_image", False))
+    # data: loss_at_full_resolution: True -- the loss itself is taken in the image plane (training_step_full_resolution), not on the token grid
+    full_loss = bool(d.get("loss_at_full_resolution", False))
+    if full_loss and not from_image:
+        raise ValueError("data: loss_at_full_resolution needs the label map and the tree of the image: set data: labels_from_image: True")
     loader = SyntheticSeqLoader(d["batch_size"], margs["in_chans"], margs["img_size"], margs["patch_size"], margs["fixed_length"], nc,
                                 iters_per_epoch(conf), device, 1234 + rank, labels_from_image=from_image)
     for epoch in range(epoch_start, conf["trainer"]["max_epochs"]):
@@ -75,8 +95,12 @@ def main(device, local_rank, rank, world):
                 # synthetic per-pixel labels from the data itself (brightness bands), one-hot over the classes, in sequence layout
                 band = torch.clamp((seq.mean(dim=1, keepdim=True) / 256.0 * nc).long(), 0, nc - 1)
                 seq_label = torch.zeros(seq.shape[0], nc, *seq.shape[2:], device=device).scatter_(1, band, 1.0)
-            loss, output = training_step_adaptive(seq / 255.0, seq_label, variables, net, margs["patch_size"], margs["twoD"], nc, sqrt_len, seq_ps,
-                                                  margs["in_chans"])
+            if full_loss:
+                loss, output = training_step_full_resolution(seq / 255.0, label_map, nodes, count, variables, net, margs["patch_size"], margs["twoD"],
+                                                             nc, sqrt_len, seq_ps, margs["in_chans"], margs["fixed_length"])
+            else:
+                loss, output = training_step_adaptive(seq / 255.0, seq_label, variables, net, margs["patch_size"], margs["twoD"], nc, sqrt_len,
+                                                      seq_ps, margs["in_chans"])
             epoch_loss += loss.detach()
             loss.backward()
             optimizer.step()
