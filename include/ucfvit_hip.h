@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define UCFVIT_ABI_VERSION 23
+#define UCFVIT_ABI_VERSION 24
 
 #define UCFVIT_OK 0
 #define UCFVIT_ERR_INVALID_ARGUMENT (-1)
@@ -676,6 +676,30 @@ int ucfvit_resample_trilinear_fwd(const void* x, void* y, int64_t B, int64_t Xi,
                                   int64_t C, int64_t ld_dst, const void* skip, int64_t Cs, void* stream);
 int ucfvit_resample_trilinear_bwd(const void* dy, void* dx, int64_t B, int64_t Xi, int64_t Yi, int64_t Zi, int64_t Xo, int64_t Yo, int64_t Zo,
                                   int64_t C, int64_t ld_dy, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Stochastic depth (csrc/drop_path.hip): timm's DropPath(drop_prob, scale_by_keep=True), which the reference's Block imports.  Every sample
+ * b of the batch has one scale s[b] (fp32, on the device): 0 for a dropped sample, 1 / keep (or 1) for a kept one.  Row r of a
+ * [rows][D] token matrix belongs to sample r / rows_per_sample; rows must be a multiple of rows_per_sample and below 2^30, s holds
+ * rows / rows_per_sample values.  fp32 arithmetic, one rounding to the output type.  16-byte accesses where D and the pointers allow
+ * (D % 8 == 0 for bf16, D % 4 == 0 for fp32, 16-byte aligned pointers, ldr a multiple of the same), else an element-wise path.
+ *
+ * ucfvit_drop_path_add: out[r][:] = res[r ldr + :] + s[r / rows_per_sample] * branch[r][:].  branch and out are dense [rows][D]; res has
+ *   the row stride ldr >= D (the last Block reads the class rows of the stream in place: ldr = N D, rows_per_sample = 1).  out may be
+ *   branch itself.  A sample with s == 0 copies res bit for bit and does not read branch: a non-finite value in a dropped branch does not
+ *   reach the stream, where timm's x + 0 * inf gives NaN.
+ * ucfvit_drop_path_scale: out[r][:] = s[r / rows_per_sample] * x[r][:] (the gradient of a branch, and the module applied on its own);
+ *   a sample with s == 0 writes zeros and does not read x.  out may be x itself.  colsum_partial (may be NULL): fp32 [R][D],
+ *   R = ucfvit_drop_path_colsum_rows(rows, rows_per_sample, D) (a host function, no HIP call), receives per row chunk the column sums of
+ *   the values written, taken in fp32 before they are rounded, in a fixed order; summed over its R rows (ucfvit_reduce_rows) they are
+ *   the bias gradient of the Linear layer that ends the branch.  No atomics: the same bits on every call.
+ * Arguments are checked before any HIP call.
+ * ------------------------------------------------------------------------------------------------------ */
+int64_t ucfvit_drop_path_colsum_rows(int64_t rows, int64_t rows_per_sample, int64_t D);
+int ucfvit_drop_path_add(const void* res, int64_t ldr, const void* branch, const float* s, void* out, int64_t rows, int64_t D,
+                         int64_t rows_per_sample, int dtype, void* stream);
+int ucfvit_drop_path_scale(const void* x, const float* s, void* out, float* colsum_partial, int64_t rows, int64_t D, int64_t rows_per_sample,
+                           int dtype, void* stream);
 
 #ifdef __cplusplus
 }

@@ -476,36 +476,81 @@ class MlpFn(torch.autograd.Function):
         return (_ret_grad(dx.view(in_shape), in_dtype),) + g + (None, None)
 
 
-class BlockFn(torch.autograd.Function):
-    """Block.forward (building_blocks.py:236-239) with LayerScale/DropPath = Identity:
-    x1 = x + proj(attn(norm1(x))) ; y = x1 + fc2(gelu(fc1(norm2(x1)))).  7 forward launches, residual adds and the
-    activation fused into GEMM epilogues; the residual-branch gradients are fused into the LayerNorm backward."""
+class DropPathFn(torch.autograd.Function):
+    """DropPath applied on its own: y = s ⊙ x with one fp32 scale per sample (s [B], x [B, ..., D]); backward is the same kernel on dy."""
 
     @staticmethod
-    def _run_forward(x2, B, N, num_heads, eps, c, params, tp):
+    def forward(ctx, x, s):
+        xc = x if x.is_contiguous() else x.contiguous()
+        B, D = xc.shape[0], xc.shape[-1]
+        x2 = xc.view(-1, D)
+        y = ops.drop_path_scale(x2, s, x2.shape[0] // B)
+        ctx.save_for_backward(s)
+        return y.view(x.shape)
+
+    @staticmethod
+    def backward(ctx, dy):
+        s, = ctx.saved_tensors
+        dc = dy if dy.is_contiguous() else dy.contiguous()
+        d2 = dc.view(-1, dc.shape[-1])
+        return ops.drop_path_scale(d2, s, d2.shape[0] // dc.shape[0]).view(dy.shape), None
+
+
+# Stochastic depth inside the fused Blocks.  A branch with a scale tensor s (fp32 [B], DropPath.draw) runs its exit GEMM without the
+# residual and ops.drop_path_add writes res + s ⊙ branch over the branch; a branch without one (s = None: eval, rate 0) keeps the residual
+# in the GEMM epilogue, launch for launch what it was.  Backward: the branch's output gradient is s ⊙ (stream gradient), and ITS column
+# sums are the bias gradient of proj / fc2 — not the column sums of the stream gradient that the LayerNorm backward kernels hand out.
+def _scaled_grad(dy2, s, rows_per_sample, want_sums):
+    """-> (s ⊙ dy2, its fp32 [D] column sums or None)"""
+    cs = torch.empty(dy2.shape[1], dtype=torch.float32, device=dy2.device) if want_sums else None
+    return ops.drop_path_scale(dy2, s, rows_per_sample, c_colsum=cs), cs
+
+
+def _refuse_group_drop_path(tp, s1, s2):
+    if tp is not None and (s1 is not None or s2 is not None):
+        raise NotImplementedError(f"drop_path under a tensor-parallel group (tp group {tp.group!r}, size {tp.size}): every rank of the group "
+                                  "would need the same draw; not implemented")
+
+
+class BlockFn(torch.autograd.Function):
+    """Block.forward (building_blocks.py:236-239) with LayerScale = Identity:
+    x1 = x + s1 ⊙ proj(attn(norm1(x))) ; y = x1 + s2 ⊙ fc2(gelu(fc1(norm2(x1)))).  Without drop path (s1 = s2 = None): 7 forward
+    launches, residual adds and the activation fused into GEMM epilogues; the residual-branch gradients are fused into the LayerNorm
+    backward.  With a scale a branch costs one row pass more forward (drop_path_add) and one backward (drop_path_scale)."""
+
+    @staticmethod
+    def _run_forward(x2, B, N, num_heads, eps, c, params, tp, s1=None, s2=None):
         n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b = params
         ln1, mean1, rstd1 = ops.layernorm_fwd(x2, c(n1w), c(n1b), eps)
-        x1, sa = _attn_fwd(ln1, B, N, num_heads, c(qkvw), c(qkvb), c(projw), c(projb), x2, tp)
+        x1, sa = _attn_fwd(ln1, B, N, num_heads, c(qkvw), c(qkvb), c(projw), c(projb), x2 if s1 is None else None, tp)
+        if s1 is not None:
+            ops.drop_path_add(x2, x1, s1, N)                                # x1 = x + s1 ⊙ branch, over the branch
         ln2, mean2, rstd2 = ops.layernorm_fwd(x1, c(n2w), c(n2b), eps)
-        y, sm = _mlp_fwd(ln2, c(f1w), c(f1b), c(f2w), c(f2b), x1, tp)
+        y, sm = _mlp_fwd(ln2, c(f1w), c(f1b), c(f2w), c(f2b), x1 if s2 is None else None, tp)
+        if s2 is not None:
+            ops.drop_path_add(x1, y, s2, N)
         return y, (mean1, rstd1, ln1, *sa, x1, mean2, rstd2, ln2, *sm)
 
     @staticmethod
-    def forward(ctx, x, n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b, num_heads, eps, cdtype, tp=None, recompute=False):
-        """recompute = activation checkpointing of the Block (reference: apply_activation_checkpointing(Block),
+    def forward(ctx, x, n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b, num_heads, eps, cdtype, tp=None, recompute=False,
+                s1=None, s2=None):
+        """s1, s2: the per-sample drop-path scales of the attention and the MLP branch (fp32 [B]); None = no drop path on that branch.
+        recompute = activation checkpointing of the Block (reference: apply_activation_checkpointing(Block),
         training_scripts/train_masked_fsdp.py:393-396): only the Block's INPUT is kept; backward re-runs the seven forward launches to
         rebuild ln1, qkv, o, lse, x1, ln2, h, a (15 of the 16 token matrices a Block otherwise keeps), then proceeds as usual.  The
-        rebuilt tensors are bit-identical (no atomics, fixed reduction orders), so gradients equal the non-checkpointed ones exactly."""
+        rebuilt tensors are bit-identical (no atomics, fixed reduction orders), so gradients equal the non-checkpointed ones exactly;
+        the scales are kept with the input, so the rebuilt forward uses the same draw."""
+        _refuse_group_drop_path(tp, s1, s2)
         xin = _as(x, cdtype)
         B, N, D = xin.shape
         x2 = xin.view(B * N, D)
         c = lambda p: compute_param(p, cdtype)
         params = (n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b)
-        y, saved = BlockFn._run_forward(x2, B, N, num_heads, eps, c, params, tp)
+        y, saved = BlockFn._run_forward(x2, B, N, num_heads, eps, c, params, tp, s1, s2)
         if recompute:
-            ctx.save_for_backward(x2, *params)
+            ctx.save_for_backward(x2, *params, s1, s2)
         else:
-            ctx.save_for_backward(x2, *saved, *params)
+            ctx.save_for_backward(x2, *saved, *params, s1, s2)
         ctx.meta = (B, N, num_heads, cdtype, x.dtype, tp)
         ctx.recompute, ctx.eps = recompute, eps
         return y.view(B, N, D)
@@ -515,28 +560,37 @@ class BlockFn(torch.autograd.Function):
         B, N, H, cdtype, in_dtype, tp = ctx.meta
         c = lambda p: compute_param(p, cdtype)
         if ctx.recompute:
-            x2, *params = ctx.saved_tensors
-            _, saved = BlockFn._run_forward(x2, B, N, H, ctx.eps, c, tuple(params), tp)
+            x2, *params, s1, s2 = ctx.saved_tensors
+            _, saved = BlockFn._run_forward(x2, B, N, H, ctx.eps, c, tuple(params), tp, s1, s2)
             (mean1, rstd1, ln1, qkv, o, lse, x1, mean2, rstd2, ln2, h, a) = saved
             n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b = params
         else:
             (x2, mean1, rstd1, ln1, qkv, o, lse, x1, mean2, rstd2, ln2, h, a,
-             n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b) = ctx.saved_tensors
+             n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b, s1, s2) = ctx.saved_tensors
         need = ctx.needs_input_grad
         dy2 = _as(dy, cdtype).reshape(x2.shape)
         wq = _queue_for(qkvw)
-        dln2, gm = _mlp_bwd(dy2, ln2, (h, a), c(f1w), c(f2w), f1w, f1b, f2w, f2b, need[9:13], tp, wq, dy2_colsum=_take_stream_colsum(wq, dy2))
+        dt2, cs2 = dy2, _take_stream_colsum(wq, dy2)       # always taken: the slot is cleared
+        if s2 is not None:
+            # the published sums are those of the unscaled dy: not this fc2's bias gradient; the sums of s2 ⊙ dy are
+            dt2, cs2 = _scaled_grad(dy2, s2, N, f2b is not None and need[12])
+        dln2, gm = _mlp_bwd(dt2, ln2, (h, a), c(f1w), c(f2w), f1w, f1b, f2w, f2b, need[9:13], tp, wq, dy2_colsum=cs2)
         # LayerNorm backward also sums its output (the residual-stream gradient) over the tokens: proj's bias gradient here ...
         projb_done = None
         pb_out, pb_acc = None, False
-        if _BIAS_FROM_EPILOGUE and projb is not None and need[6]:
+        if s1 is None and _BIAS_FROM_EPILOGUE and projb is not None and need[6]:
             pb_out, pb_acc = grad_target(projb)
             if pb_out is None:
                 pb_out = torch.empty(projb.shape, dtype=torch.float32, device=dy2.device)
             projb_done = (None if pb_acc else pb_out,)
         dx1, g_n2w, g_n2b = _ln_bwd(dln2, x1, c(n2w), mean2, rstd2, n2w, n2b, dres=dy2, dx_colsum=pb_out,       # + residual branch
                                     dx_colsum_accumulate=pb_acc)
-        dln1, ga = _attn_bwd(dx1, ln1, (qkv, o, lse), B, N, H, c(qkvw), c(projw), qkvw, qkvb, projw, projb, need[3:7], tp, wq,
+        dt1 = dx1
+        if s1 is not None:
+            # ... unless the branch is scaled: then the sums of s1 ⊙ dx1 are, and the LayerNorm backward above was not asked for any
+            dt1, cs1 = _scaled_grad(dx1, s1, N, projb is not None and need[6])
+            projb_done = (_bgrad_from(projb, cs1) if cs1 is not None else None,)
+        dln1, ga = _attn_bwd(dt1, ln1, (qkv, o, lse), B, N, H, c(qkvw), c(projw), qkvw, qkvb, projw, projb, need[3:7], tp, wq,
                              projb_done=projb_done)
         # ... and, published for whoever receives dx, the fc2 bias gradient of the Block before this one
         cs0 = torch.empty(x2.shape[1], dtype=torch.float32, device=dy2.device) if _BIAS_FROM_EPILOGUE else None
@@ -544,7 +598,7 @@ class BlockFn(torch.autograd.Function):
         if cs0 is not None and in_dtype == cdtype:
             _publish_stream_colsum(wq, dx, cs0)
         wq.end_block()                                   # the Block's 4 weight gradients: grouped launch now, or with the next Blocks'
-        return (_ret_grad(dx.view(B, N, -1), in_dtype), g_n1w, g_n1b) + ga + (g_n2w, g_n2b) + gm + (None, None, None, None, None)
+        return (_ret_grad(dx.view(B, N, -1), in_dtype), g_n1w, g_n1b) + ga + (g_n2w, g_n2b) + gm + (None,) * 7
 
 
 TAIL_ROWS = os.environ.get("UCFVIT_TAIL_ROWS", "1") != "0"     # A/B switch: 0 = the last Block runs dense like every other
@@ -561,31 +615,38 @@ class TailBlockFn(torch.autograd.Function):
     backward (dres_period = N), rounded once like the dense Block's."""
 
     @staticmethod
-    def _run_forward(x2, B, N, num_heads, eps, c, params):
+    def _run_forward(x2, B, N, num_heads, eps, c, params, s1=None, s2=None):
         n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b = params
         D = x2.shape[1]
         dh = D // num_heads
         ln1, mean1, rstd1 = ops.layernorm_fwd(x2, c(n1w), c(n1b), eps)
         qkv = ops.linear_fwd(ln1, c(qkvw), c(qkvb))
         o, lse = ops.attention_rows_fwd(qkv, B, N, num_heads, dh, dh ** -0.5, 0)
-        x1 = ops.linear_fwd(o, c(projw), c(projb), residual=x2.view(B, N, D)[:, 0])   # class rows of the stream: a [B, D] view, row stride N D
+        xc = x2.view(B, N, D)[:, 0]                                                  # class rows of the stream: a [B, D] view, row stride N D
+        x1 = ops.linear_fwd(o, c(projw), c(projb), residual=xc if s1 is None else None)
+        if s1 is not None:
+            ops.drop_path_add(xc, x1, s1, 1)                                         # one row per sample
         ln2, mean2, rstd2 = ops.layernorm_fwd(x1, c(n2w), c(n2b), eps)
-        y, (h, a) = _mlp_fwd(ln2, c(f1w), c(f1b), c(f2w), c(f2b), x1)
+        y, (h, a) = _mlp_fwd(ln2, c(f1w), c(f1b), c(f2w), c(f2b), x1 if s2 is None else None)
+        if s2 is not None:
+            ops.drop_path_add(x1, y, s2, 1)
         return y, (mean1, rstd1, ln1, qkv, o, lse, x1, mean2, rstd2, ln2, h, a)
 
     @staticmethod
-    def forward(ctx, x, n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b, num_heads, eps, cdtype, recompute=False):
-        """recompute: as in BlockFn, only the Block's input is kept and backward re-runs the forward launches (bit-identical)"""
+    def forward(ctx, x, n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b, num_heads, eps, cdtype, recompute=False,
+                s1=None, s2=None):
+        """recompute: as in BlockFn, only the Block's input is kept and backward re-runs the forward launches (bit-identical);
+        s1, s2: the drop-path scales of the two branches as in BlockFn, one row per sample from the attention on"""
         xin = _as(x, cdtype)
         B, N, D = xin.shape
         x2 = xin.view(B * N, D)
         c = lambda p: compute_param(p, cdtype)
         params = (n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b)
-        y, saved = TailBlockFn._run_forward(x2, B, N, num_heads, eps, c, params)
+        y, saved = TailBlockFn._run_forward(x2, B, N, num_heads, eps, c, params, s1, s2)
         if recompute:
-            ctx.save_for_backward(x2, *params)
+            ctx.save_for_backward(x2, *params, s1, s2)
         else:
-            ctx.save_for_backward(x2, *saved, *params)
+            ctx.save_for_backward(x2, *saved, *params, s1, s2)
         ctx.meta = (B, N, num_heads, cdtype, x.dtype)
         ctx.recompute, ctx.eps = recompute, eps
         return y
@@ -595,39 +656,46 @@ class TailBlockFn(torch.autograd.Function):
         B, N, H, cdtype, in_dtype = ctx.meta
         c = lambda p: compute_param(p, cdtype)
         if ctx.recompute:
-            x2, *params = ctx.saved_tensors
-            _, saved = TailBlockFn._run_forward(x2, B, N, H, ctx.eps, c, tuple(params))
+            x2, *params, s1, s2 = ctx.saved_tensors
+            _, saved = TailBlockFn._run_forward(x2, B, N, H, ctx.eps, c, tuple(params), s1, s2)
             (mean1, rstd1, ln1, qkv, o, lse, x1, mean2, rstd2, ln2, h, a) = saved
             n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b = params
         else:
             (x2, mean1, rstd1, ln1, qkv, o, lse, x1, mean2, rstd2, ln2, h, a,
-             n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b) = ctx.saved_tensors
+             n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b, s1, s2) = ctx.saved_tensors
         need = ctx.needs_input_grad
         D = x2.shape[1]
         dh = D // H
         dy2 = _as(dy, cdtype).reshape(B, D)
         wq = _queue_for(qkvw)
-        dln2, gm = _mlp_bwd(dy2, ln2, (h, a), c(f1w), c(f2w), f1w, f1b, f2w, f2b, need[9:13], None, wq, dy2_colsum=_take_stream_colsum(wq, dy2))
+        dt2, cs2 = dy2, _take_stream_colsum(wq, dy2)
+        if s2 is not None:                                 # as in BlockFn: the published sums of the unscaled dy are dropped
+            dt2, cs2 = _scaled_grad(dy2, s2, 1, f2b is not None and need[12])
+        dln2, gm = _mlp_bwd(dt2, ln2, (h, a), c(f1w), c(f2w), f1w, f1b, f2w, f2b, need[9:13], None, wq, dy2_colsum=cs2)
         pb_out, pb_acc, g_projb = None, False, None
-        if projb is not None and need[6]:
+        if s1 is None and projb is not None and need[6]:
             pb_out, pb_acc = grad_target(projb)
             if pb_out is None:
                 pb_out = torch.empty(projb.shape, dtype=torch.float32, device=dy2.device)
             g_projb = None if pb_acc else pb_out
         dx1, g_n2w, g_n2b = _ln_bwd(dln2, x1, c(n2w), mean2, rstd2, n2w, n2b, dres=dy2, dx_colsum=pb_out, dx_colsum_accumulate=pb_acc)
-        g_projw = _wgrad(projw, dx1, o, wq) if need[5] else None
+        dt1 = dx1
+        if s1 is not None:
+            dt1, cs1 = _scaled_grad(dx1, s1, 1, projb is not None and need[6])
+            g_projb = _bgrad_from(projb, cs1) if cs1 is not None else None
+        g_projw = _wgrad(projw, dt1, o, wq) if need[5] else None
         want_b = qkvb is not None and need[4]
         if want_b:
             # Q third: dq of every image, summed; K third: 0 exactly; V third: the column sums of the compact dO (see _attn_bwd)
             gb, acc = grad_target(qkvb)
             if gb is None:
                 gb, acc = torch.empty(3 * D, dtype=torch.float32, device=dy2.device), False
-            do = _dgrad(dx1, projw, c(projw), c_colsum=gb[2 * D:], c_colsum_accumulate=acc)
+            do = _dgrad(dt1, projw, c(projw), c_colsum=gb[2 * D:], c_colsum_accumulate=acc)
             dqkv, part = ops.attention_rows_bwd(qkv, o, do, lse, B, N, H, dh, dh ** -0.5, 0, want_colsum=True)
             ops.reduce_rows(part, gb[:2 * D], accumulate=acc)
             g_qkvb = None if acc else gb
         else:
-            do = _dgrad(dx1, projw, c(projw))
+            do = _dgrad(dt1, projw, c(projw))
             dqkv = ops.attention_rows_bwd(qkv, o, do, lse, B, N, H, dh, dh ** -0.5, 0)
             g_qkvb = None
         g_qkvw = _wgrad(qkvw, dqkv, ln1, wq) if need[3] else None
@@ -637,7 +705,7 @@ class TailBlockFn(torch.autograd.Function):
         if cs0 is not None and in_dtype == cdtype:
             _publish_stream_colsum(wq, dx, cs0)           # the fc2 bias gradient of the Block before this one
         wq.end_block()
-        return (_ret_grad(dx.view(B, N, D), in_dtype), g_n1w, g_n1b, g_qkvw, g_qkvb, g_projw, g_projb, g_n2w, g_n2b) + gm + (None, None, None, None)
+        return (_ret_grad(dx.view(B, N, D), in_dtype), g_n1w, g_n1b, g_qkvw, g_qkvb, g_projw, g_projb, g_n2w, g_n2b) + gm + (None,) * 6
 
 
 class PatchEmbedFn(torch.autograd.Function):

@@ -17,7 +17,7 @@ GS_GROWTH_FACTOR, GS_BACKOFF_FACTOR, GS_GROWTH_INTERVAL, GS_MIN_SCALE, GS_STATE_
 # label dtypes and resampling modes of the label serializers / tree deserializers (UCFVIT_LABEL_*, UCFVIT_RESAMPLE_*)
 LABEL_U8, LABEL_I64 = 0, 1
 RESAMPLE_SMOOTH, RESAMPLE_NEAREST = 0, 1
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))  # .../ucf-vit_amd
 # UCFVIT_HIP_LIB: an alternative build of the same library (A/B measurements of kernel variants); never a non-HIP fallback
@@ -147,6 +147,9 @@ SIGNATURES = {
     "ucfvit_grad_scaler_update": (c_int, [_P, _P]),
     "ucfvit_cast": (c_int, [_P, _P, _I64, _I, _I, _F, _P]),
     "ucfvit_transpose_batched": (c_int, [_P, _P, _P, _I64, _I64, _P]),
+    "ucfvit_drop_path_colsum_rows": (_I64, [_I64, _I64, _I64]),
+    "ucfvit_drop_path_add": (c_int, [_P, _I64, _P, _P, _P, _I64, _I64, _I64, _I, _P]),
+    "ucfvit_drop_path_scale": (c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _I, _P]),
 }
 
 _lib = None

@@ -1463,6 +1463,57 @@ def cast(src, dst, scale=1.0):
     return dst
 
 
+# ------------------------------------------------------------------------------------------------ stochastic depth
+def _chk_drop_scale(s, rows, rows_per_sample, name):
+    _chk(s, name + ".s")
+    if rows_per_sample <= 0 or rows % rows_per_sample:
+        raise ValueError(f"{name}: {rows} rows are not a multiple of rows_per_sample={rows_per_sample}")
+    if s.dtype != torch.float32 or s.dim() != 1 or s.numel() != rows // rows_per_sample:
+        raise TypeError(f"{name}: s must be a contiguous fp32 tensor of rows / rows_per_sample = {rows // rows_per_sample} elements")
+
+
+def drop_path_add(res, branch, s, rows_per_sample, out=None):
+    """out[r] = res[r] + s[r // rows_per_sample] * branch[r]; res [rows, D] may have padded rows (a strided view of the stream), out may
+    be branch (the default: the branch is overwritten).  A sample with s == 0 is copied from res without reading branch."""
+    L = _l.load()
+    _chk(res, "drop_path_add.res", rows_ok=True), _chk(branch, "drop_path_add.branch")
+    rows, D = branch.shape
+    out = branch if out is None else _chk(out, "drop_path_add.out")
+    if tuple(res.shape) != (rows, D) or tuple(out.shape) != (rows, D) or res.dtype != branch.dtype or out.dtype != branch.dtype:
+        raise TypeError("drop_path_add: res, branch and out must be [rows, D] of one dtype")
+    _chk_drop_scale(s, rows, rows_per_sample, "drop_path_add")
+    _l.check(L.ucfvit_drop_path_add(res.data_ptr(), res.stride(0), branch.data_ptr(), s.data_ptr(), out.data_ptr(), rows, D,
+                                    int(rows_per_sample), dt(branch), _stream()), "ucfvit_drop_path_add")
+    return out
+
+
+def drop_path_scale(x, s, rows_per_sample, out=None, c_colsum=None, c_colsum_accumulate=False):
+    """out[r] = s[r // rows_per_sample] * x[r] for x [rows, D]; c_colsum: optional fp32 [D] that receives (+)= the column sums of the
+    values written (taken in fp32 before rounding; partial sums per row chunk from the kernel, folded by ucfvit_reduce_rows)"""
+    L = _l.load()
+    _chk(x, "drop_path_scale.x")
+    rows, D = x.shape
+    out = torch.empty_like(x) if out is None else _chk(out, "drop_path_scale.out")
+    if tuple(out.shape) != (rows, D) or out.dtype != x.dtype:
+        raise TypeError("drop_path_scale: out must have x's shape and dtype")
+    _chk_drop_scale(s, rows, rows_per_sample, "drop_path_scale")
+    cs_rows, part = 0, None
+    if c_colsum is not None:
+        _chk(c_colsum, "drop_path_scale.c_colsum")
+        if c_colsum.dtype != torch.float32 or c_colsum.numel() != D:
+            raise TypeError("drop_path_scale: c_colsum must be a contiguous fp32 tensor of D elements")
+        cs_rows = L.ucfvit_drop_path_colsum_rows(rows, int(rows_per_sample), D)
+        if cs_rows <= 0:
+            raise ValueError("drop_path_scale: no column sums of an empty input")
+        part = workspace(cs_rows * D * 4, x.device)
+    _l.check(L.ucfvit_drop_path_scale(x.data_ptr(), s.data_ptr(), out.data_ptr(), _p(part), rows, D, int(rows_per_sample), dt(x), _stream()),
+             "ucfvit_drop_path_scale")
+    if part is not None:
+        _l.check(L.ucfvit_reduce_rows(part.data_ptr(), c_colsum.data_ptr(), cs_rows, D, 1 if c_colsum_accumulate else 0, _stream()),
+                 "ucfvit_reduce_rows")
+    return out
+
+
 def transpose_batched(src_flat, dst_flat, table, n_mats, total_tiles):
     L = _l.load()
     _l.check(L.ucfvit_transpose_batched(src_flat.data_ptr(), dst_flat.data_ptr(), table.data_ptr(), n_mats, total_tiles, _stream()),

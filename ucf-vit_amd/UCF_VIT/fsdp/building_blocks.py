@@ -16,7 +16,7 @@ import torch.nn as nn
 from UCF_VIT.simple.building_blocks import (  # noqa: F401  (re-exported operator set)
     PatchEmbed, LayerNorm, Linear, DropPath, LayerScale, PatchDropout, MyUnetBlock, EmbeddingDenseLayer,
     VariableMapping_Attention, to_2tuple, to_3tuple, trunc_normal_, get_act_layer, get_norm_layer, LayerType,
-    set_compute_dtype, _cd, _no_dropout, _assert)
+    set_compute_dtype, _cd, _no_dropout, _assert, _draw_drop_path)
 from UCF_VIT.simple import building_blocks as _S
 from UCF_VIT.utils.fused_attn import FusedAttn
 from UCF_VIT._hip import functional as HF
@@ -90,6 +90,9 @@ class Block(nn.Module):
                  norm_layer: nn.Module = LayerNorm, mlp_layer: nn.Module = Mlp, tensor_par_size: int = 1,
                  tensor_par_group: Optional[dist.ProcessGroup] = None) -> None:
         super().__init__()
+        if drop_path > 0.0 and tensor_par_size > 1:
+            raise NotImplementedError(f"Block(drop_path={drop_path}) under a tensor-parallel group (tensor_par_group={tensor_par_group!r}, "
+                                      f"tensor_par_size={tensor_par_size}): every rank of the group would need the same draw; not implemented")
         self.tensor_par_size, self.tensor_par_group = tensor_par_size, tensor_par_group
         self.norm1 = norm_layer(dim)
         self.attn = Attention(dim, fused_attn=fused_attn, num_heads=num_heads, qkv_bias=qkv_bias, qk_norm=qk_norm, attn_drop=attn_drop,
@@ -111,15 +114,16 @@ class Block(nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self._fusable() and x.dim() == 3:
             a, m = self.attn, self.mlp
-            for d in (self.drop_path1, self.drop_path2):
-                if isinstance(d, DropPath):
-                    _no_dropout(d.drop_prob, self.training, "drop_path")
             _no_dropout(a.attn_drop.p, self.training, "attn_drop")
             _no_dropout(a.proj_drop.p, self.training, "proj_drop")
             _no_dropout(m.drop1.p, self.training, "Mlp.drop")
-            return HF.BlockFn.apply(x, self.norm1.weight, self.norm1.bias, a.qkv.weight, a.qkv.bias, a.proj.weight, a.proj.bias,
-                                    self.norm2.weight, self.norm2.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias,
-                                    a.num_heads, self.norm1.eps, _cd(self), _tp(self.tensor_par_size, self.tensor_par_group),
-                                    getattr(self, "activation_checkpointing", False) and torch.is_grad_enabled())
+            args = (x, self.norm1.weight, self.norm1.bias, a.qkv.weight, a.qkv.bias, a.proj.weight, a.proj.bias,
+                    self.norm2.weight, self.norm2.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias,
+                    a.num_heads, self.norm1.eps, _cd(self), _tp(self.tensor_par_size, self.tensor_par_group),
+                    getattr(self, "activation_checkpointing", False) and torch.is_grad_enabled())
+            s1, s2 = _draw_drop_path(self.drop_path1, x), _draw_drop_path(self.drop_path2, x)      # None under a tensor-parallel group
+            if s1 is None and s2 is None:
+                return HF.BlockFn.apply(*args)
+            return HF.BlockFn.apply(*args, s1, s2)
         x = x + self.drop_path1(self.ls1(self.attn(self.norm1(x))))
         return x + self.drop_path2(self.ls2(self.mlp(self.norm2(x))))

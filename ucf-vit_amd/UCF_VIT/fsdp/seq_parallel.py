@@ -290,6 +290,10 @@ class SeqParallelBlock(nn.Module):
         super().__init__()
         self.block = block
         self.spg = seq_par if isinstance(seq_par, SeqParallelGroups) else _PlainGroup(seq_par)
+        for d in (getattr(block, "drop_path1", None), getattr(block, "drop_path2", None)):
+            if getattr(d, "drop_prob", 0.0) > 0.0:
+                raise NotImplementedError(f"Block(drop_path={d.drop_prob}) under a sequence-parallel group of {self.spg.size} ranks: every "
+                                          "rank of the group would need the same draw; not implemented")
         for p in block.parameters():
             p._ucf_sharded = "sequence"     # gradients are per-token-shard partial sums: HipGradScaler refuses a per-rank skip decision
 

@@ -84,13 +84,46 @@ class Linear(nn.Linear):
 
 
 class DropPath(nn.Module):
+    """Stochastic depth per sample (timm's DropPath, which the reference imports): in training sample b keeps its residual branch with
+    probability keep = 1 - drop_prob, and a kept branch is multiplied by 1 / keep (scale_by_keep).  The draw is B floats of host
+    plumbing on the device (it follows torch.manual_seed, no synchronisation); applying it is HIP (csrc/drop_path.hip).  Inside a fused
+    Block the module only draws: HF.BlockFn / HF.TailBlockFn take the scales."""
+
     def __init__(self, drop_prob: float = 0.0, scale_by_keep: bool = True):
         super().__init__()
         self.drop_prob = drop_prob
+        self.scale_by_keep = scale_by_keep
+        self.last_scale = None           # the scale tensor of the latest draw (fp32 [B]): for tests and inspection
+        self.generator = None            # None: torch's default generator of the device (torch.manual_seed); the training scripts set
+                                         # one per rank so that data-parallel ranks do not share a draw
+
+    def active(self):
+        return self.training and self.drop_prob > 0.0
+
+    def draw(self, B, device):
+        """fp32 [B] on `device`: 0 for a dropped sample, 1 / keep (1 without scale_by_keep, 0 when keep == 0) for a kept one"""
+        keep = 1.0 - self.drop_prob
+        s = torch.empty(B, dtype=torch.float32, device=device).bernoulli_(keep, generator=self.generator)
+        if keep > 0.0 and self.scale_by_keep:
+            s.div_(keep)
+        self.last_scale = s
+        return s
 
     def forward(self, x):
-        _no_dropout(self.drop_prob, self.training, "drop_path")
-        return x
+        if not self.active():
+            return x
+        if not x.is_cuda:
+            raise RuntimeError(f"DropPath: expected a tensor on the MI355X (cuda) device, got {x.device}. "
+                               "UCF_VIT operators run only through libucfvit_hip.so; there is no CPU path.")
+        return HF.DropPathFn.apply(x, self.draw(x.shape[0], x.device))
+
+    def extra_repr(self):
+        return f"drop_prob={round(self.drop_prob, 3):0.3f}"
+
+
+def _draw_drop_path(d, x):
+    """the scale tensor of one residual branch of a fused Block, or None when the branch has no drop path to apply"""
+    return d.draw(x.shape[0], x.device) if isinstance(d, DropPath) and d.active() else None
 
 
 class LayerScale(nn.Module):
@@ -212,8 +245,10 @@ class Attention(nn.Module):
 
 
 class Block(nn.Module):
-    """Pre-LN transformer block.  With the reference configuration (no LayerScale, drop_path 0, standard Attention/Mlp)
-    the whole block is ONE autograd node running a fixed sequence of fused HIP launches (HF.BlockFn)."""
+    """Pre-LN transformer block.  With the reference configuration (no LayerScale, standard Attention/Mlp) the whole block is ONE
+    autograd node running a fixed sequence of fused HIP launches (HF.BlockFn).  drop_path > 0 in training: the two DropPath modules
+    draw their per-sample scales and the node applies them (one row pass per branch and direction); eval or rate 0 runs the very
+    launches of a Block without drop path."""
 
     def __init__(self, dim: int, num_heads: int, fused_attn: FusedAttn = FusedAttn.NONE, mlp_ratio: float = 4.0,
                  qkv_bias: bool = False, qk_norm: bool = False, proj_drop: float = 0.0, attn_drop: float = 0.0,
@@ -241,32 +276,34 @@ class Block(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self._fusable() and x.dim() == 3:
-            for d in (self.drop_path1, self.drop_path2):
-                if isinstance(d, DropPath):
-                    _no_dropout(d.drop_prob, self.training, "drop_path")
             a, m = self.attn, self.mlp
             _no_dropout(a.attn_drop.p, self.training, "attn_drop")
             _no_dropout(a.proj_drop.p, self.training, "proj_drop")
             _no_dropout(m.drop1.p, self.training, "Mlp.drop")
-            return HF.BlockFn.apply(x, self.norm1.weight, self.norm1.bias, a.qkv.weight, a.qkv.bias, a.proj.weight, a.proj.bias,
-                                    self.norm2.weight, self.norm2.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias,
-                                    a.num_heads, self.norm1.eps, _cd(self), None, self.activation_checkpointing and torch.is_grad_enabled())
+            args = (x, self.norm1.weight, self.norm1.bias, a.qkv.weight, a.qkv.bias, a.proj.weight, a.proj.bias,
+                    self.norm2.weight, self.norm2.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias,
+                    a.num_heads, self.norm1.eps, _cd(self), None, self.activation_checkpointing and torch.is_grad_enabled())
+            s1, s2 = _draw_drop_path(self.drop_path1, x), _draw_drop_path(self.drop_path2, x)      # two independent draws, s1 first
+            if s1 is None and s2 is None:
+                return HF.BlockFn.apply(*args)
+            return HF.BlockFn.apply(*args, s1, s2)
         x = x + self.drop_path1(self.ls1(self.attn(self.norm1(x))))
         x = x + self.drop_path2(self.ls2(self.mlp(self.norm2(x))))
         return x
 
     def forward_class_rows(self, x: torch.Tensor) -> torch.Tensor:
         """forward(x)[:, 0] computed without the other rows (HF.TailBlockFn); the caller checked _fusable()"""
-        for d in (self.drop_path1, self.drop_path2):
-            if isinstance(d, DropPath):
-                _no_dropout(d.drop_prob, self.training, "drop_path")
         a, m = self.attn, self.mlp
         _no_dropout(a.attn_drop.p, self.training, "attn_drop")
         _no_dropout(a.proj_drop.p, self.training, "proj_drop")
         _no_dropout(m.drop1.p, self.training, "Mlp.drop")
-        return HF.TailBlockFn.apply(x, self.norm1.weight, self.norm1.bias, a.qkv.weight, a.qkv.bias, a.proj.weight, a.proj.bias,
-                                    self.norm2.weight, self.norm2.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias,
-                                    a.num_heads, self.norm1.eps, _cd(self), self.activation_checkpointing and torch.is_grad_enabled())
+        args = (x, self.norm1.weight, self.norm1.bias, a.qkv.weight, a.qkv.bias, a.proj.weight, a.proj.bias,
+                self.norm2.weight, self.norm2.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias,
+                a.num_heads, self.norm1.eps, _cd(self), self.activation_checkpointing and torch.is_grad_enabled())
+        s1, s2 = _draw_drop_path(self.drop_path1, x), _draw_drop_path(self.drop_path2, x)
+        if s1 is None and s2 is None:
+            return HF.TailBlockFn.apply(*args)
+        return HF.TailBlockFn.apply(*args, s1, s2)
 
 
 class MyUnetBlock(nn.Module):

@@ -51,6 +51,20 @@ def model_args(conf):
                 use_adaptive_pos_emb=bool(a.get("use_adaptive_pos_emb", False)) and adaptive), a, d
 
 
+def seed_drop_path(model, device, rank):
+    """The scripts seed torch alike on every rank (nobody calls torch.manual_seed: every process starts from torch's default seed), so
+    data-parallel ranks would draw the same stochastic-depth masks.  For THIS draw only, the DropPath modules of a rank share one device
+    generator seeded with torch.initial_seed() + rank; every other random stream stays as it was.  Returns the number of modules."""
+    from UCF_VIT.simple.building_blocks import DropPath
+    mods = [m for m in model.modules() if isinstance(m, DropPath) and m.drop_prob > 0.0]
+    if mods:
+        g = torch.Generator(device=device)
+        g.manual_seed(torch.initial_seed() + rank)
+        for m in mods:
+            m.generator = g
+    return len(mods)
+
+
 class SyntheticLoader:
     """per-rank synthetic batches shaped like the reference dataloader's output: (data fp32 un-normalised, label, variables)"""
 

@@ -9,7 +9,7 @@ import sys
 import torch
 
 from _common import (SyntheticSeqLoader, StepTimer, init_distributed, iters_per_epoch, load_config, maybe_resume, model_args, save_checkpoint,
-                     sqrt_len_of)
+                     seed_drop_path, sqrt_len_of)
 from UCF_VIT.simple.arch import SAP
 from UCF_VIT.utils.fused_attn import FusedAttn
 from UCF_VIT.utils.metrics import DiceBLoss
@@ -70,6 +70,7 @@ def main(device, local_rank, rank, world):
     model = SAP(num_classes=nc, sqrt_len=sqrt_len, sqrt_len_method=True, class_token=False, weight_init='skip', FusedAttn_option=FusedAttn.HIP,
                 **margs).to(device)
     model.set_compute_dtype(torch.bfloat16 if conf["trainer"].get("data_type", "float32") == "bfloat16" else torch.float32)
+    seed_drop_path(model, device, rank)                                      # stochastic depth: ranks must not share a draw
     net = HipDataParallel(model)
     optimizer = configure_optimizer(model, float(m["lr"]), float(m["beta_1"]), float(m["beta_2"]), float(m["weight_decay"]))
     scheduler = configure_scheduler(optimizer, int(m["warmup_steps"]), int(m["max_steps"]), float(m["warmup_start_lr"]), float(m["eta_min"]))
