@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define UCFVIT_ABI_VERSION 24
+#define UCFVIT_ABI_VERSION 24 /* still 24 with the dropout entry points (ucfvit_dropout, ucfvit_dropout_add): symbols were only added */
 
 #define UCFVIT_OK 0
 #define UCFVIT_ERR_INVALID_ARGUMENT (-1)
@@ -700,6 +700,39 @@ int ucfvit_drop_path_add(const void* res, int64_t ldr, const void* branch, const
                          int64_t rows_per_sample, int dtype, void* stream);
 int ucfvit_drop_path_scale(const void* x, const float* s, void* out, float* colsum_partial, int64_t rows, int64_t D, int64_t rows_per_sample,
                            int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Element-wise dropout (csrc/dropout.hip): nn.Dropout(p) in training on a [rows][D] token matrix, optionally together with the per-sample
+ * drop-path scale s of the section above (s == NULL means 1), so that a residual branch with both costs one row pass.
+ *
+ * The mask is a pure function of (seed, element index) and is never stored; the backward pass and an activation-checkpoint recomputation
+ * regenerate it from the same seed.  Definition (all integers unsigned, lo32 / hi32 the halves of a 64-bit value):
+ *   - element (r, c) of the logical [rows][D] matrix has the 64-bit index i = (r * row_step) * D + c;
+ *   - w = Philox4x32-10(counter = (lo32(i >> 2), hi32(i >> 2), 0, 0), key = (lo32(seed), hi32(seed)))[i & 3]
+ *     (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11; multipliers D2511F53 / CD9E8D57, key increments
+ *     9E3779B9 / BB67AE85, ten rounds, the key bumped before every round but the first: Random123's philox4x32_R(10, ...));
+ *   - the element is DROPPED iff w < T, T = min(2^32 - 1, floor(p * 2^32)), computed on the host in double;
+ *   - a kept element is multiplied by 1.0f / (1.0f - (float)p), an fp32 division, in fp32: with the row factor
+ *     f = s[r / rows_per_sample] * (1.0f / (1.0f - p)) (one fp32 product; without s just the quotient) the value is f * x;
+ *     a dropped element contributes exactly 0 whatever x holds (a select, so NaN / Inf under the mask do not pass).
+ *   The kernels take 0 < p < 1 (p == 0 and p == 1 need no mask: the caller returns the input / writes zeros).  row_step >= 1 is 1 for a
+ *   dense matrix and N for the class-row tail of the last Block, so that row b of the tail draws the mask of dense row b * N;
+ *   rows * row_step must stay below 2^32.  The mask depends on the index alone: the 16-byte and the element path (chosen as for drop
+ *   path), any grid and any residual stride give the same mask.  Ten rounds were kept after measuring: see profiles/dropout.md.
+ *
+ * ucfvit_dropout: out[r][c] = f_r * m(r, c) * x[r][c].  out may be x itself.  A row with s == 0 writes zeros and is not read.
+ *   colsum_partial (may be NULL): fp32 [R][D] with R = ucfvit_drop_path_colsum_rows(rows, rows_per_sample, D) -- the row-chunk geometry is
+ *   that of ucfvit_drop_path_scale, so its host function sizes these partials too -- receives per row chunk the column sums of the values
+ *   written, taken in fp32 before they are rounded, in a fixed order; ucfvit_reduce_rows folds the R rows (a bias gradient).
+ * ucfvit_dropout_add: out[r][c] = res[r ldr + c] + f_r * m(r, c) * branch[r][c]; res has the row stride ldr >= D, out may be branch
+ *   itself.  A row with s == 0 copies res bit for bit and does not read branch.
+ * fp32 arithmetic, one rounding to the output type; no atomics, the same bits on every call.  Arguments (null pointers, D, rows,
+ * rows % rows_per_sample, ldr < D, p outside (0, 1), row_step < 1, dtype) are checked before any HIP call.
+ * ------------------------------------------------------------------------------------------------------ */
+int ucfvit_dropout(const void* x, const float* s, void* out, float* colsum_partial, int64_t rows, int64_t D, int64_t rows_per_sample,
+                   int64_t row_step, double p, uint64_t seed, int dtype, void* stream);
+int ucfvit_dropout_add(const void* res, int64_t ldr, const void* branch, const float* s, void* out, int64_t rows, int64_t D,
+                       int64_t rows_per_sample, int64_t row_step, double p, uint64_t seed, int dtype, void* stream);
 
 #ifdef __cplusplus
 }

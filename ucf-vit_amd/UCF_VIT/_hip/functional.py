@@ -342,10 +342,13 @@ def _attn_bwd(dy2, x2, saved, B, N, H, wqkv, wproj, p_qkvw, p_qkvb, p_projw, p_p
     return dx, (g_qkvw, g_qkvb, g_projw, g_projb)
 
 
-def _mlp_fwd(x2, w1, b1, w2, b2, residual, tp=None):
+def _mlp_fwd(x2, w1, b1, w2, b2, residual, tp=None, drop1=None):
+    """drop1: the dropout site behind the activation (p, seed, row_step) or None; the dropped activation is what fc2 reads and what is saved"""
     h = torch.empty((x2.shape[0], w1.shape[0]), dtype=x2.dtype, device=x2.device)
     act = ACT_GELU_SAVE_DERIV if _saves_gelu_deriv(x2.dtype) else ACT_GELU
     a = ops.linear_fwd(x2, w1, b1, act=act, aux_out=h)                 # K7: fc1 GEMM + bias + erf-GELU (h: pre-activation, or gelu' of it)
+    if drop1 is not None:
+        _dropout(a, drop1, out=a)                                      # in place: a <- m ⊙ a / keep
     if tp and tp.rank != 0:
         residual = None
     y = ops.linear_fwd(a, w2, b2, residual=residual)                   # K7: fc2 GEMM + bias (+ residual)
@@ -354,8 +357,10 @@ def _mlp_fwd(x2, w1, b1, w2, b2, residual, tp=None):
     return y, (h, a)
 
 
-def _mlp_bwd(dy2, x2, saved, w1, w2, p_w1, p_b1, p_w2, p_b2, needs, tp=None, wq=None, dy2_colsum=None):
-    """dy2_colsum: column sums of dy2 when its producer (a LayerNorm backward) published them: the fc2 bias gradient"""
+def _mlp_bwd(dy2, x2, saved, w1, w2, p_w1, p_b1, p_w2, p_b2, needs, tp=None, wq=None, dy2_colsum=None, drop1=None):
+    """dy2_colsum: column sums of dy2 when its producer (a LayerNorm backward) published them: the fc2 bias gradient;
+    drop1: the dropout site behind the activation: dh is masked in place after the fused gelu' epilogue, and the column sums of the masked
+    dh (the fc1 bias gradient) come from that pass, not from the epilogue"""
     h, a = saved
     g_w2 = _wgrad(p_w2, dy2, a, wq) if needs[2] else None
     if p_b2 is not None and needs[3]:
@@ -364,7 +369,12 @@ def _mlp_bwd(dy2, x2, saved, w1, w2, p_w1, p_b1, p_w2, p_b2, needs, tp=None, wq=
         g_b2 = None
     # dgrad fused with gelu'(pre-activation); the fc1 bias gradient = column sums of dh comes out of the same epilogue
     need_b1 = p_b1 is not None and needs[1]
-    if need_b1 and _BIAS_FROM_EPILOGUE:
+    if drop1 is not None:
+        dh = _dgrad(dy2, p_w2, w2, aux=h, aux_is_deriv=_saves_gelu_deriv(h.dtype))
+        cs = torch.empty(dh.shape[1], dtype=torch.float32, device=dy2.device) if need_b1 else None
+        _dropout(dh, drop1, out=dh, c_colsum=cs)
+        g_b1 = _bgrad_from(p_b1, cs) if need_b1 else None
+    elif need_b1 and _BIAS_FROM_EPILOGUE:
         bout, bacc = grad_target(p_b1)
         if bout is None:
             bout = torch.empty(p_b1.shape, dtype=torch.float32, device=dy2.device)
@@ -433,14 +443,19 @@ class AttentionFn(torch.autograd.Function):
     """Attention.forward (building_blocks.py:157-192): qkv Linear -> fused SDPA -> proj Linear."""
 
     @staticmethod
-    def forward(ctx, x, qkvw, qkvb, projw, projb, num_heads, cdtype, tp=None):
+    def forward(ctx, x, qkvw, qkvb, projw, projb, num_heads, cdtype, tp=None, drop=None):
+        """drop: (p, seed) of proj_drop in training, or None"""
+        drop = _site(drop, tp)
         xin = _as(x, cdtype)
         B, N, D = xin.shape
         x2 = xin.view(B * N, D)
         c = lambda p: compute_param(p, cdtype)
         y, saved = _attn_fwd(x2, B, N, num_heads, c(qkvw), c(qkvb), c(projw), c(projb), None, tp)
+        if drop is not None:
+            _dropout(y, drop, out=y)
         ctx.save_for_backward(x2, *saved, qkvw, qkvb, projw, projb)
         ctx.meta = (B, N, num_heads, cdtype, x.dtype, tp)
+        ctx.drop = drop
         return y.view(B, N, D)
 
     @staticmethod
@@ -449,21 +464,31 @@ class AttentionFn(torch.autograd.Function):
         B, N, H, cdtype, in_dtype, tp = ctx.meta
         dy2 = _as(dy, cdtype).reshape(x2.shape)
         c = lambda p: compute_param(p, cdtype)
-        dx, g = _attn_bwd(dy2, x2, (qkv, o, lse), B, N, H, c(qkvw), c(projw), qkvw, qkvb, projw, projb, ctx.needs_input_grad[1:5], tp)
-        return (_ret_grad(dx.view(B, N, -1), in_dtype),) + g + (None, None, None)
+        projb_done = None
+        if ctx.drop is not None:                               # the gradient of proj's output, and its column sums: proj's bias gradient
+            dy2, cs = _branch_grad(dy2, None, 1, ctx.drop, projb is not None and ctx.needs_input_grad[4])
+            projb_done = (_bgrad_from(projb, cs) if cs is not None else None,)
+        dx, g = _attn_bwd(dy2, x2, (qkv, o, lse), B, N, H, c(qkvw), c(projw), qkvw, qkvb, projw, projb, ctx.needs_input_grad[1:5], tp,
+                          projb_done=projb_done)
+        return (_ret_grad(dx.view(B, N, -1), in_dtype),) + g + (None, None, None, None)
 
 
 class MlpFn(torch.autograd.Function):
-    """Mlp.forward (building_blocks.py:122-129): fc1 -> erf-GELU -> fc2 (drops are p=0, norm=Identity)."""
+    """Mlp.forward (building_blocks.py:122-129): fc1 -> erf-GELU -> drop1 -> fc2 -> drop2 (norm=Identity; the drops only in training)."""
 
     @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, cdtype, tp=None):
+    def forward(ctx, x, w1, b1, w2, b2, cdtype, tp=None, drop1=None, drop2=None):
+        """drop1, drop2: (p, seed) of the dropout behind the activation and behind fc2 in training, or None"""
+        drop1, drop2 = _site(drop1, tp), _site(drop2, tp)
         xin = _as(x, cdtype)
         x2 = xin.reshape(-1, xin.shape[-1])
         c = lambda p: compute_param(p, cdtype)
-        y, saved = _mlp_fwd(x2, c(w1), c(b1), c(w2), c(b2), None, tp)
+        y, saved = _mlp_fwd(x2, c(w1), c(b1), c(w2), c(b2), None, tp, drop1=drop1)
+        if drop2 is not None:
+            _dropout(y, drop2, out=y)
         ctx.save_for_backward(x2, *saved, w1, b1, w2, b2)
         ctx.meta = (cdtype, x.dtype, x.shape, tp)
+        ctx.drops = (drop1, drop2)
         return y.view(*x.shape[:-1], y.shape[-1])
 
     @staticmethod
@@ -472,8 +497,12 @@ class MlpFn(torch.autograd.Function):
         cdtype, in_dtype, in_shape, tp = ctx.meta
         dy2 = _as(dy, cdtype).reshape(-1, dy.shape[-1])
         c = lambda p: compute_param(p, cdtype)
-        dx, g = _mlp_bwd(dy2, x2, (h, a), c(w1), c(w2), w1, b1, w2, b2, ctx.needs_input_grad[1:5], tp)
-        return (_ret_grad(dx.view(in_shape), in_dtype),) + g + (None, None)
+        drop1, drop2 = ctx.drops
+        cs = None
+        if drop2 is not None:
+            dy2, cs = _branch_grad(dy2, None, 1, drop2, b2 is not None and ctx.needs_input_grad[4])
+        dx, g = _mlp_bwd(dy2, x2, (h, a), c(w1), c(w2), w1, b1, w2, b2, ctx.needs_input_grad[1:5], tp, dy2_colsum=cs, drop1=drop1)
+        return (_ret_grad(dx.view(in_shape), in_dtype),) + g + (None, None, None, None)
 
 
 class DropPathFn(torch.autograd.Function):
@@ -494,6 +523,71 @@ class DropPathFn(torch.autograd.Function):
         dc = dy if dy.is_contiguous() else dy.contiguous()
         d2 = dc.view(-1, dc.shape[-1])
         return ops.drop_path_scale(d2, s, d2.shape[0] // dc.shape[0]).view(dy.shape), None
+
+
+# Element-wise dropout.  A site is (p, seed, row_step): the rate, the 64-bit seed of this forward pass (a host integer, HipDropout.draw)
+# and the row step of the mask index (include/ucfvit_hip.h: 1 for a dense matrix, N for the class-row tail).  The mask is never stored:
+# backward and a checkpoint recomputation call the same kernel with the same seed.
+def _site(drop, tp=None, row_step=1):
+    """(p, seed) from a module -> the site tuple, None for no dropout; refused under a tensor-parallel group"""
+    if drop is None or drop[0] <= 0.0:
+        return None
+    if tp is not None:
+        raise NotImplementedError(f"dropout under a tensor-parallel group (tp group {tp.group!r}, size {tp.size}): every rank of the group "
+                                  "would need the same seed; not implemented")
+    return (float(drop[0]), int(drop[1]), int(row_step))
+
+
+def _dropout(x2, site, s=None, rows_per_sample=1, out=None, c_colsum=None):
+    """out = s ⊙ m ⊙ x2 / keep (ops.dropout).  p == 1 needs no mask: zeros"""
+    p, seed, row_step = site
+    if p >= 1.0:
+        out = torch.empty_like(x2) if out is None else out
+        if c_colsum is not None:
+            c_colsum.zero_()
+        return out.zero_()
+    return ops.dropout(x2, p, seed, s=s, rows_per_sample=rows_per_sample, row_step=row_step, out=out, c_colsum=c_colsum)
+
+
+def _branch_exit(res, y, s, rows_per_sample, site):
+    """the exit of a residual branch whose GEMM ran without the residual: y <- res + s ⊙ m ⊙ y / keep in place (site None: drop path only)"""
+    if site is None:
+        return ops.drop_path_add(res, y, s, rows_per_sample)
+    p, seed, row_step = site
+    if p >= 1.0:
+        return y.copy_(res)
+    return ops.dropout_add(res, y, p, seed, s=s, rows_per_sample=rows_per_sample, row_step=row_step)
+
+
+def _branch_grad(dy2, s, rows_per_sample, site, want_sums):
+    """-> (s ⊙ m ⊙ dy2 / keep, its fp32 [D] column sums or None): the gradient of a branch's exit GEMM output and that GEMM's bias gradient"""
+    if site is None:
+        return _scaled_grad(dy2, s, rows_per_sample, want_sums)
+    cs = torch.empty(dy2.shape[1], dtype=torch.float32, device=dy2.device) if want_sums else None
+    return _dropout(dy2, site, s, rows_per_sample, c_colsum=cs), cs
+
+
+def _block_sites(drop, tp, row_step):
+    """BlockFn's dropout argument (p, seed_proj, seed_drop1, seed_drop2) -> the three sites (proj, drop1, drop2)"""
+    if drop is None or drop[0] <= 0.0:
+        return None, None, None
+    p = drop[0]
+    return tuple(_site((p, seed), tp, row_step) for seed in drop[1:4])
+
+
+class DropoutFn(torch.autograd.Function):
+    """HipDropout applied on its own: y = m ⊙ x / keep over the last dimension's rows; backward is the same kernel on dy with the same seed."""
+
+    @staticmethod
+    def forward(ctx, x, p, seed):
+        xc = x if x.is_contiguous() else x.contiguous()
+        ctx.site = (float(p), int(seed), 1)
+        return _dropout(xc.view(-1, xc.shape[-1]), ctx.site).view(x.shape)
+
+    @staticmethod
+    def backward(ctx, dy):
+        dc = dy if dy.is_contiguous() else dy.contiguous()
+        return _dropout(dc.view(-1, dc.shape[-1]), ctx.site).view(dy.shape), None, None
 
 
 # Stochastic depth inside the fused Blocks.  A branch with a scale tensor s (fp32 [B], DropPath.draw) runs its exit GEMM without the
@@ -519,34 +613,41 @@ class BlockFn(torch.autograd.Function):
     backward.  With a scale a branch costs one row pass more forward (drop_path_add) and one backward (drop_path_scale)."""
 
     @staticmethod
-    def _run_forward(x2, B, N, num_heads, eps, c, params, tp, s1=None, s2=None):
+    def _run_forward(x2, B, N, num_heads, eps, c, params, tp, s1=None, s2=None, sites=(None, None, None)):
         n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b = params
+        dproj, d1, d2 = sites
+        plain1, plain2 = s1 is None and dproj is None, s2 is None and d2 is None
         ln1, mean1, rstd1 = ops.layernorm_fwd(x2, c(n1w), c(n1b), eps)
-        x1, sa = _attn_fwd(ln1, B, N, num_heads, c(qkvw), c(qkvb), c(projw), c(projb), x2 if s1 is None else None, tp)
-        if s1 is not None:
-            ops.drop_path_add(x2, x1, s1, N)                                # x1 = x + s1 ⊙ branch, over the branch
+        x1, sa = _attn_fwd(ln1, B, N, num_heads, c(qkvw), c(qkvb), c(projw), c(projb), x2 if plain1 else None, tp)
+        if not plain1:
+            _branch_exit(x2, x1, s1, N, dproj)                              # x1 = x + s1 ⊙ m ⊙ branch / keep, over the branch
         ln2, mean2, rstd2 = ops.layernorm_fwd(x1, c(n2w), c(n2b), eps)
-        y, sm = _mlp_fwd(ln2, c(f1w), c(f1b), c(f2w), c(f2b), x1 if s2 is None else None, tp)
-        if s2 is not None:
-            ops.drop_path_add(x1, y, s2, N)
+        y, sm = _mlp_fwd(ln2, c(f1w), c(f1b), c(f2w), c(f2b), x1 if plain2 else None, tp, drop1=d1)
+        if not plain2:
+            _branch_exit(x1, y, s2, N, d2)
         return y, (mean1, rstd1, ln1, *sa, x1, mean2, rstd2, ln2, *sm)
 
     @staticmethod
     def forward(ctx, x, n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b, num_heads, eps, cdtype, tp=None, recompute=False,
-                s1=None, s2=None):
+                s1=None, s2=None, drop=None):
         """s1, s2: the per-sample drop-path scales of the attention and the MLP branch (fp32 [B]); None = no drop path on that branch.
+        drop: (p, seed_proj, seed_drop1, seed_drop2) = the rate of proj_drop / Mlp.drop and this pass's seeds of the three sites, or None.
+        A branch with dropout runs its exit GEMM without the residual and ops.dropout_add writes res + s ⊙ m ⊙ branch / keep over it (the
+        drop-path scale rides along); drop1 masks the activation in place before fc2.  The seeds are host integers kept on ctx, so the
+        recomputation below regenerates the same masks.
         recompute = activation checkpointing of the Block (reference: apply_activation_checkpointing(Block),
         training_scripts/train_masked_fsdp.py:393-396): only the Block's INPUT is kept; backward re-runs the seven forward launches to
         rebuild ln1, qkv, o, lse, x1, ln2, h, a (15 of the 16 token matrices a Block otherwise keeps), then proceeds as usual.  The
         rebuilt tensors are bit-identical (no atomics, fixed reduction orders), so gradients equal the non-checkpointed ones exactly;
         the scales are kept with the input, so the rebuilt forward uses the same draw."""
         _refuse_group_drop_path(tp, s1, s2)
+        ctx.sites = sites = _block_sites(drop, tp, 1)
         xin = _as(x, cdtype)
         B, N, D = xin.shape
         x2 = xin.view(B * N, D)
         c = lambda p: compute_param(p, cdtype)
         params = (n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b)
-        y, saved = BlockFn._run_forward(x2, B, N, num_heads, eps, c, params, tp, s1, s2)
+        y, saved = BlockFn._run_forward(x2, B, N, num_heads, eps, c, params, tp, s1, s2, sites)
         if recompute:
             ctx.save_for_backward(x2, *params, s1, s2)
         else:
@@ -561,24 +662,25 @@ class BlockFn(torch.autograd.Function):
         c = lambda p: compute_param(p, cdtype)
         if ctx.recompute:
             x2, *params, s1, s2 = ctx.saved_tensors
-            _, saved = BlockFn._run_forward(x2, B, N, H, ctx.eps, c, tuple(params), tp, s1, s2)
+            _, saved = BlockFn._run_forward(x2, B, N, H, ctx.eps, c, tuple(params), tp, s1, s2, ctx.sites)
             (mean1, rstd1, ln1, qkv, o, lse, x1, mean2, rstd2, ln2, h, a) = saved
             n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b = params
         else:
             (x2, mean1, rstd1, ln1, qkv, o, lse, x1, mean2, rstd2, ln2, h, a,
              n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b, s1, s2) = ctx.saved_tensors
         need = ctx.needs_input_grad
+        dproj, d1, d2 = ctx.sites
         dy2 = _as(dy, cdtype).reshape(x2.shape)
         wq = _queue_for(qkvw)
         dt2, cs2 = dy2, _take_stream_colsum(wq, dy2)       # always taken: the slot is cleared
-        if s2 is not None:
-            # the published sums are those of the unscaled dy: not this fc2's bias gradient; the sums of s2 ⊙ dy are
-            dt2, cs2 = _scaled_grad(dy2, s2, N, f2b is not None and need[12])
-        dln2, gm = _mlp_bwd(dt2, ln2, (h, a), c(f1w), c(f2w), f1w, f1b, f2w, f2b, need[9:13], tp, wq, dy2_colsum=cs2)
+        if s2 is not None or d2 is not None:
+            # the published sums are those of the unscaled, unmasked dy: not this fc2's bias gradient; the sums of s2 ⊙ m ⊙ dy / keep are
+            dt2, cs2 = _branch_grad(dy2, s2, N, d2, f2b is not None and need[12])
+        dln2, gm = _mlp_bwd(dt2, ln2, (h, a), c(f1w), c(f2w), f1w, f1b, f2w, f2b, need[9:13], tp, wq, dy2_colsum=cs2, drop1=d1)
         # LayerNorm backward also sums its output (the residual-stream gradient) over the tokens: proj's bias gradient here ...
         projb_done = None
         pb_out, pb_acc = None, False
-        if s1 is None and _BIAS_FROM_EPILOGUE and projb is not None and need[6]:
+        if s1 is None and dproj is None and _BIAS_FROM_EPILOGUE and projb is not None and need[6]:
             pb_out, pb_acc = grad_target(projb)
             if pb_out is None:
                 pb_out = torch.empty(projb.shape, dtype=torch.float32, device=dy2.device)
@@ -586,9 +688,10 @@ class BlockFn(torch.autograd.Function):
         dx1, g_n2w, g_n2b = _ln_bwd(dln2, x1, c(n2w), mean2, rstd2, n2w, n2b, dres=dy2, dx_colsum=pb_out,       # + residual branch
                                     dx_colsum_accumulate=pb_acc)
         dt1 = dx1
-        if s1 is not None:
-            # ... unless the branch is scaled: then the sums of s1 ⊙ dx1 are, and the LayerNorm backward above was not asked for any
-            dt1, cs1 = _scaled_grad(dx1, s1, N, projb is not None and need[6])
+        if s1 is not None or dproj is not None:
+            # ... unless the branch is scaled or masked: then the sums of s1 ⊙ m ⊙ dx1 / keep are, and the LayerNorm backward above was not
+            # asked for any
+            dt1, cs1 = _branch_grad(dx1, s1, N, dproj, projb is not None and need[6])
             projb_done = (_bgrad_from(projb, cs1) if cs1 is not None else None,)
         dln1, ga = _attn_bwd(dt1, ln1, (qkv, o, lse), B, N, H, c(qkvw), c(projw), qkvw, qkvb, projw, projb, need[3:7], tp, wq,
                              projb_done=projb_done)
@@ -598,7 +701,7 @@ class BlockFn(torch.autograd.Function):
         if cs0 is not None and in_dtype == cdtype:
             _publish_stream_colsum(wq, dx, cs0)
         wq.end_block()                                   # the Block's 4 weight gradients: grouped launch now, or with the next Blocks'
-        return (_ret_grad(dx.view(B, N, -1), in_dtype), g_n1w, g_n1b) + ga + (g_n2w, g_n2b) + gm + (None,) * 7
+        return (_ret_grad(dx.view(B, N, -1), in_dtype), g_n1w, g_n1b) + ga + (g_n2w, g_n2b) + gm + (None,) * 8
 
 
 TAIL_ROWS = os.environ.get("UCFVIT_TAIL_ROWS", "1") != "0"     # A/B switch: 0 = the last Block runs dense like every other
@@ -615,34 +718,38 @@ class TailBlockFn(torch.autograd.Function):
     backward (dres_period = N), rounded once like the dense Block's."""
 
     @staticmethod
-    def _run_forward(x2, B, N, num_heads, eps, c, params, s1=None, s2=None):
+    def _run_forward(x2, B, N, num_heads, eps, c, params, s1=None, s2=None, sites=(None, None, None)):
         n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b = params
+        dproj, d1, d2 = sites
+        plain1, plain2 = s1 is None and dproj is None, s2 is None and d2 is None
         D = x2.shape[1]
         dh = D // num_heads
         ln1, mean1, rstd1 = ops.layernorm_fwd(x2, c(n1w), c(n1b), eps)
         qkv = ops.linear_fwd(ln1, c(qkvw), c(qkvb))
         o, lse = ops.attention_rows_fwd(qkv, B, N, num_heads, dh, dh ** -0.5, 0)
         xc = x2.view(B, N, D)[:, 0]                                                  # class rows of the stream: a [B, D] view, row stride N D
-        x1 = ops.linear_fwd(o, c(projw), c(projb), residual=xc if s1 is None else None)
-        if s1 is not None:
-            ops.drop_path_add(xc, x1, s1, 1)                                         # one row per sample
+        x1 = ops.linear_fwd(o, c(projw), c(projb), residual=xc if plain1 else None)
+        if not plain1:
+            _branch_exit(xc, x1, s1, 1, dproj)                                       # one row per sample; the mask of dense row b N
         ln2, mean2, rstd2 = ops.layernorm_fwd(x1, c(n2w), c(n2b), eps)
-        y, (h, a) = _mlp_fwd(ln2, c(f1w), c(f1b), c(f2w), c(f2b), x1 if s2 is None else None)
-        if s2 is not None:
-            ops.drop_path_add(x1, y, s2, 1)
+        y, (h, a) = _mlp_fwd(ln2, c(f1w), c(f1b), c(f2w), c(f2b), x1 if plain2 else None, drop1=d1)
+        if not plain2:
+            _branch_exit(x1, y, s2, 1, d2)
         return y, (mean1, rstd1, ln1, qkv, o, lse, x1, mean2, rstd2, ln2, h, a)
 
     @staticmethod
     def forward(ctx, x, n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b, num_heads, eps, cdtype, recompute=False,
-                s1=None, s2=None):
+                s1=None, s2=None, drop=None):
         """recompute: as in BlockFn, only the Block's input is kept and backward re-runs the forward launches (bit-identical);
-        s1, s2: the drop-path scales of the two branches as in BlockFn, one row per sample from the attention on"""
+        s1, s2: the drop-path scales of the two branches as in BlockFn, one row per sample from the attention on;
+        drop: BlockFn's dropout argument; the mask index steps by N rows, so class row b draws the mask of row b N of the dense Block"""
         xin = _as(x, cdtype)
         B, N, D = xin.shape
+        ctx.sites = sites = _block_sites(drop, None, N)
         x2 = xin.view(B * N, D)
         c = lambda p: compute_param(p, cdtype)
         params = (n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b)
-        y, saved = TailBlockFn._run_forward(x2, B, N, num_heads, eps, c, params, s1, s2)
+        y, saved = TailBlockFn._run_forward(x2, B, N, num_heads, eps, c, params, s1, s2, sites)
         if recompute:
             ctx.save_for_backward(x2, *params, s1, s2)
         else:
@@ -657,7 +764,7 @@ class TailBlockFn(torch.autograd.Function):
         c = lambda p: compute_param(p, cdtype)
         if ctx.recompute:
             x2, *params, s1, s2 = ctx.saved_tensors
-            _, saved = TailBlockFn._run_forward(x2, B, N, H, ctx.eps, c, tuple(params), s1, s2)
+            _, saved = TailBlockFn._run_forward(x2, B, N, H, ctx.eps, c, tuple(params), s1, s2, ctx.sites)
             (mean1, rstd1, ln1, qkv, o, lse, x1, mean2, rstd2, ln2, h, a) = saved
             n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b = params
         else:
@@ -668,20 +775,21 @@ class TailBlockFn(torch.autograd.Function):
         dh = D // H
         dy2 = _as(dy, cdtype).reshape(B, D)
         wq = _queue_for(qkvw)
+        dproj, d1, d2 = ctx.sites
         dt2, cs2 = dy2, _take_stream_colsum(wq, dy2)
-        if s2 is not None:                                 # as in BlockFn: the published sums of the unscaled dy are dropped
-            dt2, cs2 = _scaled_grad(dy2, s2, 1, f2b is not None and need[12])
-        dln2, gm = _mlp_bwd(dt2, ln2, (h, a), c(f1w), c(f2w), f1w, f1b, f2w, f2b, need[9:13], None, wq, dy2_colsum=cs2)
+        if s2 is not None or d2 is not None:               # as in BlockFn: the published sums of the unscaled dy are dropped
+            dt2, cs2 = _branch_grad(dy2, s2, 1, d2, f2b is not None and need[12])
+        dln2, gm = _mlp_bwd(dt2, ln2, (h, a), c(f1w), c(f2w), f1w, f1b, f2w, f2b, need[9:13], None, wq, dy2_colsum=cs2, drop1=d1)
         pb_out, pb_acc, g_projb = None, False, None
-        if s1 is None and projb is not None and need[6]:
+        if s1 is None and dproj is None and projb is not None and need[6]:
             pb_out, pb_acc = grad_target(projb)
             if pb_out is None:
                 pb_out = torch.empty(projb.shape, dtype=torch.float32, device=dy2.device)
             g_projb = None if pb_acc else pb_out
         dx1, g_n2w, g_n2b = _ln_bwd(dln2, x1, c(n2w), mean2, rstd2, n2w, n2b, dres=dy2, dx_colsum=pb_out, dx_colsum_accumulate=pb_acc)
         dt1 = dx1
-        if s1 is not None:
-            dt1, cs1 = _scaled_grad(dx1, s1, 1, projb is not None and need[6])
+        if s1 is not None or dproj is not None:
+            dt1, cs1 = _branch_grad(dx1, s1, 1, dproj, projb is not None and need[6])
             g_projb = _bgrad_from(projb, cs1) if cs1 is not None else None
         g_projw = _wgrad(projw, dt1, o, wq) if need[5] else None
         want_b = qkvb is not None and need[4]
@@ -705,7 +813,7 @@ class TailBlockFn(torch.autograd.Function):
         if cs0 is not None and in_dtype == cdtype:
             _publish_stream_colsum(wq, dx, cs0)           # the fc2 bias gradient of the Block before this one
         wq.end_block()
-        return (_ret_grad(dx.view(B, N, D), in_dtype), g_n1w, g_n1b, g_qkvw, g_qkvb, g_projw, g_projb, g_n2w, g_n2b) + gm + (None,) * 6
+        return (_ret_grad(dx.view(B, N, D), in_dtype), g_n1w, g_n1b, g_qkvw, g_qkvb, g_projw, g_projb, g_n2w, g_n2b) + gm + (None,) * 7
 
 
 class PatchEmbedFn(torch.autograd.Function):

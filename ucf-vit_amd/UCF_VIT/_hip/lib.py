@@ -5,7 +5,7 @@ missing or a call fails, a RuntimeError is raised with the library's own message
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint64, c_void_p
 
 F32, BF16 = 0, 1
 LAYOUT_KC, LAYOUT_KS = 0, 1
@@ -150,6 +150,8 @@ SIGNATURES = {
     "ucfvit_drop_path_colsum_rows": (_I64, [_I64, _I64, _I64]),
     "ucfvit_drop_path_add": (c_int, [_P, _I64, _P, _P, _P, _I64, _I64, _I64, _I, _P]),
     "ucfvit_drop_path_scale": (c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _I, _P]),
+    "ucfvit_dropout": (c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _D, c_uint64, _I, _P]),
+    "ucfvit_dropout_add": (c_int, [_P, _I64, _P, _P, _P, _I64, _I64, _I64, _I64, _D, c_uint64, _I, _P]),
 }
 
 _lib = None

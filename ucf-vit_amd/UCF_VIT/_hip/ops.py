@@ -1514,6 +1514,64 @@ def drop_path_scale(x, s, rows_per_sample, out=None, c_colsum=None, c_colsum_acc
     return out
 
 
+# ------------------------------------------------------------------------------------------------ element-wise dropout
+def _chk_dropout(s, rows, rows_per_sample, row_step, p, seed, name):
+    if s is not None:
+        _chk_drop_scale(s, rows, rows_per_sample, name)
+    elif rows_per_sample <= 0 or rows % rows_per_sample:
+        raise ValueError(f"{name}: {rows} rows are not a multiple of rows_per_sample={rows_per_sample}")
+    if not 0.0 < p < 1.0:
+        raise ValueError(f"{name}: the kernels take 0 < p < 1, got p={p} (p == 0 is the input itself, p == 1 is zeros: no launch needs a mask)")
+    if row_step < 1:
+        raise ValueError(f"{name}: row_step={row_step} < 1")
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"{name}: the seed must be an unsigned 64-bit integer, got {seed}")
+
+
+def dropout_add(res, branch, p, seed, s=None, rows_per_sample=1, row_step=1, out=None):
+    """out[r] = res[r] + s[r // rows_per_sample] * m * branch[r] / keep with the mask m of (seed, element index) that include/ucfvit_hip.h
+    defines (index (r * row_step) * D + c); s: optional fp32 drop-path scale per sample (None: 1).  res [rows, D] may have padded rows, out
+    may be branch (the default: the branch is overwritten).  A sample with s == 0 is copied from res without reading branch."""
+    L = _l.load()
+    _chk(res, "dropout_add.res", rows_ok=True), _chk(branch, "dropout_add.branch")
+    rows, D = branch.shape
+    out = branch if out is None else _chk(out, "dropout_add.out")
+    if tuple(res.shape) != (rows, D) or tuple(out.shape) != (rows, D) or res.dtype != branch.dtype or out.dtype != branch.dtype:
+        raise TypeError("dropout_add: res, branch and out must be [rows, D] of one dtype")
+    _chk_dropout(s, rows, rows_per_sample, row_step, p, seed, "dropout_add")
+    _l.check(L.ucfvit_dropout_add(res.data_ptr(), res.stride(0), branch.data_ptr(), _p(s), out.data_ptr(), rows, D, int(rows_per_sample),
+                                  int(row_step), float(p), int(seed), dt(branch), _stream()), "ucfvit_dropout_add")
+    return out
+
+
+def dropout(x, p, seed, s=None, rows_per_sample=1, row_step=1, out=None, c_colsum=None, c_colsum_accumulate=False):
+    """out[r] = s[r // rows_per_sample] * m * x[r] / keep for x [rows, D] (mask and s as in dropout_add; out may be x); c_colsum: optional
+    fp32 [D] that receives (+)= the column sums of the values written (taken in fp32 before rounding; partial sums per row chunk from the
+    kernel, sized by ucfvit_drop_path_colsum_rows, folded by ucfvit_reduce_rows)"""
+    L = _l.load()
+    _chk(x, "dropout.x")
+    rows, D = x.shape
+    out = torch.empty_like(x) if out is None else _chk(out, "dropout.out")
+    if tuple(out.shape) != (rows, D) or out.dtype != x.dtype:
+        raise TypeError("dropout: out must have x's shape and dtype")
+    _chk_dropout(s, rows, rows_per_sample, row_step, p, seed, "dropout")
+    cs_rows, part = 0, None
+    if c_colsum is not None:
+        _chk(c_colsum, "dropout.c_colsum")
+        if c_colsum.dtype != torch.float32 or c_colsum.numel() != D:
+            raise TypeError("dropout: c_colsum must be a contiguous fp32 tensor of D elements")
+        cs_rows = L.ucfvit_drop_path_colsum_rows(rows, int(rows_per_sample), D)
+        if cs_rows <= 0:
+            raise ValueError("dropout: no column sums of an empty input")
+        part = workspace(cs_rows * D * 4, x.device)
+    _l.check(L.ucfvit_dropout(x.data_ptr(), _p(s), out.data_ptr(), _p(part), rows, D, int(rows_per_sample), int(row_step), float(p), int(seed),
+                              dt(x), _stream()), "ucfvit_dropout")
+    if part is not None:
+        _l.check(L.ucfvit_reduce_rows(part.data_ptr(), c_colsum.data_ptr(), cs_rows, D, 1 if c_colsum_accumulate else 0, _stream()),
+                 "ucfvit_reduce_rows")
+    return out
+
+
 def transpose_batched(src_flat, dst_flat, table, n_mats, total_tiles):
     L = _l.load()
     _l.check(L.ucfvit_transpose_batched(src_flat.data_ptr(), dst_flat.data_ptr(), table.data_ptr(), n_mats, total_tiles, _stream()),

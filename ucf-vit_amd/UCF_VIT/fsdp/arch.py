@@ -129,6 +129,7 @@ class UNETR(_TPMixin, _S.UNETR):
     def _embed_local_tokens(self, x):
         """tokens [lo, hi) of the (h, w[, d]) row-major grid: whole slabs along the first spatial axis when the grid allows it (every rank
         then reads 1 / P of the volume), else the full embedding sliced"""
+        self._refuse_group_pos_drop()
         spg, p = self._spg, self.patch_size
         n = self.num_patches // spg.size
         lo = spg.rank * n

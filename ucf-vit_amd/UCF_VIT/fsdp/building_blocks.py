@@ -14,9 +14,9 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from UCF_VIT.simple.building_blocks import (  # noqa: F401  (re-exported operator set)
-    PatchEmbed, LayerNorm, Linear, DropPath, LayerScale, PatchDropout, MyUnetBlock, EmbeddingDenseLayer,
+    PatchEmbed, LayerNorm, Linear, DropPath, HipDropout, LayerScale, PatchDropout, MyUnetBlock, EmbeddingDenseLayer,
     VariableMapping_Attention, to_2tuple, to_3tuple, trunc_normal_, get_act_layer, get_norm_layer, LayerType,
-    set_compute_dtype, _cd, _no_dropout, _assert, _draw_drop_path)
+    set_compute_dtype, _cd, _no_dropout, _assert, _draw_drop_path, _draw_dropout, _block_dropout)
 from UCF_VIT.simple import building_blocks as _S
 from UCF_VIT.utils.fused_attn import FusedAttn
 from UCF_VIT._hip import functional as HF
@@ -24,6 +24,12 @@ from UCF_VIT._hip import functional as HF
 
 def _tp(size, group):
     return HF.TP(group, size) if size > 1 else None
+
+
+def _refuse_group_dropout(p, size, group, what):
+    if p > 0.0 and size > 1:
+        raise NotImplementedError(f"{what}={p} under a tensor-parallel group (tensor_par_group={group!r}, tensor_par_size={size}): every "
+                                  "rank of the group would need the same seed; not implemented")
 
 
 def _mark_sharded(module, size):
@@ -45,11 +51,13 @@ class Mlp(_S.Mlp):
         _mark_sharded(self, tensor_par_size)
 
     def forward(self, x):
-        _no_dropout(self.drop1.p, self.training, "Mlp.drop")
         if not self._fusable():
             raise NotImplementedError("HIP Mlp implements fc1 -> exact GELU -> fc2 (the reference configuration)")
-        return HF.MlpFn.apply(x, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, _cd(self),
-                              _tp(self.tensor_par_size, self.tensor_par_group))
+        args = (x, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, _cd(self), _tp(self.tensor_par_size, self.tensor_par_group))
+        d1, d2 = _draw_dropout(self.drop1), _draw_dropout(self.drop2)
+        if d1 is None and d2 is None:
+            return HF.MlpFn.apply(*args)
+        return HF.MlpFn.apply(*args, d1, d2)                       # refused under a tensor-parallel group (HF._site)
 
 
 class Attention(nn.Module):
@@ -66,9 +74,9 @@ class Attention(nn.Module):
         self.qkv = nn.Linear(dim, dim * 3 // tensor_par_size, bias=qkv_bias)
         self.q_norm = norm_layer(self.head_dim) if qk_norm else nn.Identity()
         self.k_norm = norm_layer(self.head_dim) if qk_norm else nn.Identity()
-        self.attn_drop = nn.Dropout(attn_drop)
+        self.attn_drop = HipDropout(attn_drop)
         self.proj = nn.Linear(dim // tensor_par_size, dim)
-        self.proj_drop = nn.Dropout(proj_drop)
+        self.proj_drop = HipDropout(proj_drop)
         _mark_sharded(self, tensor_par_size)
 
     def _fusable(self):
@@ -76,11 +84,12 @@ class Attention(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         _no_dropout(self.attn_drop.p, self.training, "attn_drop")
-        _no_dropout(self.proj_drop.p, self.training, "proj_drop")
         if not self._fusable():
             raise NotImplementedError("qk_norm=True is not on the HIP hot path; reference configs use qk_norm=False")
-        return HF.AttentionFn.apply(x, self.qkv.weight, self.qkv.bias, self.proj.weight, self.proj.bias, self.num_heads, _cd(self),
-                                    _tp(self.tensor_par_size, self.tensor_par_group))
+        args = (x, self.qkv.weight, self.qkv.bias, self.proj.weight, self.proj.bias, self.num_heads, _cd(self),
+                _tp(self.tensor_par_size, self.tensor_par_group))
+        d = _draw_dropout(self.proj_drop)
+        return HF.AttentionFn.apply(*args) if d is None else HF.AttentionFn.apply(*args, d)     # refused under a group (HF._site)
 
 
 class Block(nn.Module):
@@ -115,15 +124,16 @@ class Block(nn.Module):
         if self._fusable() and x.dim() == 3:
             a, m = self.attn, self.mlp
             _no_dropout(a.attn_drop.p, self.training, "attn_drop")
-            _no_dropout(a.proj_drop.p, self.training, "proj_drop")
-            _no_dropout(m.drop1.p, self.training, "Mlp.drop")
+            if self.training:
+                _refuse_group_dropout(a.proj_drop.p, self.tensor_par_size, self.tensor_par_group, "proj_drop")
             args = (x, self.norm1.weight, self.norm1.bias, a.qkv.weight, a.qkv.bias, a.proj.weight, a.proj.bias,
                     self.norm2.weight, self.norm2.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias,
                     a.num_heads, self.norm1.eps, _cd(self), _tp(self.tensor_par_size, self.tensor_par_group),
                     getattr(self, "activation_checkpointing", False) and torch.is_grad_enabled())
             s1, s2 = _draw_drop_path(self.drop_path1, x), _draw_drop_path(self.drop_path2, x)      # None under a tensor-parallel group
-            if s1 is None and s2 is None:
+            drop = _block_dropout(a, m)
+            if s1 is None and s2 is None and drop is None:
                 return HF.BlockFn.apply(*args)
-            return HF.BlockFn.apply(*args, s1, s2)
+            return HF.BlockFn.apply(*args, s1, s2, drop)
         x = x + self.drop_path1(self.ls1(self.attn(self.norm1(x))))
         return x + self.drop_path2(self.ls2(self.mlp(self.norm2(x))))

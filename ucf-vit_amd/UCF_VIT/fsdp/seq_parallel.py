@@ -300,6 +300,10 @@ class SeqParallelBlock(nn.Module):
     def forward(self, x):
         b = self.block
         a = b.attn
+        for what, d in (("proj_drop", a.proj_drop), ("Mlp.drop", getattr(b.mlp, "drop1", None)), ("Mlp.drop", getattr(b.mlp, "drop2", None))):
+            if b.training and getattr(d, "p", 0.0) > 0.0:
+                raise NotImplementedError(f"{what}={d.p} under a sequence-parallel group of {self.spg.size} ranks: every rank of the group "
+                                          "would need the same seed; not implemented")
         h = SeqParallelAttentionFn.apply(b.norm1(x), a.qkv.weight, a.qkv.bias, a.proj.weight, a.proj.bias, a.num_heads, _cd(b), self.spg)
         x = x + h if x.dtype == h.dtype else x.to(h.dtype) + h
         return x + b.mlp(b.norm2(x))

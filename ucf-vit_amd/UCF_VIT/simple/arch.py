@@ -21,7 +21,7 @@ import os
 import torch
 import torch.nn as nn
 
-from .building_blocks import (Block, PatchEmbed, Mlp, LayerNorm, Linear, DropPath, PatchDropout, trunc_normal_, get_act_layer,
+from .building_blocks import (Block, PatchEmbed, Mlp, LayerNorm, Linear, DropPath, HipDropout, PatchDropout, trunc_normal_, get_act_layer,
                               get_norm_layer, LayerType, MyUnetBlock, EmbeddingDenseLayer, VariableMapping_Attention,
                               set_compute_dtype, _cd)
 from UCF_VIT.utils.pos_embed import (get_1d_sincos_pos_embed_from_grid, get_2d_sincos_pos_embed, get_3d_sincos_pos_embed,
@@ -147,7 +147,7 @@ class VIT(nn.Module):
             self.pos_embed = None
         else:
             self.pos_embed = nn.Parameter(torch.randn(1, self.embed_len, embed_dim) * .02)
-        self.pos_drop = nn.Dropout(p=pos_drop_rate)
+        self.pos_drop = HipDropout(p=pos_drop_rate)
         self.patch_drop = PatchDropout(patch_drop_rate, num_prefix_tokens=self.num_prefix_tokens) if patch_drop_rate > 0 else nn.Identity()
 
         dpr = [x.item() for x in torch.linspace(0, drop_path_rate, depth)]
@@ -157,7 +157,7 @@ class VIT(nn.Module):
                      drop_path=dpr[i], norm_layer=norm_layer, act_layer=act_layer, mlp_layer=mlp_layer)
             for i in range(depth)])
         self.norm = norm_layer(embed_dim)
-        self.head_drop = nn.Dropout(drop_rate)
+        self.head_drop = HipDropout(drop_rate)
         if num_classes is not None:
             self.head = Linear(embed_dim, num_classes) if num_classes > 0 else nn.Identity()
         else:
@@ -278,16 +278,24 @@ class VIT(nn.Module):
     def _pos_embed(self, x: torch.Tensor, seq_ps) -> torch.Tensor:
         if self.pos_embed is None:
             return x.view(x.shape[0], -1, x.shape[-1])      # reference :367-368 returns before the class token is attached
-        if self.pos_drop.p > 0.0 and self.training:
-            raise NotImplementedError("pos_drop_rate > 0 is not on the HIP hot path")
+        self._refuse_group_pos_drop()
         if self.use_adaptive_pos_emb:
             if seq_ps is None:
                 raise ValueError("use_adaptive_pos_emb needs seq_ps [B, S, 3|4] (position and size of every token)")
             lin = self.adaptive_pos_dep_emb[0]
-            return HF.AdaptivePosFn.apply(x, seq_ps, lin.weight, lin.bias, self.cls_token, _cd(self))
-        if self.pos_drop.p > 0.0 and self.training:
-            raise NotImplementedError("pos_drop_rate > 0 is not on the HIP hot path")
-        return HF.TokensFn.apply(x, self.cls_token, self.pos_embed, _cd(self))
+            return self.pos_drop(HF.AdaptivePosFn.apply(x, seq_ps, lin.weight, lin.bias, self.cls_token, _cd(self)))
+        return self.pos_drop(HF.TokensFn.apply(x, self.cls_token, self.pos_embed, _cd(self)))
+
+    def _refuse_group_pos_drop(self):
+        """an active pos_drop under a tensor- or sequence-parallel group: the ranks of the group hold one sample's tokens between them"""
+        if not self.pos_drop.active():
+            return
+        for kind in ("tensor", "seq"):
+            size = getattr(self, kind + "_par_size", 1)
+            if size > 1:
+                group = getattr(self, "tensor_par_group", None) if kind == "tensor" else getattr(self, "_spg", None)
+                raise NotImplementedError(f"pos_drop_rate={self.pos_drop.p} under a {'tensor' if kind == 'tensor' else 'sequence'}-parallel group "
+                                          f"({group!r}, {size} ranks): every rank of the group would need the same seed; not implemented")
 
     # ------------------------------------------------------------------ forward
     def forward_features(self, x: torch.Tensor, variables, seq_ps) -> torch.Tensor:
@@ -302,10 +310,7 @@ class VIT(nn.Module):
         return global_pool_nlc(x, num_prefix_tokens=self.num_prefix_tokens)
 
     def forward_head(self, x: torch.Tensor) -> torch.Tensor:
-        x = self.pool(x)
-        if self.head_drop.p > 0.0 and self.training:
-            raise NotImplementedError("drop_rate > 0 is not on the HIP hot path")
-        return self.head(x)
+        return self.head(self.head_drop(self.pool(x)))
 
     def tail_rows_applies(self) -> bool:
         """forward() may run the last Block for the class-token rows only (HF.TailBlockFn): pooling takes token 0 of every sequence
@@ -331,9 +336,7 @@ class VIT(nn.Module):
             x = self.norm(self.blocks[-1].forward_class_rows(x))            # [B, D]: the rows pool() would take
         else:
             x = self.pool(self.norm(self.blocks[-1](x)))
-        if self.head_drop.p > 0.0 and self.training:
-            raise NotImplementedError("drop_rate > 0 is not on the HIP hot path")
-        return self.head(x)
+        return self.head(self.head_drop(x))
 
 
 class SAP(VIT):

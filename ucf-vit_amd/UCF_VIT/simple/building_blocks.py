@@ -65,8 +65,9 @@ def _cd(m):
 
 
 def _no_dropout(p, training, what):
+    """attn_drop (inside the LDS-resident attention kernels) and patch_drop_rate (changes the token count) are not on the HIP hot path"""
     if p > 0.0 and training:
-        raise NotImplementedError(f"{what}={p}: the HIP hot path implements the reference configs (all drop rates 0.0)")
+        raise NotImplementedError(f"{what}={p}: not on the HIP hot path (head, position and projection / MLP dropout are)")
 
 
 class LayerNorm(nn.LayerNorm):
@@ -124,6 +125,51 @@ class DropPath(nn.Module):
 def _draw_drop_path(d, x):
     """the scale tensor of one residual branch of a fused Block, or None when the branch has no drop path to apply"""
     return d.draw(x.shape[0], x.device) if isinstance(d, DropPath) and d.active() else None
+
+
+class HipDropout(nn.Dropout):
+    """nn.Dropout(p) whose training arithmetic is HIP (csrc/dropout.hip): no parameters, the same state_dict.  The mask is a function of
+    (seed, element index) defined in include/ucfvit_hip.h and never stored; the module only draws one 64-bit seed per forward pass, on the
+    host: a Python int from a CPU generator (self.generator, else torch's default one, so it follows torch.manual_seed), no device work
+    and no synchronisation.  Inside a fused Block / Attention / Mlp the module only draws: the autograd Functions take (p, seed)."""
+
+    def __init__(self, p: float = 0.0, inplace: bool = False):
+        super().__init__(p, False)       # the kernels decide where they write; `inplace` is accepted for the signature only
+        self.last_seed = None            # the seed of the latest draw: for tests and inspection
+        self.generator = None            # None: torch's default CPU generator; the training scripts set one per rank and module
+
+    def active(self):
+        return self.training and self.p > 0.0
+
+    def draw(self):
+        """a fresh seed in [0, 2^64): two 32-bit halves, since torch draws int64 below 2^63"""
+        hi, lo = torch.randint(0, 1 << 32, (2,), dtype=torch.int64, generator=self.generator).tolist()
+        self.last_seed = (hi << 32) | lo
+        return self.last_seed
+
+    def forward(self, x):
+        if not self.active():
+            return x
+        if not x.is_cuda:
+            raise RuntimeError(f"HipDropout: expected a tensor on the MI355X (cuda) device, got {x.device}. "
+                               "UCF_VIT operators run only through libucfvit_hip.so; there is no CPU path.")
+        return HF.DropoutFn.apply(x, self.p, self.draw())
+
+
+def _draw_dropout(d):
+    """(p, seed) of one dropout site for the autograd Functions, or None when the site has nothing to apply"""
+    return (d.p, d.draw()) if isinstance(d, HipDropout) and d.active() else None
+
+
+def _block_dropout(attn, mlp):
+    """BlockFn's dropout argument (p, seed_proj, seed_drop1, seed_drop2) from the three modules a Block builds with one rate, or None.
+    Three draws, proj first."""
+    sites = [_draw_dropout(attn.proj_drop), _draw_dropout(mlp.drop1), _draw_dropout(mlp.drop2)]
+    if all(s is None for s in sites):
+        return None
+    if any(s is None for s in sites) or len({s[0] for s in sites}) != 1:
+        raise NotImplementedError("the fused Block takes one rate for proj_drop, Mlp.drop1 and Mlp.drop2 (Block(proj_drop=p) builds them so)")
+    return (sites[0][0],) + tuple(s[1] for s in sites)
 
 
 class LayerScale(nn.Module):
@@ -198,21 +244,23 @@ class Mlp(nn.Module):
             raise NotImplementedError("Mlp(use_conv=True) is not used by the reference models")
         self.fc1 = nn.Linear(in_features, hidden_features, bias=bias[0])
         self.act = act_layer()
-        self.drop1 = nn.Dropout(drop_probs[0])
+        self.drop1 = HipDropout(drop_probs[0])
         self.norm = norm_layer(hidden_features) if norm_layer is not None else nn.Identity()
         self.fc2 = nn.Linear(hidden_features, out_features, bias=bias[1])
-        self.drop2 = nn.Dropout(drop_probs[1])
+        self.drop2 = HipDropout(drop_probs[1])
 
     def _fusable(self):
         return (isinstance(self.act, nn.GELU) and getattr(self.act, "approximate", "none") == "none"
                 and isinstance(self.norm, nn.Identity))
 
     def forward(self, x):
-        _no_dropout(self.drop1.p, self.training, "Mlp.drop")
-        _no_dropout(self.drop2.p, self.training, "Mlp.drop")
         if not self._fusable():
             raise NotImplementedError("HIP Mlp implements fc1 -> exact GELU -> fc2 (the reference configuration)")
-        return HF.MlpFn.apply(x, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, _cd(self))
+        args = (x, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, _cd(self))
+        d1, d2 = _draw_dropout(self.drop1), _draw_dropout(self.drop2)           # two seeds, drop1 first
+        if d1 is None and d2 is None:
+            return HF.MlpFn.apply(*args)
+        return HF.MlpFn.apply(*args, None, d1, d2)
 
 
 class Attention(nn.Module):
@@ -229,26 +277,28 @@ class Attention(nn.Module):
         self.qkv = nn.Linear(dim, dim * 3, bias=qkv_bias)
         self.q_norm = norm_layer(self.head_dim) if qk_norm else nn.Identity()
         self.k_norm = norm_layer(self.head_dim) if qk_norm else nn.Identity()
-        self.attn_drop = nn.Dropout(attn_drop)
+        self.attn_drop = HipDropout(attn_drop)      # still refused when active: it lives inside the LDS-resident attention kernels
         self.proj = nn.Linear(dim, dim)
-        self.proj_drop = nn.Dropout(proj_drop)
+        self.proj_drop = HipDropout(proj_drop)
 
     def _fusable(self):
         return isinstance(self.q_norm, nn.Identity) and isinstance(self.k_norm, nn.Identity)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         _no_dropout(self.attn_drop.p, self.training, "attn_drop")
-        _no_dropout(self.proj_drop.p, self.training, "proj_drop")
         if not self._fusable():
             raise NotImplementedError("qk_norm=True is not on the HIP hot path; reference configs use qk_norm=False")
-        return HF.AttentionFn.apply(x, self.qkv.weight, self.qkv.bias, self.proj.weight, self.proj.bias, self.num_heads, _cd(self))
+        args = (x, self.qkv.weight, self.qkv.bias, self.proj.weight, self.proj.bias, self.num_heads, _cd(self))
+        d = _draw_dropout(self.proj_drop)
+        return HF.AttentionFn.apply(*args) if d is None else HF.AttentionFn.apply(*args, None, d)
 
 
 class Block(nn.Module):
     """Pre-LN transformer block.  With the reference configuration (no LayerScale, standard Attention/Mlp) the whole block is ONE
     autograd node running a fixed sequence of fused HIP launches (HF.BlockFn).  drop_path > 0 in training: the two DropPath modules
-    draw their per-sample scales and the node applies them (one row pass per branch and direction); eval or rate 0 runs the very
-    launches of a Block without drop path."""
+    draw their per-sample scales and the node applies them (one row pass per branch and direction); proj_drop > 0 in training: the
+    three HipDropout modules draw their seeds and the same row passes apply the masks (plus one pass over the activation).  Eval or
+    rates 0 run the very launches of a Block without either."""
 
     def __init__(self, dim: int, num_heads: int, fused_attn: FusedAttn = FusedAttn.NONE, mlp_ratio: float = 4.0,
                  qkv_bias: bool = False, qk_norm: bool = False, proj_drop: float = 0.0, attn_drop: float = 0.0,
@@ -278,15 +328,14 @@ class Block(nn.Module):
         if self._fusable() and x.dim() == 3:
             a, m = self.attn, self.mlp
             _no_dropout(a.attn_drop.p, self.training, "attn_drop")
-            _no_dropout(a.proj_drop.p, self.training, "proj_drop")
-            _no_dropout(m.drop1.p, self.training, "Mlp.drop")
             args = (x, self.norm1.weight, self.norm1.bias, a.qkv.weight, a.qkv.bias, a.proj.weight, a.proj.bias,
                     self.norm2.weight, self.norm2.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias,
                     a.num_heads, self.norm1.eps, _cd(self), None, self.activation_checkpointing and torch.is_grad_enabled())
             s1, s2 = _draw_drop_path(self.drop_path1, x), _draw_drop_path(self.drop_path2, x)      # two independent draws, s1 first
-            if s1 is None and s2 is None:
+            drop = _block_dropout(a, m)
+            if s1 is None and s2 is None and drop is None:
                 return HF.BlockFn.apply(*args)
-            return HF.BlockFn.apply(*args, s1, s2)
+            return HF.BlockFn.apply(*args, s1, s2, drop)
         x = x + self.drop_path1(self.ls1(self.attn(self.norm1(x))))
         x = x + self.drop_path2(self.ls2(self.mlp(self.norm2(x))))
         return x
@@ -295,15 +344,14 @@ class Block(nn.Module):
         """forward(x)[:, 0] computed without the other rows (HF.TailBlockFn); the caller checked _fusable()"""
         a, m = self.attn, self.mlp
         _no_dropout(a.attn_drop.p, self.training, "attn_drop")
-        _no_dropout(a.proj_drop.p, self.training, "proj_drop")
-        _no_dropout(m.drop1.p, self.training, "Mlp.drop")
         args = (x, self.norm1.weight, self.norm1.bias, a.qkv.weight, a.qkv.bias, a.proj.weight, a.proj.bias,
                 self.norm2.weight, self.norm2.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias,
                 a.num_heads, self.norm1.eps, _cd(self), self.activation_checkpointing and torch.is_grad_enabled())
         s1, s2 = _draw_drop_path(self.drop_path1, x), _draw_drop_path(self.drop_path2, x)
-        if s1 is None and s2 is None:
+        drop = _block_dropout(a, m)
+        if s1 is None and s2 is None and drop is None:
             return HF.TailBlockFn.apply(*args)
-        return HF.TailBlockFn.apply(*args, s1, s2)
+        return HF.TailBlockFn.apply(*args, s1, s2, drop)
 
 
 class MyUnetBlock(nn.Module):

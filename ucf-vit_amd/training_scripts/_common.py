@@ -45,7 +45,8 @@ def model_args(conf):
     chans = 1 if d.get("single_channel", False) else max(1, d["num_channels_used"][dataset])
     adaptive = bool(a.get("adaptive_patching", False))
     return dict(img_size=a["tile_size"], patch_size=a["patch_size"], in_chans=chans, embed_dim=a["embed_dim"], depth=a["depth"],
-                num_heads=a["num_heads"], mlp_ratio=a["mlp_ratio"], drop_path_rate=a.get("drop_path", 0.0), twoD=a["twoD"],
+                num_heads=a["num_heads"], mlp_ratio=a["mlp_ratio"], drop_path_rate=a.get("drop_path", 0.0), pos_drop_rate=a.get("pos_drop_rate", 0.0),
+                proj_drop_rate=a.get("proj_drop_rate", 0.0), twoD=a["twoD"],
                 default_vars=a["default_vars"], single_channel=d.get("single_channel", False), use_varemb=bool(a.get("use_varemb", False)),
                 adaptive_patching=adaptive, fixed_length=a.get("fixed_length", 4096),
                 use_adaptive_pos_emb=bool(a.get("use_adaptive_pos_emb", False)) and adaptive), a, d
@@ -62,6 +63,19 @@ def seed_drop_path(model, device, rank):
         g.manual_seed(torch.initial_seed() + rank)
         for m in mods:
             m.generator = g
+    return len(mods)
+
+
+def seed_dropout(model, device, rank):
+    """Element-wise dropout (HipDropout) draws one seed per forward pass from a CPU generator.  As for stochastic depth, data-parallel
+    ranks must not share masks, and neither should two modules: every module with a non-zero rate gets its own CPU generator, seeded
+    from torch.initial_seed(), the rank and the module's position in the model; every other random stream stays as it was (`device` is
+    taken for symmetry with seed_drop_path: the draw is host work).  Returns the number of modules."""
+    from UCF_VIT.simple.building_blocks import HipDropout
+    mods = [m for m in model.modules() if isinstance(m, HipDropout) and m.p > 0.0]
+    for k, m in enumerate(mods):
+        m.generator = torch.Generator()
+        m.generator.manual_seed((torch.initial_seed() + 0x9E3779B97F4A7C15 * (rank * len(mods) + k + 1)) % (1 << 63))
     return len(mods)
 
 

@@ -16,7 +16,7 @@ import torch
 import torch.nn.functional as F
 
 from _common import (SyntheticLoader, SyntheticSeqLoader, StepTimer, init_distributed, iters_per_epoch, load_config, maybe_resume, model_args,
-                     save_checkpoint, seed_drop_path, seq_to_pseudo_image, sqrt_len_of)
+                     save_checkpoint, seed_drop_path, seed_dropout, seq_to_pseudo_image, sqrt_len_of)
 from UCF_VIT.simple.arch import UNETR
 from UCF_VIT.utils.fused_attn import FusedAttn
 from UCF_VIT.utils.metrics import DiceMetric
@@ -59,6 +59,7 @@ def main(device, local_rank, rank, world):
                   sqrt_len_method=adaptive, FusedAttn_option=FusedAttn.HIP, **margs).to(device)
     model.set_compute_dtype(torch.bfloat16 if conf["trainer"].get("data_type", "float32") == "bfloat16" else torch.float32)
     seed_drop_path(model, device, rank)                                      # stochastic depth: ranks must not share a draw
+    seed_dropout(model, device, rank)                                        # dropout: neither ranks nor modules share a seed
     net = HipDataParallel(model)
     optimizer = configure_optimizer(model, float(m["lr"]), float(m["beta_1"]), float(m["beta_2"]), float(m["weight_decay"]))   # PyYAML reads "1e-5" as str
     scheduler = configure_scheduler(optimizer, int(m["warmup_steps"]), int(m["max_steps"]), float(m["warmup_start_lr"]), float(m["eta_min"]))
