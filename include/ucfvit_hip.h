@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define UCFVIT_ABI_VERSION 24 /* still 24 with the dropout entry points (ucfvit_dropout, ucfvit_dropout_add): symbols were only added */
+#define UCFVIT_ABI_VERSION 24 /* still 24 with the dropout and LayerScale entry points (ucfvit_dropout*, ucfvit_layer_scale_*): symbols were only added */
 
 #define UCFVIT_OK 0
 #define UCFVIT_ERR_INVALID_ARGUMENT (-1)
@@ -733,6 +733,37 @@ int ucfvit_dropout(const void* x, const float* s, void* out, float* colsum_parti
                    int64_t row_step, double p, uint64_t seed, int dtype, void* stream);
 int ucfvit_dropout_add(const void* res, int64_t ldr, const void* branch, const float* s, void* out, int64_t rows, int64_t D,
                        int64_t rows_per_sample, int64_t row_step, double p, uint64_t seed, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * LayerScale (csrc/layer_scale.hip): timm's LayerScale(dim, init_values), the ls1 / ls2 of the reference's Block: a learned factor
+ * gamma[c] per column on a residual branch.  gamma is always fp32 [D] (the master parameter, read directly).  The drop-path scale s (may
+ * be NULL) and the dropout mask (p, seed, row_step) of the two sections above ride along, so that a branch with all three costs one row
+ * pass per direction.  Here p == 0 is allowed and means "no mask": such a call runs a kernel without any Philox code.  0 < p < 1 uses
+ * the mask definition above unchanged (index (r * row_step) * D + c, threshold T, factor 1.0f / (1.0f - (float)p)).  The row factor is
+ * f_r = s[r / rows_per_sample] * (1 / keep) in fp32, a missing factor being 1; with neither s nor a mask no product by f_r is made.
+ * fp32 arithmetic, one rounding to the output type; 16-byte accesses under the rule of the drop-path section (all of D, ldr and the
+ * pointers of the token matrices), else the element path, with the same mask; no atomics, the same bits on every call.
+ *
+ * ucfvit_layer_scale_add: out[r][c] = res[r ldr + c] + f_r * m(r, c) * (gamma[c] * branch[r][c]), evaluated as u = fl(gamma * b),
+ *   t = fl(f_r * u), then the add (which the compiler may contract with the product before it).  res == NULL gives
+ *   out = f_r * m * gamma * branch, the LayerScale module applied on its own; ldr is then ignored.  res has the row stride ldr >= D, out
+ *   may be branch itself.  A row with f_r == 0 copies res bit for bit (zeros without res) and does not read branch; a masked element is a
+ *   select, so NaN / Inf under the mask or in a dropped sample do not pass.  Under a masked element of a kept row the result is
+ *   res + (+0): the residual's value, a residual of -0 coming out as +0; only whole rows with f_r == 0 are copied bit for bit.
+ * ucfvit_layer_scale_grad: with g = f_r * m(r, c) * dy[r][c] in fp32, dbranch[r][c] = round(gamma[c] * g); dbranch may be dy itself.
+ *   colsum_partial (may be NULL) receives per row chunk the column sums of gamma[c] * g before rounding: folded, the bias gradient of the
+ *   branch's exit Linear.  gamma_partial (may be NULL) receives per row chunk the column sums of g * branch[r][c]: folded, the gradient of
+ *   gamma.  branch (the branch's unscaled output) may be NULL only when gamma_partial is.  Both partials are fp32 [R][D],
+ *   R = ucfvit_drop_path_colsum_rows(rows, rows_per_sample, D), in the fixed summation order of ucfvit_drop_path_scale, folded by
+ *   ucfvit_reduce_rows.  A row with f_r == 0 writes zeros, reads neither dy nor branch and adds exact zeros to both sums.
+ * Arguments (null pointers, null gamma, branch == NULL with gamma_partial, D, rows, rows % rows_per_sample, ldr < D, p outside [0, 1),
+ * row_step < 1, dtype, sums of an empty input) are checked before any HIP call.
+ * ------------------------------------------------------------------------------------------------------ */
+int ucfvit_layer_scale_add(const void* res, int64_t ldr, const void* branch, const float* gamma, const float* s, void* out, int64_t rows,
+                           int64_t D, int64_t rows_per_sample, int64_t row_step, double p, uint64_t seed, int dtype, void* stream);
+int ucfvit_layer_scale_grad(const void* dy, const void* branch, const float* gamma, const float* s, void* dbranch, float* colsum_partial,
+                            float* gamma_partial, int64_t rows, int64_t D, int64_t rows_per_sample, int64_t row_step, double p, uint64_t seed,
+                            int dtype, void* stream);
 
 #ifdef __cplusplus
 }

@@ -567,6 +567,62 @@ def _branch_grad(dy2, s, rows_per_sample, site, want_sums):
     return _dropout(dy2, site, s, rows_per_sample, c_colsum=cs), cs
 
 
+# LayerScale inside the fused Blocks.  A branch with a gamma (the fp32 master parameter of ls1 / ls2) is never "plain": its exit GEMM runs
+# without the residual and ops.layer_scale_add writes res + s ⊙ m ⊙ (gamma ⊙ branch) / keep, the drop-path scale and the dropout site riding
+# along.  Backward needs the UNSCALED branch output (gamma's gradient is the column sums of g ⊙ branch), so with keep the sum goes to a new
+# buffer and the branch output is saved; without (no_grad, nothing that requires a gradient, the first pass of a checkpointed Block) it
+# overwrites the branch.
+def _ls_branch_exit(res, y, gamma, s, rows_per_sample, site, keep):
+    """-> res + s ⊙ m ⊙ (gamma ⊙ y) / keep: in a new buffer when keep (y stays the branch output), else over y"""
+    out = torch.empty_like(y) if keep else y
+    p, seed, row_step = site if site is not None else (0.0, 0, 1)
+    if p >= 1.0:
+        return out.copy_(res)
+    return ops.layer_scale_add(res, y, gamma, s=s, rows_per_sample=rows_per_sample, p=p, seed=seed, row_step=row_step, out=out)
+
+
+def _ls_branch_grad(dy2, branch, gamma, s, rows_per_sample, site, want_sums, want_gamma):
+    """-> (gamma ⊙ g, its fp32 [D] column sums or None, the fp32 [D] column sums of g ⊙ branch or None) with g = s ⊙ m ⊙ dy2 / keep: the
+    gradient of the branch's exit GEMM output, that GEMM's bias gradient, and gamma's gradient"""
+    D, dev = dy2.shape[1], dy2.device
+    cs = torch.empty(D, dtype=torch.float32, device=dev) if want_sums else None
+    gs = torch.empty(D, dtype=torch.float32, device=dev) if want_gamma else None
+    p, seed, row_step = site if site is not None else (0.0, 0, 1)
+    if p >= 1.0:
+        for t in (cs, gs):
+            if t is not None:
+                t.zero_()
+        return torch.zeros_like(dy2), cs, gs
+    d = ops.layer_scale_grad(dy2, branch if want_gamma else None, gamma, s=s, rows_per_sample=rows_per_sample, p=p, seed=seed,
+                             row_step=row_step, c_colsum=cs, c_gamma=gs)
+    return d, cs, gs
+
+
+def _refuse_group_layer_scale(tp, g1, g2):
+    if tp is not None and (g1 is not None or g2 is not None):
+        raise NotImplementedError(f"LayerScale under a tensor-parallel group (tp group {tp.group!r}, size {tp.size}): the row-parallel exit "
+                                  "GEMM's partial outputs would have to be summed before gamma is applied; not implemented")
+
+
+class LayerScaleFn(torch.autograd.Function):
+    """LayerScale applied on its own: y = gamma ⊙ x over the last dimension (gamma: the fp32 parameter); backward is one layer_scale_grad."""
+
+    @staticmethod
+    def forward(ctx, x, gamma):
+        xc = x if x.is_contiguous() else x.contiguous()
+        x2 = xc.view(-1, xc.shape[-1])
+        ctx.save_for_backward(x2, gamma)
+        return ops.layer_scale_add(None, x2, gamma, out=torch.empty_like(x2)).view(x.shape)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2, gamma = ctx.saved_tensors
+        dc = dy if dy.is_contiguous() else dy.contiguous()
+        want_gamma = ctx.needs_input_grad[1]
+        dx, _, gs = _ls_branch_grad(dc.view(x2.shape), x2, gamma, None, 1, None, False, want_gamma)
+        return dx.view(dy.shape), (_bgrad_from(gamma, gs) if want_gamma else None)
+
+
 def _block_sites(drop, tp, row_step):
     """BlockFn's dropout argument (p, seed_proj, seed_drop1, seed_drop2) -> the three sites (proj, drop1, drop2)"""
     if drop is None or drop[0] <= 0.0:
@@ -607,30 +663,45 @@ def _refuse_group_drop_path(tp, s1, s2):
 
 
 class BlockFn(torch.autograd.Function):
-    """Block.forward (building_blocks.py:236-239) with LayerScale = Identity:
-    x1 = x + s1 ⊙ proj(attn(norm1(x))) ; y = x1 + s2 ⊙ fc2(gelu(fc1(norm2(x1)))).  Without drop path (s1 = s2 = None): 7 forward
+    """Block.forward (building_blocks.py:236-239):
+    x1 = x + s1 ⊙ γ1 ⊙ proj(attn(norm1(x))) ; y = x1 + s2 ⊙ γ2 ⊙ fc2(gelu(fc1(norm2(x1)))) (γ: LayerScale, absent = Identity).  Without drop path (s1 = s2 = None): 7 forward
     launches, residual adds and the activation fused into GEMM epilogues; the residual-branch gradients are fused into the LayerNorm
     backward.  With a scale a branch costs one row pass more forward (drop_path_add) and one backward (drop_path_scale)."""
 
     @staticmethod
-    def _run_forward(x2, B, N, num_heads, eps, c, params, tp, s1=None, s2=None, sites=(None, None, None)):
+    def _run_forward(x2, B, N, num_heads, eps, c, params, tp, s1=None, s2=None, sites=(None, None, None), g1=None, g2=None, keep=False):
+        """g1, g2: the LayerScale gammas of the two branches or None; keep: their unscaled branch outputs b1, b2 are kept for backward"""
         n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b = params
         dproj, d1, d2 = sites
-        plain1, plain2 = s1 is None and dproj is None, s2 is None and d2 is None
+        plain1, plain2 = s1 is None and dproj is None and g1 is None, s2 is None and d2 is None and g2 is None
+        b1 = b2 = None
         ln1, mean1, rstd1 = ops.layernorm_fwd(x2, c(n1w), c(n1b), eps)
         x1, sa = _attn_fwd(ln1, B, N, num_heads, c(qkvw), c(qkvb), c(projw), c(projb), x2 if plain1 else None, tp)
-        if not plain1:
+        if g1 is not None:
+            b1 = x1 if keep else None
+            x1 = _ls_branch_exit(x2, x1, g1, s1, N, dproj, keep)            # x1 = x + s1 ⊙ m ⊙ (gamma1 ⊙ branch) / keep
+        elif not plain1:
             _branch_exit(x2, x1, s1, N, dproj)                              # x1 = x + s1 ⊙ m ⊙ branch / keep, over the branch
         ln2, mean2, rstd2 = ops.layernorm_fwd(x1, c(n2w), c(n2b), eps)
         y, sm = _mlp_fwd(ln2, c(f1w), c(f1b), c(f2w), c(f2b), x1 if plain2 else None, tp, drop1=d1)
-        if not plain2:
+        if g2 is not None:
+            b2 = y if keep else None
+            y = _ls_branch_exit(x1, y, g2, s2, N, d2, keep)
+        elif not plain2:
             _branch_exit(x1, y, s2, N, d2)
-        return y, (mean1, rstd1, ln1, *sa, x1, mean2, rstd2, ln2, *sm)
+        return y, (mean1, rstd1, ln1, *sa, x1, mean2, rstd2, ln2, *sm, b1, b2)
 
     @staticmethod
     def forward(ctx, x, n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b, num_heads, eps, cdtype, tp=None, recompute=False,
-                s1=None, s2=None, drop=None):
+                s1=None, s2=None, drop=None, gamma1=None, gamma2=None, save_branch=None):
         """s1, s2: the per-sample drop-path scales of the attention and the MLP branch (fp32 [B]); None = no drop path on that branch.
+        gamma1, gamma2: the LayerScale parameters of the two branches (fp32 [D], ls1.gamma / ls2.gamma) or None.  A branch with a gamma runs
+        its exit GEMM without the residual and ops.layer_scale_add writes res + s ⊙ m ⊙ (gamma ⊙ branch) / keep; when a gradient is wanted
+        the sum goes to a new buffer and the unscaled branch output is saved (two more token matrices per Block), else it overwrites the
+        branch.  Under recompute only the input is kept, as without LayerScale.
+        save_branch: whether a backward pass can follow.  Grad mode is always off in here, and needs_input_grad only says which inputs
+        require a gradient, so the caller passes torch.is_grad_enabled() (as the modules do); None: decided from needs_input_grad alone,
+        which keeps the branch outputs under no_grad too (the same bits, two token matrices more).
         drop: (p, seed_proj, seed_drop1, seed_drop2) = the rate of proj_drop / Mlp.drop and this pass's seeds of the three sites, or None.
         A branch with dropout runs its exit GEMM without the residual and ops.dropout_add writes res + s ⊙ m ⊙ branch / keep over it (the
         drop-path scale rides along); drop1 masks the activation in place before fc2.  The seeds are host integers kept on ctx, so the
@@ -641,17 +712,19 @@ class BlockFn(torch.autograd.Function):
         rebuilt tensors are bit-identical (no atomics, fixed reduction orders), so gradients equal the non-checkpointed ones exactly;
         the scales are kept with the input, so the rebuilt forward uses the same draw."""
         _refuse_group_drop_path(tp, s1, s2)
+        _refuse_group_layer_scale(tp, gamma1, gamma2)
         ctx.sites = sites = _block_sites(drop, tp, 1)
         xin = _as(x, cdtype)
         B, N, D = xin.shape
         x2 = xin.view(B * N, D)
         c = lambda p: compute_param(p, cdtype)
         params = (n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b)
-        y, saved = BlockFn._run_forward(x2, B, N, num_heads, eps, c, params, tp, s1, s2, sites)
+        keep = not recompute and any(ctx.needs_input_grad) and (save_branch is None or bool(save_branch))
+        y, saved = BlockFn._run_forward(x2, B, N, num_heads, eps, c, params, tp, s1, s2, sites, gamma1, gamma2, keep)
         if recompute:
-            ctx.save_for_backward(x2, *params, s1, s2)
+            ctx.save_for_backward(x2, *params, s1, s2, gamma1, gamma2)
         else:
-            ctx.save_for_backward(x2, *saved, *params, s1, s2)
+            ctx.save_for_backward(x2, *saved, *params, s1, s2, gamma1, gamma2)
         ctx.meta = (B, N, num_heads, cdtype, x.dtype, tp)
         ctx.recompute, ctx.eps = recompute, eps
         return y.view(B, N, D)
@@ -661,26 +734,31 @@ class BlockFn(torch.autograd.Function):
         B, N, H, cdtype, in_dtype, tp = ctx.meta
         c = lambda p: compute_param(p, cdtype)
         if ctx.recompute:
-            x2, *params, s1, s2 = ctx.saved_tensors
-            _, saved = BlockFn._run_forward(x2, B, N, H, ctx.eps, c, tuple(params), tp, s1, s2, ctx.sites)
-            (mean1, rstd1, ln1, qkv, o, lse, x1, mean2, rstd2, ln2, h, a) = saved
+            x2, *params, s1, s2, g1, g2 = ctx.saved_tensors
+            _, saved = BlockFn._run_forward(x2, B, N, H, ctx.eps, c, tuple(params), tp, s1, s2, ctx.sites, g1, g2, True)
+            (mean1, rstd1, ln1, qkv, o, lse, x1, mean2, rstd2, ln2, h, a, b1, b2) = saved
             n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b = params
         else:
-            (x2, mean1, rstd1, ln1, qkv, o, lse, x1, mean2, rstd2, ln2, h, a,
-             n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b, s1, s2) = ctx.saved_tensors
+            (x2, mean1, rstd1, ln1, qkv, o, lse, x1, mean2, rstd2, ln2, h, a, b1, b2,
+             n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b, s1, s2, g1, g2) = ctx.saved_tensors
         need = ctx.needs_input_grad
         dproj, d1, d2 = ctx.sites
         dy2 = _as(dy, cdtype).reshape(x2.shape)
         wq = _queue_for(qkvw)
+        g_g1 = g_g2 = None
         dt2, cs2 = dy2, _take_stream_colsum(wq, dy2)       # always taken: the slot is cleared
-        if s2 is not None or d2 is not None:
+        if g2 is not None:
+            # as below, and the sums are those of gamma2 ⊙ g; gamma2's own gradient comes out of the same pass
+            dt2, cs2, gs2 = _ls_branch_grad(dy2, b2, g2, s2, N, d2, f2b is not None and need[12], need[22])
+            g_g2 = _bgrad_from(g2, gs2) if gs2 is not None else None
+        elif s2 is not None or d2 is not None:
             # the published sums are those of the unscaled, unmasked dy: not this fc2's bias gradient; the sums of s2 ⊙ m ⊙ dy / keep are
             dt2, cs2 = _branch_grad(dy2, s2, N, d2, f2b is not None and need[12])
         dln2, gm = _mlp_bwd(dt2, ln2, (h, a), c(f1w), c(f2w), f1w, f1b, f2w, f2b, need[9:13], tp, wq, dy2_colsum=cs2, drop1=d1)
         # LayerNorm backward also sums its output (the residual-stream gradient) over the tokens: proj's bias gradient here ...
         projb_done = None
         pb_out, pb_acc = None, False
-        if s1 is None and dproj is None and _BIAS_FROM_EPILOGUE and projb is not None and need[6]:
+        if s1 is None and dproj is None and g1 is None and _BIAS_FROM_EPILOGUE and projb is not None and need[6]:
             pb_out, pb_acc = grad_target(projb)
             if pb_out is None:
                 pb_out = torch.empty(projb.shape, dtype=torch.float32, device=dy2.device)
@@ -688,7 +766,11 @@ class BlockFn(torch.autograd.Function):
         dx1, g_n2w, g_n2b = _ln_bwd(dln2, x1, c(n2w), mean2, rstd2, n2w, n2b, dres=dy2, dx_colsum=pb_out,       # + residual branch
                                     dx_colsum_accumulate=pb_acc)
         dt1 = dx1
-        if s1 is not None or dproj is not None:
+        if g1 is not None:
+            dt1, cs1, gs1 = _ls_branch_grad(dx1, b1, g1, s1, N, dproj, projb is not None and need[6], need[21])
+            projb_done = (_bgrad_from(projb, cs1) if cs1 is not None else None,)
+            g_g1 = _bgrad_from(g1, gs1) if gs1 is not None else None
+        elif s1 is not None or dproj is not None:
             # ... unless the branch is scaled or masked: then the sums of s1 ⊙ m ⊙ dx1 / keep are, and the LayerNorm backward above was not
             # asked for any
             dt1, cs1 = _branch_grad(dx1, s1, N, dproj, projb is not None and need[6])
@@ -701,7 +783,7 @@ class BlockFn(torch.autograd.Function):
         if cs0 is not None and in_dtype == cdtype:
             _publish_stream_colsum(wq, dx, cs0)
         wq.end_block()                                   # the Block's 4 weight gradients: grouped launch now, or with the next Blocks'
-        return (_ret_grad(dx.view(B, N, -1), in_dtype), g_n1w, g_n1b) + ga + (g_n2w, g_n2b) + gm + (None,) * 8
+        return (_ret_grad(dx.view(B, N, -1), in_dtype), g_n1w, g_n1b) + ga + (g_n2w, g_n2b) + gm + (None,) * 8 + (g_g1, g_g2, None)
 
 
 TAIL_ROWS = os.environ.get("UCFVIT_TAIL_ROWS", "1") != "0"     # A/B switch: 0 = the last Block runs dense like every other
@@ -718,10 +800,11 @@ class TailBlockFn(torch.autograd.Function):
     backward (dres_period = N), rounded once like the dense Block's."""
 
     @staticmethod
-    def _run_forward(x2, B, N, num_heads, eps, c, params, s1=None, s2=None, sites=(None, None, None)):
+    def _run_forward(x2, B, N, num_heads, eps, c, params, s1=None, s2=None, sites=(None, None, None), g1=None, g2=None, keep=False):
         n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b = params
         dproj, d1, d2 = sites
-        plain1, plain2 = s1 is None and dproj is None, s2 is None and d2 is None
+        plain1, plain2 = s1 is None and dproj is None and g1 is None, s2 is None and d2 is None and g2 is None
+        b1 = b2 = None
         D = x2.shape[1]
         dh = D // num_heads
         ln1, mean1, rstd1 = ops.layernorm_fwd(x2, c(n1w), c(n1b), eps)
@@ -729,18 +812,25 @@ class TailBlockFn(torch.autograd.Function):
         o, lse = ops.attention_rows_fwd(qkv, B, N, num_heads, dh, dh ** -0.5, 0)
         xc = x2.view(B, N, D)[:, 0]                                                  # class rows of the stream: a [B, D] view, row stride N D
         x1 = ops.linear_fwd(o, c(projw), c(projb), residual=xc if plain1 else None)
-        if not plain1:
+        if g1 is not None:
+            b1 = x1 if keep else None
+            x1 = _ls_branch_exit(xc, x1, g1, s1, 1, dproj, keep)                     # ldr = N D, one row per sample, row_step = N in the site
+        elif not plain1:
             _branch_exit(xc, x1, s1, 1, dproj)                                       # one row per sample; the mask of dense row b N
         ln2, mean2, rstd2 = ops.layernorm_fwd(x1, c(n2w), c(n2b), eps)
         y, (h, a) = _mlp_fwd(ln2, c(f1w), c(f1b), c(f2w), c(f2b), x1 if plain2 else None, drop1=d1)
-        if not plain2:
+        if g2 is not None:
+            b2 = y if keep else None
+            y = _ls_branch_exit(x1, y, g2, s2, 1, d2, keep)
+        elif not plain2:
             _branch_exit(x1, y, s2, 1, d2)
-        return y, (mean1, rstd1, ln1, qkv, o, lse, x1, mean2, rstd2, ln2, h, a)
+        return y, (mean1, rstd1, ln1, qkv, o, lse, x1, mean2, rstd2, ln2, h, a, b1, b2)
 
     @staticmethod
     def forward(ctx, x, n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b, num_heads, eps, cdtype, recompute=False,
-                s1=None, s2=None, drop=None):
+                s1=None, s2=None, drop=None, gamma1=None, gamma2=None, save_branch=None):
         """recompute: as in BlockFn, only the Block's input is kept and backward re-runs the forward launches (bit-identical);
+        gamma1, gamma2, save_branch: the LayerScale parameters and the grad-mode flag as in BlockFn, applied to the class rows;
         s1, s2: the drop-path scales of the two branches as in BlockFn, one row per sample from the attention on;
         drop: BlockFn's dropout argument; the mask index steps by N rows, so class row b draws the mask of row b N of the dense Block"""
         xin = _as(x, cdtype)
@@ -749,11 +839,12 @@ class TailBlockFn(torch.autograd.Function):
         x2 = xin.view(B * N, D)
         c = lambda p: compute_param(p, cdtype)
         params = (n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b)
-        y, saved = TailBlockFn._run_forward(x2, B, N, num_heads, eps, c, params, s1, s2, sites)
+        keep = not recompute and any(ctx.needs_input_grad) and (save_branch is None or bool(save_branch))
+        y, saved = TailBlockFn._run_forward(x2, B, N, num_heads, eps, c, params, s1, s2, sites, gamma1, gamma2, keep)
         if recompute:
-            ctx.save_for_backward(x2, *params, s1, s2)
+            ctx.save_for_backward(x2, *params, s1, s2, gamma1, gamma2)
         else:
-            ctx.save_for_backward(x2, *saved, *params, s1, s2)
+            ctx.save_for_backward(x2, *saved, *params, s1, s2, gamma1, gamma2)
         ctx.meta = (B, N, num_heads, cdtype, x.dtype)
         ctx.recompute, ctx.eps = recompute, eps
         return y
@@ -763,32 +854,40 @@ class TailBlockFn(torch.autograd.Function):
         B, N, H, cdtype, in_dtype = ctx.meta
         c = lambda p: compute_param(p, cdtype)
         if ctx.recompute:
-            x2, *params, s1, s2 = ctx.saved_tensors
-            _, saved = TailBlockFn._run_forward(x2, B, N, H, ctx.eps, c, tuple(params), s1, s2, ctx.sites)
-            (mean1, rstd1, ln1, qkv, o, lse, x1, mean2, rstd2, ln2, h, a) = saved
+            x2, *params, s1, s2, g1, g2 = ctx.saved_tensors
+            _, saved = TailBlockFn._run_forward(x2, B, N, H, ctx.eps, c, tuple(params), s1, s2, ctx.sites, g1, g2, True)
+            (mean1, rstd1, ln1, qkv, o, lse, x1, mean2, rstd2, ln2, h, a, b1, b2) = saved
             n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b = params
         else:
-            (x2, mean1, rstd1, ln1, qkv, o, lse, x1, mean2, rstd2, ln2, h, a,
-             n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b, s1, s2) = ctx.saved_tensors
+            (x2, mean1, rstd1, ln1, qkv, o, lse, x1, mean2, rstd2, ln2, h, a, b1, b2,
+             n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b, s1, s2, g1, g2) = ctx.saved_tensors
         need = ctx.needs_input_grad
         D = x2.shape[1]
         dh = D // H
         dy2 = _as(dy, cdtype).reshape(B, D)
         wq = _queue_for(qkvw)
         dproj, d1, d2 = ctx.sites
+        g_g1 = g_g2 = None
         dt2, cs2 = dy2, _take_stream_colsum(wq, dy2)
-        if s2 is not None or d2 is not None:               # as in BlockFn: the published sums of the unscaled dy are dropped
+        if g2 is not None:
+            dt2, cs2, gs2 = _ls_branch_grad(dy2, b2, g2, s2, 1, d2, f2b is not None and need[12], need[21])
+            g_g2 = _bgrad_from(g2, gs2) if gs2 is not None else None
+        elif s2 is not None or d2 is not None:             # as in BlockFn: the published sums of the unscaled dy are dropped
             dt2, cs2 = _branch_grad(dy2, s2, 1, d2, f2b is not None and need[12])
         dln2, gm = _mlp_bwd(dt2, ln2, (h, a), c(f1w), c(f2w), f1w, f1b, f2w, f2b, need[9:13], None, wq, dy2_colsum=cs2, drop1=d1)
         pb_out, pb_acc, g_projb = None, False, None
-        if s1 is None and dproj is None and projb is not None and need[6]:
+        if s1 is None and dproj is None and g1 is None and projb is not None and need[6]:
             pb_out, pb_acc = grad_target(projb)
             if pb_out is None:
                 pb_out = torch.empty(projb.shape, dtype=torch.float32, device=dy2.device)
             g_projb = None if pb_acc else pb_out
         dx1, g_n2w, g_n2b = _ln_bwd(dln2, x1, c(n2w), mean2, rstd2, n2w, n2b, dres=dy2, dx_colsum=pb_out, dx_colsum_accumulate=pb_acc)
         dt1 = dx1
-        if s1 is not None or dproj is not None:
+        if g1 is not None:
+            dt1, cs1, gs1 = _ls_branch_grad(dx1, b1, g1, s1, 1, dproj, projb is not None and need[6], need[20])
+            g_projb = _bgrad_from(projb, cs1) if cs1 is not None else None
+            g_g1 = _bgrad_from(g1, gs1) if gs1 is not None else None
+        elif s1 is not None or dproj is not None:
             dt1, cs1 = _branch_grad(dx1, s1, 1, dproj, projb is not None and need[6])
             g_projb = _bgrad_from(projb, cs1) if cs1 is not None else None
         g_projw = _wgrad(projw, dt1, o, wq) if need[5] else None
@@ -813,7 +912,7 @@ class TailBlockFn(torch.autograd.Function):
         if cs0 is not None and in_dtype == cdtype:
             _publish_stream_colsum(wq, dx, cs0)           # the fc2 bias gradient of the Block before this one
         wq.end_block()
-        return (_ret_grad(dx.view(B, N, D), in_dtype), g_n1w, g_n1b, g_qkvw, g_qkvb, g_projw, g_projb, g_n2w, g_n2b) + gm + (None,) * 7
+        return (_ret_grad(dx.view(B, N, D), in_dtype), g_n1w, g_n1b, g_qkvw, g_qkvb, g_projw, g_projb, g_n2w, g_n2b) + gm + (None,) * 7 + (g_g1, g_g2, None)
 
 
 class PatchEmbedFn(torch.autograd.Function):

@@ -152,6 +152,8 @@ SIGNATURES = {
     "ucfvit_drop_path_scale": (c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _I, _P]),
     "ucfvit_dropout": (c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _D, c_uint64, _I, _P]),
     "ucfvit_dropout_add": (c_int, [_P, _I64, _P, _P, _P, _I64, _I64, _I64, _I64, _D, c_uint64, _I, _P]),
+    "ucfvit_layer_scale_add": (c_int, [_P, _I64, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _D, c_uint64, _I, _P]),
+    "ucfvit_layer_scale_grad": (c_int, [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _D, c_uint64, _I, _P]),
 }
 
 _lib = None

@@ -1572,6 +1572,84 @@ def dropout(x, p, seed, s=None, rows_per_sample=1, row_step=1, out=None, c_colsu
     return out
 
 
+# ------------------------------------------------------------------------------------------------ LayerScale
+def _chk_layer_scale(gamma, s, rows, D, rows_per_sample, row_step, p, seed, name):
+    _chk(gamma, name + ".gamma")
+    if gamma.dtype != torch.float32 or gamma.numel() != D:
+        raise TypeError(f"{name}: gamma must be a contiguous fp32 tensor of D = {D} elements (the master parameter)")
+    if s is not None:
+        _chk_drop_scale(s, rows, rows_per_sample, name)
+    elif rows_per_sample <= 0 or rows % rows_per_sample:
+        raise ValueError(f"{name}: {rows} rows are not a multiple of rows_per_sample={rows_per_sample}")
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"{name}: the kernels take 0 <= p < 1 (0: no mask), got p={p}")
+    if row_step < 1:
+        raise ValueError(f"{name}: row_step={row_step} < 1")
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"{name}: the seed must be an unsigned 64-bit integer, got {seed}")
+
+
+def layer_scale_add(res, branch, gamma, s=None, rows_per_sample=1, p=0.0, seed=0, row_step=1, out=None):
+    """out[r] = res[r] + s[r // rows_per_sample] * m * (gamma * branch[r]) / keep; gamma fp32 [D]; res None: without the residual (the
+    LayerScale module on its own); s: optional fp32 drop-path scale per sample; p > 0: the dropout mask of (seed, element index) as in
+    dropout_add, p == 0: no mask.  res [rows, D] may have padded rows, out may be branch (the default: the branch is overwritten)."""
+    L = _l.load()
+    _chk(branch, "layer_scale_add.branch")
+    rows, D = branch.shape
+    out = branch if out is None else _chk(out, "layer_scale_add.out")
+    if tuple(out.shape) != (rows, D) or out.dtype != branch.dtype:
+        raise TypeError("layer_scale_add: res, branch and out must be [rows, D] of one dtype")
+    if res is not None:
+        _chk(res, "layer_scale_add.res", rows_ok=True)
+        if tuple(res.shape) != (rows, D) or res.dtype != branch.dtype:
+            raise TypeError("layer_scale_add: res, branch and out must be [rows, D] of one dtype")
+    _chk_layer_scale(gamma, s, rows, D, rows_per_sample, row_step, p, seed, "layer_scale_add")
+    _l.check(L.ucfvit_layer_scale_add(_p(res), 0 if res is None else res.stride(0), branch.data_ptr(), gamma.data_ptr(), _p(s), out.data_ptr(),
+                                      rows, D, int(rows_per_sample), int(row_step), float(p), int(seed), dt(branch), _stream()),
+             "ucfvit_layer_scale_add")
+    return out
+
+
+def layer_scale_grad(dy, branch, gamma, s=None, rows_per_sample=1, p=0.0, seed=0, row_step=1, out=None, c_colsum=None,
+                     c_colsum_accumulate=False, c_gamma=None, c_gamma_accumulate=False):
+    """out[r] = gamma * g[r] with g[r] = s[r // rows_per_sample] * m * dy[r] / keep (s, mask as in layer_scale_add; out may be dy);
+    c_colsum: optional fp32 [D] that receives (+)= the column sums of gamma * g (the exit Linear's bias gradient); c_gamma: optional fp32 [D]
+    that receives (+)= the column sums of g * branch (gamma's gradient; branch, the unscaled branch output, may be None without it).  Both
+    are taken in fp32 before rounding: partial sums per row chunk from the kernel, folded by ucfvit_reduce_rows."""
+    L = _l.load()
+    _chk(dy, "layer_scale_grad.dy")
+    rows, D = dy.shape
+    out = torch.empty_like(dy) if out is None else _chk(out, "layer_scale_grad.out")
+    if tuple(out.shape) != (rows, D) or out.dtype != dy.dtype:
+        raise TypeError("layer_scale_grad: out must have dy's shape and dtype")
+    if branch is not None:
+        _chk(branch, "layer_scale_grad.branch")
+        if tuple(branch.shape) != (rows, D) or branch.dtype != dy.dtype:
+            raise TypeError("layer_scale_grad: branch must have dy's shape and dtype")
+    elif c_gamma is not None:
+        raise ValueError("layer_scale_grad: the gamma sums need the branch output (branch is None)")
+    _chk_layer_scale(gamma, s, rows, D, rows_per_sample, row_step, p, seed, "layer_scale_grad")
+    cs_rows, parts = 0, [None, None]
+    if c_colsum is not None or c_gamma is not None:
+        for i, (c, nm) in enumerate(((c_colsum, "c_colsum"), (c_gamma, "c_gamma"))):
+            if c is None:
+                continue
+            _chk(c, "layer_scale_grad." + nm)
+            if c.dtype != torch.float32 or c.numel() != D:
+                raise TypeError(f"layer_scale_grad: {nm} must be a contiguous fp32 tensor of D elements")
+        cs_rows = L.ucfvit_drop_path_colsum_rows(rows, int(rows_per_sample), D)
+        if cs_rows <= 0:
+            raise ValueError("layer_scale_grad: no column sums of an empty input")
+        ws = workspace(2 * cs_rows * D * 4, dy.device)
+        parts = [ws[:cs_rows * D] if c_colsum is not None else None, ws[cs_rows * D:2 * cs_rows * D] if c_gamma is not None else None]
+    _l.check(L.ucfvit_layer_scale_grad(dy.data_ptr(), _p(branch), gamma.data_ptr(), _p(s), out.data_ptr(), _p(parts[0]), _p(parts[1]), rows, D,
+                                       int(rows_per_sample), int(row_step), float(p), int(seed), dt(dy), _stream()), "ucfvit_layer_scale_grad")
+    for part, c, acc in ((parts[0], c_colsum, c_colsum_accumulate), (parts[1], c_gamma, c_gamma_accumulate)):
+        if part is not None:
+            _l.check(L.ucfvit_reduce_rows(part.data_ptr(), c.data_ptr(), cs_rows, D, 1 if acc else 0, _stream()), "ucfvit_reduce_rows")
+    return out
+
+
 def transpose_batched(src_flat, dst_flat, table, n_mats, total_tiles):
     L = _l.load()
     _l.check(L.ucfvit_transpose_batched(src_flat.data_ptr(), dst_flat.data_ptr(), table.data_ptr(), n_mats, total_tiles, _stream()),

@@ -16,7 +16,7 @@ import torch.nn as nn
 from UCF_VIT.simple.building_blocks import (  # noqa: F401  (re-exported operator set)
     PatchEmbed, LayerNorm, Linear, DropPath, HipDropout, LayerScale, PatchDropout, MyUnetBlock, EmbeddingDenseLayer,
     VariableMapping_Attention, to_2tuple, to_3tuple, trunc_normal_, get_act_layer, get_norm_layer, LayerType,
-    set_compute_dtype, _cd, _no_dropout, _assert, _draw_drop_path, _draw_dropout, _block_dropout)
+    set_compute_dtype, _cd, _no_dropout, _assert, _draw_drop_path, _draw_dropout, _block_dropout, _block_gammas)
 from UCF_VIT.simple import building_blocks as _S
 from UCF_VIT.utils.fused_attn import FusedAttn
 from UCF_VIT._hip import functional as HF
@@ -102,6 +102,10 @@ class Block(nn.Module):
         if drop_path > 0.0 and tensor_par_size > 1:
             raise NotImplementedError(f"Block(drop_path={drop_path}) under a tensor-parallel group (tensor_par_group={tensor_par_group!r}, "
                                       f"tensor_par_size={tensor_par_size}): every rank of the group would need the same draw; not implemented")
+        if init_values and tensor_par_size > 1:
+            raise NotImplementedError(f"Block(init_values={init_values}) under a tensor-parallel group (tensor_par_group={tensor_par_group!r}, "
+                                      f"tensor_par_size={tensor_par_size}): LayerScale would have to follow the group's sum of the "
+                                      "row-parallel exit GEMM; not implemented")
         self.tensor_par_size, self.tensor_par_group = tensor_par_size, tensor_par_group
         self.norm1 = norm_layer(dim)
         self.attn = Attention(dim, fused_attn=fused_attn, num_heads=num_heads, qkv_bias=qkv_bias, qk_norm=qk_norm, attn_drop=attn_drop,
@@ -116,7 +120,8 @@ class Block(nn.Module):
 
     def _fusable(self):
         return (isinstance(self.norm1, nn.LayerNorm) and isinstance(self.norm2, nn.LayerNorm) and self.norm1.eps == self.norm2.eps
-                and isinstance(self.ls1, nn.Identity) and isinstance(self.ls2, nn.Identity)
+                and ((isinstance(self.ls1, nn.Identity) and isinstance(self.ls2, nn.Identity))
+                     or (type(self.ls1) is LayerScale and type(self.ls2) is LayerScale))
                 and type(self.attn) is Attention and self.attn._fusable() and type(self.mlp) is Mlp and self.mlp._fusable()
                 and self.mlp.fc1.out_features % 8 == 0)
 
@@ -132,6 +137,9 @@ class Block(nn.Module):
                     getattr(self, "activation_checkpointing", False) and torch.is_grad_enabled())
             s1, s2 = _draw_drop_path(self.drop_path1, x), _draw_drop_path(self.drop_path2, x)      # None under a tensor-parallel group
             drop = _block_dropout(a, m)
+            g1, g2 = _block_gammas(self)                                                           # None under a tensor-parallel group
+            if g1 is not None:
+                return HF.BlockFn.apply(*args, s1, s2, drop, g1, g2, torch.is_grad_enabled())
             if s1 is None and s2 is None and drop is None:
                 return HF.BlockFn.apply(*args)
             return HF.BlockFn.apply(*args, s1, s2, drop)

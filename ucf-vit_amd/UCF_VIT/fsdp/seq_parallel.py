@@ -294,6 +294,11 @@ class SeqParallelBlock(nn.Module):
             if getattr(d, "drop_prob", 0.0) > 0.0:
                 raise NotImplementedError(f"Block(drop_path={d.drop_prob}) under a sequence-parallel group of {self.spg.size} ranks: every "
                                           "rank of the group would need the same draw; not implemented")
+        for ls in (getattr(block, "ls1", None), getattr(block, "ls2", None)):
+            if hasattr(ls, "gamma"):
+                raise NotImplementedError(f"Block(init_values=...) under a sequence-parallel group of {self.spg.size} ranks "
+                                          f"(group {getattr(self.spg, 'sp_group', None)!r}): the gradient of LayerScale's gamma would need a sum over the "
+                                          "group; not implemented")
         for p in block.parameters():
             p._ucf_sharded = "sequence"     # gradients are per-token-shard partial sums: HipGradScaler refuses a per-rank skip decision
 

@@ -173,12 +173,26 @@ def _block_dropout(attn, mlp):
 
 
 class LayerScale(nn.Module):
+    """timm's LayerScale: y = gamma ⊙ x with one learned fp32 factor per channel (state_dict key `gamma`).  Applying it is HIP
+    (csrc/layer_scale.hip); `inplace` is accepted for the signature only.  Inside a fused Block the module only holds the parameter:
+    HF.BlockFn / HF.TailBlockFn take the gammas and fold them into the branch-exit row pass."""
+
     def __init__(self, dim, init_values=1e-5, inplace=False):
         super().__init__()
         self.gamma = nn.Parameter(init_values * torch.ones(dim))
 
     def forward(self, x):
-        raise NotImplementedError("LayerScale (init_values) is not on the HIP hot path; reference configs use init_values=None")
+        if not x.is_cuda:
+            raise RuntimeError(f"LayerScale: expected a tensor on the MI355X (cuda) device, got {x.device}. "
+                               "UCF_VIT operators run only through libucfvit_hip.so; there is no CPU path.")
+        return HF.LayerScaleFn.apply(x, self.gamma)
+
+
+def _block_gammas(block):
+    """(gamma1, gamma2) of a fused Block: both LayerScale parameters, or (None, None) when ls1 / ls2 are Identity"""
+    if isinstance(block.ls1, LayerScale):
+        return block.ls1.gamma, block.ls2.gamma
+    return None, None
 
 
 class PatchDropout(nn.Module):
@@ -294,11 +308,12 @@ class Attention(nn.Module):
 
 
 class Block(nn.Module):
-    """Pre-LN transformer block.  With the reference configuration (no LayerScale, standard Attention/Mlp) the whole block is ONE
+    """Pre-LN transformer block.  With standard Attention/Mlp the whole block is ONE
     autograd node running a fixed sequence of fused HIP launches (HF.BlockFn).  drop_path > 0 in training: the two DropPath modules
     draw their per-sample scales and the node applies them (one row pass per branch and direction); proj_drop > 0 in training: the
     three HipDropout modules draw their seeds and the same row passes apply the masks (plus one pass over the activation).  Eval or
-    rates 0 run the very launches of a Block without either."""
+    rates 0 run the very launches of a Block without either.  init_values: ls1 / ls2 are LayerScale modules and the node folds their
+    gammas into the same row passes (a branch with a gamma always takes one); without it the launches are those of a Block without."""
 
     def __init__(self, dim: int, num_heads: int, fused_attn: FusedAttn = FusedAttn.NONE, mlp_ratio: float = 4.0,
                  qkv_bias: bool = False, qk_norm: bool = False, proj_drop: float = 0.0, attn_drop: float = 0.0,
@@ -319,7 +334,8 @@ class Block(nn.Module):
     def _fusable(self):
         return (isinstance(self.norm1, nn.LayerNorm) and isinstance(self.norm2, nn.LayerNorm)
                 and self.norm1.elementwise_affine and self.norm2.elementwise_affine and self.norm1.eps == self.norm2.eps
-                and isinstance(self.ls1, nn.Identity) and isinstance(self.ls2, nn.Identity)
+                and ((isinstance(self.ls1, nn.Identity) and isinstance(self.ls2, nn.Identity))
+                     or (type(self.ls1) is LayerScale and type(self.ls2) is LayerScale))
                 and type(self.attn) is Attention and self.attn._fusable()
                 and type(self.mlp) is Mlp and self.mlp._fusable()
                 and self.mlp.fc1.out_features % 8 == 0)
@@ -333,6 +349,9 @@ class Block(nn.Module):
                     a.num_heads, self.norm1.eps, _cd(self), None, self.activation_checkpointing and torch.is_grad_enabled())
             s1, s2 = _draw_drop_path(self.drop_path1, x), _draw_drop_path(self.drop_path2, x)      # two independent draws, s1 first
             drop = _block_dropout(a, m)
+            g1, g2 = _block_gammas(self)
+            if g1 is not None:
+                return HF.BlockFn.apply(*args, s1, s2, drop, g1, g2, torch.is_grad_enabled())
             if s1 is None and s2 is None and drop is None:
                 return HF.BlockFn.apply(*args)
             return HF.BlockFn.apply(*args, s1, s2, drop)
@@ -349,6 +368,9 @@ class Block(nn.Module):
                 a.num_heads, self.norm1.eps, _cd(self), self.activation_checkpointing and torch.is_grad_enabled())
         s1, s2 = _draw_drop_path(self.drop_path1, x), _draw_drop_path(self.drop_path2, x)
         drop = _block_dropout(a, m)
+        g1, g2 = _block_gammas(self)
+        if g1 is not None:
+            return HF.TailBlockFn.apply(*args, s1, s2, drop, g1, g2, torch.is_grad_enabled())
         if s1 is None and s2 is None and drop is None:
             return HF.TailBlockFn.apply(*args)
         return HF.TailBlockFn.apply(*args, s1, s2, drop)

@@ -45,8 +45,8 @@ def model_args(conf):
     chans = 1 if d.get("single_channel", False) else max(1, d["num_channels_used"][dataset])
     adaptive = bool(a.get("adaptive_patching", False))
     return dict(img_size=a["tile_size"], patch_size=a["patch_size"], in_chans=chans, embed_dim=a["embed_dim"], depth=a["depth"],
-                num_heads=a["num_heads"], mlp_ratio=a["mlp_ratio"], drop_path_rate=a.get("drop_path", 0.0), pos_drop_rate=a.get("pos_drop_rate", 0.0),
-                proj_drop_rate=a.get("proj_drop_rate", 0.0), twoD=a["twoD"],
+                num_heads=a["num_heads"], mlp_ratio=a["mlp_ratio"], drop_path_rate=a.get("drop_path", 0.0), init_values=a.get("init_values"),
+                pos_drop_rate=a.get("pos_drop_rate", 0.0), proj_drop_rate=a.get("proj_drop_rate", 0.0), twoD=a["twoD"],
                 default_vars=a["default_vars"], single_channel=d.get("single_channel", False), use_varemb=bool(a.get("use_varemb", False)),
                 adaptive_patching=adaptive, fixed_length=a.get("fixed_length", 4096),
                 use_adaptive_pos_emb=bool(a.get("use_adaptive_pos_emb", False)) and adaptive), a, d
