@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define UCFVIT_ABI_VERSION 24 /* still 24 with the dropout and LayerScale entry points (ucfvit_dropout*, ucfvit_layer_scale_*): symbols were only added */
+#define UCFVIT_ABI_VERSION 24 /* still 24 with the dropout, LayerScale and QK-norm entry points (ucfvit_dropout*, ucfvit_layer_scale_*, ucfvit_qk_norm_*): symbols were only added */
 
 #define UCFVIT_OK 0
 #define UCFVIT_ERR_INVALID_ARGUMENT (-1)
@@ -764,6 +764,34 @@ int ucfvit_layer_scale_add(const void* res, int64_t ldr, const void* branch, con
 int ucfvit_layer_scale_grad(const void* dy, const void* branch, const float* gamma, const float* s, void* dbranch, float* colsum_partial,
                             float* gamma_partial, int64_t rows, int64_t D, int64_t rows_per_sample, int64_t row_step, double p, uint64_t seed,
                             int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * QK-norm (csrc/qk_norm.hip): the q_norm / k_norm of the reference's Attention, a LayerNorm over the dh elements of every (row, head)
+ * segment of Q and of K, applied between the qkv Linear and the attention core.  The layout is the attention contract: qkv is
+ * [rows = B N][3][H][dh], what the qkv GEMM writes and ucfvit_attention_fwd / ucfvit_attention_rows_fwd read.  dh is 32, 64 or 128, the
+ * dtype fp32 or bf16.  gamma_q, beta_q, gamma_k, beta_k are fp32 [dh], shared by all heads: the master parameters, read directly.  fp32
+ * arithmetic (mean, then the biased variance of the centred values, rstd = rsqrt(var + eps)), one rounding to the output type; 16-byte
+ * accesses, so qkv / dqkv / saved_qk must be 16-byte aligned; no atomics, a fixed summation order, the same bits on every call.
+ *
+ * ucfvit_qk_norm_fwd: normalises the Q and K thirds of qkv in place, Q with (gamma_q, beta_q), K with (gamma_k, beta_k); the V third is
+ *   neither read nor written.  saved_qk, mean, rstd go together: all three NULL (eval, no_grad) writes nothing but the in-place result;
+ *   otherwise saved_qk [rows][2][H][dh] of the dtype receives the un-normalised Q and K bit for bit and mean / rstd fp32 [rows][2][H] the
+ *   statistics.  The in-place result is the same bits either way.
+ * ucfvit_qk_norm_bwd: rewrites the Q and K thirds of dqkv in place, from the gradient of the normalised values to the gradient of the
+ *   Linear's output: dx = rstd * (g - mean_seg(g) - xhat * mean_seg(g * xhat)) with g = dy * gamma and xhat = (saved - mean) * rstd
+ *   recomputed in fp32.  The V third is untouched.  param_partial (may be NULL) is fp32 [R][4][dh]: per row chunk the sums over rows and
+ *   heads of dy * xhat and of dy for Q, then for K (dgamma_q, dbeta_q, dgamma_k, dbeta_k).  colsum_partial (may be NULL) is fp32
+ *   [R][2][H][dh]: per row chunk the column sums of the values written to the Q and K thirds, taken before rounding: folded, the Q and K
+ *   thirds of the qkv bias gradient (with a LayerNorm behind the bias the K third is no longer 0 and the Q third no longer the sum of
+ *   dQ).  R = ucfvit_qk_norm_partial_rows(rows, H, dh) (0 for what the kernels refuse); ucfvit_reduce_rows folds both.
+ * Arguments (null pointers, null parameters, dh outside {32, 64, 128}, H < 1, rows < 0 or >= 2^31 - 4096, eps < 0 or NaN, dtype,
+ * alignment, saved_qk without the statistics or the reverse, sums of an empty input) are checked before any HIP call.
+ * ------------------------------------------------------------------------------------------------------ */
+int64_t ucfvit_qk_norm_partial_rows(int64_t rows, int64_t H, int64_t dh);
+int ucfvit_qk_norm_fwd(void* qkv, const float* gamma_q, const float* beta_q, const float* gamma_k, const float* beta_k, void* saved_qk,
+                       float* mean, float* rstd, int64_t rows, int64_t H, int64_t dh, float eps, int dtype, void* stream);
+int ucfvit_qk_norm_bwd(void* dqkv, const void* saved_qk, const float* gamma_q, const float* gamma_k, const float* mean, const float* rstd,
+                       float* param_partial, float* colsum_partial, int64_t rows, int64_t H, int64_t dh, int dtype, void* stream);
 
 #ifdef __cplusplus
 }

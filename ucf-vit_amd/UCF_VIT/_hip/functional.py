@@ -295,22 +295,57 @@ class TP:
 # fc2: 4D/tp columns; reference fsdp/building_blocks.py:123-142,169-217): the exit GEMM output is SUM-all-reduced (forward) and
 # the entry gradient is SUM-all-reduced (backward).  The residual is fused on TP rank 0 only, so the sum adds it exactly once;
 # the row-parallel biases are added on every rank like the reference does (bias counted tp times).
-def _attn_fwd(x2, B, N, H, wqkv, bqkv, wproj, bproj, residual, tp=None):
+# QK-norm (the reference Attention's q_norm / k_norm): qkn = (gamma_q, beta_q, gamma_k, beta_k, eps), the four fp32 [dh] master parameters
+# of the two LayerNorms and their eps, or None = exactly the launches without it.  ops.qk_norm_fwd normalises the Q and K thirds of the qkv
+# buffer in place between the qkv GEMM and the attention kernels, which do not change.  For backward it keeps the un-normalised Q and K
+# (saved_qk: two more D-wide token matrices per Block, the price LayerScale paid for its branch outputs) and the fp32 statistics.
+def _refuse_group_qk_norm(tp, qkn):
+    if tp is not None and qkn is not None:
+        raise NotImplementedError(f"qk_norm under a tensor-parallel group (tp group {tp.group!r}, size {tp.size}): the heads are sharded and "
+                                  "the [head_dim] parameters replicated, so their gradient would have to be summed over the group; not implemented")
+
+
+def _qkn_of(qnw, qnb, knw, knb, eps):
+    """the Functions' five trailing arguments -> qkn, or None without qk_norm"""
+    if qnw is None and qnb is None and knw is None and knb is None:
+        return None
+    if qnw is None or qnb is None or knw is None or knb is None or eps is None:
+        raise ValueError("qk_norm needs q_norm.weight, q_norm.bias, k_norm.weight, k_norm.bias and eps together")
+    return (qnw, qnb, knw, knb, float(eps))
+
+
+def _attn_fwd(x2, B, N, H, wqkv, bqkv, wproj, bproj, residual, tp=None, qkn=None, save_qk=True):
+    """-> y, (qkv, o, lse, saved_qk, mean_qk, rstd_qk); the last three are None without qkn, or with save_qk false (no backward follows)"""
     dh = wproj.shape[0] // H
     Hl = H // tp.size if tp else H
     qkv = ops.linear_fwd(x2, wqkv, bqkv)                               # K4: qkv GEMM + bias
+    sq = (None, None, None)
+    if qkn is not None:
+        _refuse_group_qk_norm(tp, qkn)
+        sq = ops.qk_norm_fwd(qkv, qkn[0], qkn[1], qkn[2], qkn[3], Hl, dh, qkn[4], save=save_qk)      # in place: Q, K <- LayerNorm over dh
     o, lse = ops.attention_fwd(qkv, B, N, Hl, dh, dh ** -0.5)          # K5: fused softmax(QKᵀ)V over the local heads
     if tp and tp.rank != 0:
         residual = None
     y = ops.linear_fwd(o, wproj, bproj, residual=residual)             # K6: proj GEMM + bias (+ residual)
     if tp:
         tp.all_reduce(y)                                               # C3: exit all-reduce
-    return y, (qkv, o, lse)
+    return y, (qkv, o, lse, *sq)
 
 
-def _attn_bwd(dy2, x2, saved, B, N, H, wqkv, wproj, p_qkvw, p_qkvb, p_projw, p_projb, needs, tp=None, wq=None, projb_done=None):
-    """projb_done: (grad,) when the producer of dy2 (LayerNorm backward) has already written the proj bias gradient"""
-    qkv, o, lse = saved
+def _qkn_bwd(dqkv, sq, qkn, H, dh, qkn_needs, gb2, gb2_acc):
+    """the QK-norm backward over the Q and K thirds of dqkv, in place; gb2: fp32 [2 H dh] view that receives (+)= the Q and K thirds of the
+    qkv bias gradient, or None.  -> the four parameter gradients (through the path LayerScale's gamma takes)"""
+    saved_qk, mean, rstd = sq
+    pg = torch.empty((4, dh), dtype=torch.float32, device=dqkv.device) if any(qkn_needs) else None
+    ops.qk_norm_bwd(dqkv, saved_qk, qkn[0], qkn[2], mean, rstd, H, dh, param_grads=pg, c_colsum=gb2, c_colsum_accumulate=gb2_acc)
+    return tuple(_bgrad_from(qkn[i], pg[i]) if qkn_needs[i] else None for i in range(4))
+
+
+def _attn_bwd(dy2, x2, saved, B, N, H, wqkv, wproj, p_qkvw, p_qkvb, p_projw, p_projb, needs, tp=None, wq=None, projb_done=None, qkn=None,
+              qkn_needs=(False,) * 4):
+    """projb_done: (grad,) when the producer of dy2 (LayerNorm backward) has already written the proj bias gradient
+    qkn: as in _attn_fwd; then -> dx, grads, (the gradients of gamma_q, beta_q, gamma_k, beta_k)"""
+    qkv, o, lse, *sq = saved
     dh = wproj.shape[0] // H
     H = H // tp.size if tp else H
     g_projw = _wgrad(p_projw, dy2, o, wq) if needs[2] else None
@@ -319,7 +354,22 @@ def _attn_bwd(dy2, x2, saved, B, N, H, wqkv, wproj, p_qkvw, p_qkvb, p_projw, p_p
     else:
         g_projb = _bgrad(p_projb, dy2) if (p_projb is not None and needs[3]) else None
     want_b = p_qkvb is not None and needs[1]
-    if want_b and ops.attention_bwd_colsum_supported(B, N, H, dh, qkv.dtype):
+    g_qkn = None
+    if qkn is not None:
+        # with a LayerNorm between the bias and the scores the shortcut below does not hold for the Q and K thirds (the K third is not 0, the Q
+        # third not the sum of dQ): they are the column sums of what qk_norm_bwd writes; the V third is still the column sum of dO
+        Dl = H * dh
+        gb, acc = grad_target(p_qkvb) if want_b else (None, False)
+        if want_b and gb is None:
+            gb, acc = torch.empty(3 * Dl, dtype=torch.float32, device=dy2.device), False
+        from_epi = want_b and _BIAS_FROM_EPILOGUE
+        do = _dgrad(dy2, p_projw, wproj, c_colsum=gb[2 * Dl:] if from_epi else None, c_colsum_accumulate=acc)
+        dqkv = ops.attention_bwd(qkv, o, do, lse, B, N, H, dh, dh ** -0.5)
+        if want_b and not from_epi:
+            ops.colsum(dqkv[:, 2 * Dl:], out=gb[2 * Dl:], accumulate=acc)
+        g_qkn = _qkn_bwd(dqkv, sq, qkn, H, dh, qkn_needs, gb[:2 * Dl] if want_b else None, acc)
+        g_qkvb = (None if acc else gb) if want_b else None
+    elif want_b and ops.attention_bwd_colsum_supported(B, N, H, dh, qkv.dtype):
         # the qkv bias gradient without a second read of dqkv (include/ucfvit_hip.h, ucfvit_attention_bwd_colsum): Q third = the per-image
         # column sums the backward kernel hands out, summed over the images; K third = 0 exactly; V third = the column sums of dO, taken in
         # the epilogue of the GEMM that produces dO
@@ -339,6 +389,8 @@ def _attn_bwd(dy2, x2, saved, B, N, H, wqkv, wproj, p_qkvw, p_qkvb, p_projw, p_p
     dx = _dgrad(dqkv, p_qkvw, wqkv)
     if tp:
         tp.all_reduce(dx)                                              # C2: entry gradient all-reduce
+    if qkn is not None:
+        return dx, (g_qkvw, g_qkvb, g_projw, g_projb), g_qkn
     return dx, (g_qkvw, g_qkvb, g_projw, g_projb)
 
 
@@ -443,34 +495,44 @@ class AttentionFn(torch.autograd.Function):
     """Attention.forward (building_blocks.py:157-192): qkv Linear -> fused SDPA -> proj Linear."""
 
     @staticmethod
-    def forward(ctx, x, qkvw, qkvb, projw, projb, num_heads, cdtype, tp=None, drop=None):
-        """drop: (p, seed) of proj_drop in training, or None"""
+    def forward(ctx, x, qkvw, qkvb, projw, projb, num_heads, cdtype, tp=None, drop=None, qnw=None, qnb=None, knw=None, knb=None, qk_eps=None,
+                save_qk=None):
+        """drop: (p, seed) of proj_drop in training, or None
+        qnw, qnb, knw, knb, qk_eps: the weight and bias of q_norm and k_norm (fp32 [head_dim] master parameters) and their eps, or None: the
+        Q and K thirds of the qkv buffer are LayerNormed per head in place before the attention kernels.  When a backward pass can follow
+        the un-normalised Q and K are kept (two more D-wide token matrices) with the fp32 statistics; save_qk: whether one can (the caller
+        passes torch.is_grad_enabled(), as for BlockFn's save_branch); None: decided from needs_input_grad alone"""
         drop = _site(drop, tp)
+        qkn = _qkn_of(qnw, qnb, knw, knb, qk_eps)
+        _refuse_group_qk_norm(tp, qkn)
+        keep = any(ctx.needs_input_grad) and (save_qk is None or bool(save_qk))
         xin = _as(x, cdtype)
         B, N, D = xin.shape
         x2 = xin.view(B * N, D)
         c = lambda p: compute_param(p, cdtype)
-        y, saved = _attn_fwd(x2, B, N, num_heads, c(qkvw), c(qkvb), c(projw), c(projb), None, tp)
+        y, saved = _attn_fwd(x2, B, N, num_heads, c(qkvw), c(qkvb), c(projw), c(projb), None, tp, qkn, keep)
         if drop is not None:
             _dropout(y, drop, out=y)
-        ctx.save_for_backward(x2, *saved, qkvw, qkvb, projw, projb)
+        ctx.save_for_backward(x2, *saved, qkvw, qkvb, projw, projb, qnw, qnb, knw, knb)
         ctx.meta = (B, N, num_heads, cdtype, x.dtype, tp)
+        ctx.qk_eps = qk_eps
         ctx.drop = drop
         return y.view(B, N, D)
 
     @staticmethod
     def backward(ctx, dy):
-        x2, qkv, o, lse, qkvw, qkvb, projw, projb = ctx.saved_tensors
+        x2, qkv, o, lse, sqk, mqk, rqk, qkvw, qkvb, projw, projb, qnw, qnb, knw, knb = ctx.saved_tensors
         B, N, H, cdtype, in_dtype, tp = ctx.meta
+        qkn = _qkn_of(qnw, qnb, knw, knb, ctx.qk_eps)
         dy2 = _as(dy, cdtype).reshape(x2.shape)
         c = lambda p: compute_param(p, cdtype)
         projb_done = None
         if ctx.drop is not None:                               # the gradient of proj's output, and its column sums: proj's bias gradient
             dy2, cs = _branch_grad(dy2, None, 1, ctx.drop, projb is not None and ctx.needs_input_grad[4])
             projb_done = (_bgrad_from(projb, cs) if cs is not None else None,)
-        dx, g = _attn_bwd(dy2, x2, (qkv, o, lse), B, N, H, c(qkvw), c(projw), qkvw, qkvb, projw, projb, ctx.needs_input_grad[1:5], tp,
-                          projb_done=projb_done)
-        return (_ret_grad(dx.view(B, N, -1), in_dtype),) + g + (None, None, None, None)
+        dx, g, *gq = _attn_bwd(dy2, x2, (qkv, o, lse, sqk, mqk, rqk), B, N, H, c(qkvw), c(projw), qkvw, qkvb, projw, projb,
+                               ctx.needs_input_grad[1:5], tp, projb_done=projb_done, qkn=qkn, qkn_needs=ctx.needs_input_grad[9:13])
+        return (_ret_grad(dx.view(B, N, -1), in_dtype),) + g + (None, None, None, None) + (gq[0] if gq else (None,) * 4) + (None, None)
 
 
 class MlpFn(torch.autograd.Function):
@@ -669,14 +731,16 @@ class BlockFn(torch.autograd.Function):
     backward.  With a scale a branch costs one row pass more forward (drop_path_add) and one backward (drop_path_scale)."""
 
     @staticmethod
-    def _run_forward(x2, B, N, num_heads, eps, c, params, tp, s1=None, s2=None, sites=(None, None, None), g1=None, g2=None, keep=False):
-        """g1, g2: the LayerScale gammas of the two branches or None; keep: their unscaled branch outputs b1, b2 are kept for backward"""
+    def _run_forward(x2, B, N, num_heads, eps, c, params, tp, s1=None, s2=None, sites=(None, None, None), g1=None, g2=None, keep=False,
+                     qkn=None):
+        """g1, g2: the LayerScale gammas of the two branches or None; keep: their unscaled branch outputs b1, b2 are kept for backward, and
+        with qkn (see _attn_fwd) the un-normalised Q and K and their statistics"""
         n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b = params
         dproj, d1, d2 = sites
         plain1, plain2 = s1 is None and dproj is None and g1 is None, s2 is None and d2 is None and g2 is None
         b1 = b2 = None
         ln1, mean1, rstd1 = ops.layernorm_fwd(x2, c(n1w), c(n1b), eps)
-        x1, sa = _attn_fwd(ln1, B, N, num_heads, c(qkvw), c(qkvb), c(projw), c(projb), x2 if plain1 else None, tp)
+        x1, sa = _attn_fwd(ln1, B, N, num_heads, c(qkvw), c(qkvb), c(projw), c(projb), x2 if plain1 else None, tp, qkn, keep)
         if g1 is not None:
             b1 = x1 if keep else None
             x1 = _ls_branch_exit(x2, x1, g1, s1, N, dproj, keep)            # x1 = x + s1 ⊙ m ⊙ (gamma1 ⊙ branch) / keep
@@ -693,8 +757,12 @@ class BlockFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b, num_heads, eps, cdtype, tp=None, recompute=False,
-                s1=None, s2=None, drop=None, gamma1=None, gamma2=None, save_branch=None):
+                s1=None, s2=None, drop=None, gamma1=None, gamma2=None, save_branch=None, qnw=None, qnb=None, knw=None, knb=None, qk_eps=None):
         """s1, s2: the per-sample drop-path scales of the attention and the MLP branch (fp32 [B]); None = no drop path on that branch.
+        qnw, qnb, knw, knb, qk_eps: the weight and bias of attn.q_norm / attn.k_norm (fp32 [head_dim]) and their eps, or None (no qk_norm:
+        the launches of a Block without it).  One row pass over the qkv buffer forward, one over its gradient backward; when a gradient is
+        wanted (save_branch) the un-normalised Q and K are kept: two more D-wide token matrices per Block, none under recompute, whose
+        rebuilt forward gives the same bits.
         gamma1, gamma2: the LayerScale parameters of the two branches (fp32 [D], ls1.gamma / ls2.gamma) or None.  A branch with a gamma runs
         its exit GEMM without the residual and ops.layer_scale_add writes res + s ⊙ m ⊙ (gamma ⊙ branch) / keep; when a gradient is wanted
         the sum goes to a new buffer and the unscaled branch output is saved (two more token matrices per Block), else it overwrites the
@@ -713,6 +781,9 @@ class BlockFn(torch.autograd.Function):
         the scales are kept with the input, so the rebuilt forward uses the same draw."""
         _refuse_group_drop_path(tp, s1, s2)
         _refuse_group_layer_scale(tp, gamma1, gamma2)
+        qkn = _qkn_of(qnw, qnb, knw, knb, qk_eps)
+        _refuse_group_qk_norm(tp, qkn)
+        ctx.qk_eps = qk_eps
         ctx.sites = sites = _block_sites(drop, tp, 1)
         xin = _as(x, cdtype)
         B, N, D = xin.shape
@@ -720,11 +791,11 @@ class BlockFn(torch.autograd.Function):
         c = lambda p: compute_param(p, cdtype)
         params = (n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b)
         keep = not recompute and any(ctx.needs_input_grad) and (save_branch is None or bool(save_branch))
-        y, saved = BlockFn._run_forward(x2, B, N, num_heads, eps, c, params, tp, s1, s2, sites, gamma1, gamma2, keep)
+        y, saved = BlockFn._run_forward(x2, B, N, num_heads, eps, c, params, tp, s1, s2, sites, gamma1, gamma2, keep, qkn)
         if recompute:
-            ctx.save_for_backward(x2, *params, s1, s2, gamma1, gamma2)
+            ctx.save_for_backward(x2, *params, s1, s2, gamma1, gamma2, qnw, qnb, knw, knb)
         else:
-            ctx.save_for_backward(x2, *saved, *params, s1, s2, gamma1, gamma2)
+            ctx.save_for_backward(x2, *saved, *params, s1, s2, gamma1, gamma2, qnw, qnb, knw, knb)
         ctx.meta = (B, N, num_heads, cdtype, x.dtype, tp)
         ctx.recompute, ctx.eps = recompute, eps
         return y.view(B, N, D)
@@ -734,13 +805,15 @@ class BlockFn(torch.autograd.Function):
         B, N, H, cdtype, in_dtype, tp = ctx.meta
         c = lambda p: compute_param(p, cdtype)
         if ctx.recompute:
-            x2, *params, s1, s2, g1, g2 = ctx.saved_tensors
-            _, saved = BlockFn._run_forward(x2, B, N, H, ctx.eps, c, tuple(params), tp, s1, s2, ctx.sites, g1, g2, True)
-            (mean1, rstd1, ln1, qkv, o, lse, x1, mean2, rstd2, ln2, h, a, b1, b2) = saved
+            x2, *params, s1, s2, g1, g2, qnw, qnb, knw, knb = ctx.saved_tensors
+            _, saved = BlockFn._run_forward(x2, B, N, H, ctx.eps, c, tuple(params), tp, s1, s2, ctx.sites, g1, g2, True,
+                                            _qkn_of(qnw, qnb, knw, knb, ctx.qk_eps))
+            (mean1, rstd1, ln1, qkv, o, lse, sqk, mqk, rqk, x1, mean2, rstd2, ln2, h, a, b1, b2) = saved
             n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b = params
         else:
-            (x2, mean1, rstd1, ln1, qkv, o, lse, x1, mean2, rstd2, ln2, h, a, b1, b2,
-             n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b, s1, s2, g1, g2) = ctx.saved_tensors
+            (x2, mean1, rstd1, ln1, qkv, o, lse, sqk, mqk, rqk, x1, mean2, rstd2, ln2, h, a, b1, b2,
+             n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b, s1, s2, g1, g2, qnw, qnb, knw, knb) = ctx.saved_tensors
+        qkn = _qkn_of(qnw, qnb, knw, knb, ctx.qk_eps)
         need = ctx.needs_input_grad
         dproj, d1, d2 = ctx.sites
         dy2 = _as(dy, cdtype).reshape(x2.shape)
@@ -775,15 +848,16 @@ class BlockFn(torch.autograd.Function):
             # asked for any
             dt1, cs1 = _branch_grad(dx1, s1, N, dproj, projb is not None and need[6])
             projb_done = (_bgrad_from(projb, cs1) if cs1 is not None else None,)
-        dln1, ga = _attn_bwd(dt1, ln1, (qkv, o, lse), B, N, H, c(qkvw), c(projw), qkvw, qkvb, projw, projb, need[3:7], tp, wq,
-                             projb_done=projb_done)
+        dln1, ga, *gq = _attn_bwd(dt1, ln1, (qkv, o, lse, sqk, mqk, rqk), B, N, H, c(qkvw), c(projw), qkvw, qkvb, projw, projb, need[3:7], tp,
+                                  wq, projb_done=projb_done, qkn=qkn, qkn_needs=need[24:28])
         # ... and, published for whoever receives dx, the fc2 bias gradient of the Block before this one
         cs0 = torch.empty(x2.shape[1], dtype=torch.float32, device=dy2.device) if _BIAS_FROM_EPILOGUE else None
         dx, g_n1w, g_n1b = _ln_bwd(dln1, x2, c(n1w), mean1, rstd1, n1w, n1b, dres=dx1, dx_colsum=cs0)
         if cs0 is not None and in_dtype == cdtype:
             _publish_stream_colsum(wq, dx, cs0)
         wq.end_block()                                   # the Block's 4 weight gradients: grouped launch now, or with the next Blocks'
-        return (_ret_grad(dx.view(B, N, -1), in_dtype), g_n1w, g_n1b) + ga + (g_n2w, g_n2b) + gm + (None,) * 8 + (g_g1, g_g2, None)
+        return ((_ret_grad(dx.view(B, N, -1), in_dtype), g_n1w, g_n1b) + ga + (g_n2w, g_n2b) + gm + (None,) * 8 + (g_g1, g_g2, None)
+                + (gq[0] if gq else (None,) * 4) + (None,))
 
 
 TAIL_ROWS = os.environ.get("UCFVIT_TAIL_ROWS", "1") != "0"     # A/B switch: 0 = the last Block runs dense like every other
@@ -800,7 +874,7 @@ class TailBlockFn(torch.autograd.Function):
     backward (dres_period = N), rounded once like the dense Block's."""
 
     @staticmethod
-    def _run_forward(x2, B, N, num_heads, eps, c, params, s1=None, s2=None, sites=(None, None, None), g1=None, g2=None, keep=False):
+    def _run_forward(x2, B, N, num_heads, eps, c, params, s1=None, s2=None, sites=(None, None, None), g1=None, g2=None, keep=False, qkn=None):
         n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b = params
         dproj, d1, d2 = sites
         plain1, plain2 = s1 is None and dproj is None and g1 is None, s2 is None and d2 is None and g2 is None
@@ -809,6 +883,9 @@ class TailBlockFn(torch.autograd.Function):
         dh = D // num_heads
         ln1, mean1, rstd1 = ops.layernorm_fwd(x2, c(n1w), c(n1b), eps)
         qkv = ops.linear_fwd(ln1, c(qkvw), c(qkvb))
+        sq = (None, None, None)
+        if qkn is not None:                                                          # the whole buffer: the class rows' queries need every key
+            sq = ops.qk_norm_fwd(qkv, qkn[0], qkn[1], qkn[2], qkn[3], num_heads, dh, qkn[4], save=keep)
         o, lse = ops.attention_rows_fwd(qkv, B, N, num_heads, dh, dh ** -0.5, 0)
         xc = x2.view(B, N, D)[:, 0]                                                  # class rows of the stream: a [B, D] view, row stride N D
         x1 = ops.linear_fwd(o, c(projw), c(projb), residual=xc if plain1 else None)
@@ -824,27 +901,30 @@ class TailBlockFn(torch.autograd.Function):
             y = _ls_branch_exit(x1, y, g2, s2, 1, d2, keep)
         elif not plain2:
             _branch_exit(x1, y, s2, 1, d2)
-        return y, (mean1, rstd1, ln1, qkv, o, lse, x1, mean2, rstd2, ln2, h, a, b1, b2)
+        return y, (mean1, rstd1, ln1, qkv, o, lse, *sq, x1, mean2, rstd2, ln2, h, a, b1, b2)
 
     @staticmethod
     def forward(ctx, x, n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b, num_heads, eps, cdtype, recompute=False,
-                s1=None, s2=None, drop=None, gamma1=None, gamma2=None, save_branch=None):
+                s1=None, s2=None, drop=None, gamma1=None, gamma2=None, save_branch=None, qnw=None, qnb=None, knw=None, knb=None, qk_eps=None):
         """recompute: as in BlockFn, only the Block's input is kept and backward re-runs the forward launches (bit-identical);
+        qnw, qnb, knw, knb, qk_eps: qk_norm as in BlockFn; the whole qkv buffer is normalised (every key is needed), then the class rows run;
         gamma1, gamma2, save_branch: the LayerScale parameters and the grad-mode flag as in BlockFn, applied to the class rows;
         s1, s2: the drop-path scales of the two branches as in BlockFn, one row per sample from the attention on;
         drop: BlockFn's dropout argument; the mask index steps by N rows, so class row b draws the mask of row b N of the dense Block"""
         xin = _as(x, cdtype)
         B, N, D = xin.shape
         ctx.sites = sites = _block_sites(drop, None, N)
+        qkn = _qkn_of(qnw, qnb, knw, knb, qk_eps)
+        ctx.qk_eps = qk_eps
         x2 = xin.view(B * N, D)
         c = lambda p: compute_param(p, cdtype)
         params = (n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b)
         keep = not recompute and any(ctx.needs_input_grad) and (save_branch is None or bool(save_branch))
-        y, saved = TailBlockFn._run_forward(x2, B, N, num_heads, eps, c, params, s1, s2, sites, gamma1, gamma2, keep)
+        y, saved = TailBlockFn._run_forward(x2, B, N, num_heads, eps, c, params, s1, s2, sites, gamma1, gamma2, keep, qkn)
         if recompute:
-            ctx.save_for_backward(x2, *params, s1, s2, gamma1, gamma2)
+            ctx.save_for_backward(x2, *params, s1, s2, gamma1, gamma2, qnw, qnb, knw, knb)
         else:
-            ctx.save_for_backward(x2, *saved, *params, s1, s2, gamma1, gamma2)
+            ctx.save_for_backward(x2, *saved, *params, s1, s2, gamma1, gamma2, qnw, qnb, knw, knb)
         ctx.meta = (B, N, num_heads, cdtype, x.dtype)
         ctx.recompute, ctx.eps = recompute, eps
         return y
@@ -854,13 +934,16 @@ class TailBlockFn(torch.autograd.Function):
         B, N, H, cdtype, in_dtype = ctx.meta
         c = lambda p: compute_param(p, cdtype)
         if ctx.recompute:
-            x2, *params, s1, s2, g1, g2 = ctx.saved_tensors
-            _, saved = TailBlockFn._run_forward(x2, B, N, H, ctx.eps, c, tuple(params), s1, s2, ctx.sites, g1, g2, True)
-            (mean1, rstd1, ln1, qkv, o, lse, x1, mean2, rstd2, ln2, h, a, b1, b2) = saved
+            x2, *params, s1, s2, g1, g2, qnw, qnb, knw, knb = ctx.saved_tensors
+            _, saved = TailBlockFn._run_forward(x2, B, N, H, ctx.eps, c, tuple(params), s1, s2, ctx.sites, g1, g2, True,
+                                                _qkn_of(qnw, qnb, knw, knb, ctx.qk_eps))
+            (mean1, rstd1, ln1, qkv, o, lse, sqk, mqk, rqk, x1, mean2, rstd2, ln2, h, a, b1, b2) = saved
             n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b = params
         else:
-            (x2, mean1, rstd1, ln1, qkv, o, lse, x1, mean2, rstd2, ln2, h, a, b1, b2,
-             n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b, s1, s2, g1, g2) = ctx.saved_tensors
+            (x2, mean1, rstd1, ln1, qkv, o, lse, sqk, mqk, rqk, x1, mean2, rstd2, ln2, h, a, b1, b2,
+             n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b, s1, s2, g1, g2, qnw, qnb, knw, knb) = ctx.saved_tensors
+        qkn = _qkn_of(qnw, qnb, knw, knb, ctx.qk_eps)
+        g_qkn = (None,) * 4
         need = ctx.needs_input_grad
         D = x2.shape[1]
         dh = D // H
@@ -892,7 +975,16 @@ class TailBlockFn(torch.autograd.Function):
             g_projb = _bgrad_from(projb, cs1) if cs1 is not None else None
         g_projw = _wgrad(projw, dt1, o, wq) if need[5] else None
         want_b = qkvb is not None and need[4]
-        if want_b:
+        if qkn is not None:
+            # as in _attn_bwd: the Q and K thirds of the bias gradient are the column sums of what qk_norm_bwd writes, the V third those of dO
+            gb, acc = grad_target(qkvb) if want_b else (None, False)
+            if want_b and gb is None:
+                gb, acc = torch.empty(3 * D, dtype=torch.float32, device=dy2.device), False
+            do = _dgrad(dt1, projw, c(projw), c_colsum=gb[2 * D:] if want_b else None, c_colsum_accumulate=acc)
+            dqkv = ops.attention_rows_bwd(qkv, o, do, lse, B, N, H, dh, dh ** -0.5, 0)
+            g_qkn = _qkn_bwd(dqkv, (sqk, mqk, rqk), qkn, H, dh, need[23:27], gb[:2 * D] if want_b else None, acc)
+            g_qkvb = (None if acc else gb) if want_b else None
+        elif want_b:
             # Q third: dq of every image, summed; K third: 0 exactly; V third: the column sums of the compact dO (see _attn_bwd)
             gb, acc = grad_target(qkvb)
             if gb is None:
@@ -912,7 +1004,8 @@ class TailBlockFn(torch.autograd.Function):
         if cs0 is not None and in_dtype == cdtype:
             _publish_stream_colsum(wq, dx, cs0)           # the fc2 bias gradient of the Block before this one
         wq.end_block()
-        return (_ret_grad(dx.view(B, N, D), in_dtype), g_n1w, g_n1b, g_qkvw, g_qkvb, g_projw, g_projb, g_n2w, g_n2b) + gm + (None,) * 7 + (g_g1, g_g2, None)
+        return ((_ret_grad(dx.view(B, N, D), in_dtype), g_n1w, g_n1b, g_qkvw, g_qkvb, g_projw, g_projb, g_n2w, g_n2b) + gm + (None,) * 7
+                + (g_g1, g_g2, None) + g_qkn + (None,))
 
 
 class PatchEmbedFn(torch.autograd.Function):

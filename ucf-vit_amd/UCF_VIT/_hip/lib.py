@@ -154,6 +154,9 @@ SIGNATURES = {
     "ucfvit_dropout_add": (c_int, [_P, _I64, _P, _P, _P, _I64, _I64, _I64, _I64, _D, c_uint64, _I, _P]),
     "ucfvit_layer_scale_add": (c_int, [_P, _I64, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _D, c_uint64, _I, _P]),
     "ucfvit_layer_scale_grad": (c_int, [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _D, c_uint64, _I, _P]),
+    "ucfvit_qk_norm_partial_rows": (c_int64, [_I64, _I64, _I64]),
+    "ucfvit_qk_norm_fwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _F, _I, _P]),
+    "ucfvit_qk_norm_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I, _P]),
 }
 
 _lib = None

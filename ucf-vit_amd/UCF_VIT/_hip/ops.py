@@ -1650,6 +1650,82 @@ def layer_scale_grad(dy, branch, gamma, s=None, rows_per_sample=1, p=0.0, seed=0
     return out
 
 
+# ------------------------------------------------------------------------------------------------ QK-norm
+def _chk_qk_norm(t, rows, H, dh, params, name):
+    _chk(t, name + ".qkv")
+    if t.dim() != 2 or t.shape[1] != 3 * H * dh or H < 1:
+        raise TypeError(f"{name}: qkv must be [rows, 3 H dh] = [rows, {3 * H * dh}], got {tuple(t.shape)}")
+    if dh not in (32, 64, 128):
+        raise ValueError(f"{name}: head width dh={dh} is not one of 32, 64, 128")
+    for i, p in enumerate(params):
+        _chk(p, f"{name}.param{i}")
+        if p.dtype != torch.float32 or p.numel() != dh:
+            raise TypeError(f"{name}: the q_norm / k_norm parameters must be contiguous fp32 tensors of dh = {dh} elements (the master parameters)")
+
+
+def qk_norm_fwd(qkv, gamma_q, beta_q, gamma_k, beta_k, H, dh, eps, save=True):
+    """LayerNorm over the dh elements of every (row, head) segment of the Q third (gamma_q, beta_q) and of the K third (gamma_k, beta_k) of
+    qkv [rows, 3 H dh], IN PLACE (the packed layout the attention entry points take); the V third is not touched.  The parameters are fp32
+    [dh].  -> (saved_qk [rows, 2 H dh] = the un-normalised Q and K, mean, rstd fp32 [rows, 2 H]) with save, else (None, None, None)."""
+    L = _l.load()
+    rows = qkv.shape[0]
+    _chk_qk_norm(qkv, rows, H, dh, (gamma_q, beta_q, gamma_k, beta_k), "qk_norm_fwd")
+    saved = mean = rstd = None
+    if save:
+        saved = torch.empty((rows, 2 * H * dh), dtype=qkv.dtype, device=qkv.device)
+        mean = torch.empty((rows, 2 * H), dtype=torch.float32, device=qkv.device)
+        rstd = torch.empty((rows, 2 * H), dtype=torch.float32, device=qkv.device)
+    if rows == 0:                                                      # (an empty tensor has no address to hand over)
+        return saved, mean, rstd
+    _l.check(L.ucfvit_qk_norm_fwd(qkv.data_ptr(), gamma_q.data_ptr(), beta_q.data_ptr(), gamma_k.data_ptr(), beta_k.data_ptr(), _p(saved),
+                                  _p(mean), _p(rstd), rows, H, dh, float(eps), dt(qkv), _stream()), "ucfvit_qk_norm_fwd")
+    return saved, mean, rstd
+
+
+def qk_norm_bwd(dqkv, saved_qk, gamma_q, gamma_k, mean, rstd, H, dh, param_grads=None, param_accumulate=False, c_colsum=None,
+                c_colsum_accumulate=False):
+    """rewrites the Q and K thirds of dqkv [rows, 3 H dh] IN PLACE from the gradient of the normalised values to the gradient of the qkv
+    Linear's output (the V third stays).  param_grads: optional fp32 [4, dh] that receives (+)= dgamma_q, dbeta_q, dgamma_k, dbeta_k (sums
+    over rows and heads); c_colsum: optional fp32 [2 H dh] that receives (+)= the column sums of the new Q and K thirds, taken before
+    rounding (the Q and K thirds of the qkv bias gradient).  Partial sums per row chunk from the kernel, folded by ucfvit_reduce_rows."""
+    L = _l.load()
+    rows = dqkv.shape[0]
+    _chk_qk_norm(dqkv, rows, H, dh, (gamma_q, gamma_k), "qk_norm_bwd")
+    _chk(saved_qk, "qk_norm_bwd.saved_qk")
+    if tuple(saved_qk.shape) != (rows, 2 * H * dh) or saved_qk.dtype != dqkv.dtype:
+        raise TypeError("qk_norm_bwd: saved_qk must be [rows, 2 H dh] of dqkv's dtype")
+    for t, nm in ((mean, "mean"), (rstd, "rstd")):
+        _chk(t, "qk_norm_bwd." + nm)
+        if t.dtype != torch.float32 or t.numel() != rows * 2 * H:
+            raise TypeError(f"qk_norm_bwd: {nm} must be fp32 [rows, 2 H]")
+    R, pp, cp = 0, None, None
+    if rows == 0:
+        if param_grads is not None or c_colsum is not None:
+            raise ValueError("qk_norm_bwd: no sums of an empty input")
+        return dqkv
+    if param_grads is not None or c_colsum is not None:
+        if param_grads is not None and (_chk(param_grads, "qk_norm_bwd.param_grads").dtype != torch.float32 or param_grads.numel() != 4 * dh):
+            raise TypeError("qk_norm_bwd: param_grads must be a contiguous fp32 tensor of 4 dh elements")
+        if c_colsum is not None and (_chk(c_colsum, "qk_norm_bwd.c_colsum").dtype != torch.float32 or c_colsum.numel() != 2 * H * dh):
+            raise TypeError("qk_norm_bwd: c_colsum must be a contiguous fp32 tensor of 2 H dh elements")
+        R = L.ucfvit_qk_norm_partial_rows(rows, H, dh)
+        if R <= 0:
+            raise ValueError("qk_norm_bwd: no sums of an empty input")
+        np_, nc = R * 4 * dh, R * 2 * H * dh
+        ws = workspace((np_ + nc) * 4, dqkv.device)
+        pp = ws[:np_] if param_grads is not None else None
+        cp = ws[np_:np_ + nc] if c_colsum is not None else None
+    _l.check(L.ucfvit_qk_norm_bwd(dqkv.data_ptr(), saved_qk.data_ptr(), gamma_q.data_ptr(), gamma_k.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                                  _p(pp), _p(cp), rows, H, dh, dt(dqkv), _stream()), "ucfvit_qk_norm_bwd")
+    if pp is not None:
+        _l.check(L.ucfvit_reduce_rows(pp.data_ptr(), param_grads.data_ptr(), R, 4 * dh, 1 if param_accumulate else 0, _stream()),
+                 "ucfvit_reduce_rows")
+    if cp is not None:
+        _l.check(L.ucfvit_reduce_rows(cp.data_ptr(), c_colsum.data_ptr(), R, 2 * H * dh, 1 if c_colsum_accumulate else 0, _stream()),
+                 "ucfvit_reduce_rows")
+    return dqkv
+
+
 def transpose_batched(src_flat, dst_flat, table, n_mats, total_tiles):
     L = _l.load()
     _l.check(L.ucfvit_transpose_batched(src_flat.data_ptr(), dst_flat.data_ptr(), table.data_ptr(), n_mats, total_tiles, _stream()),

@@ -16,7 +16,7 @@ import torch.nn as nn
 from UCF_VIT.simple.building_blocks import (  # noqa: F401  (re-exported operator set)
     PatchEmbed, LayerNorm, Linear, DropPath, HipDropout, LayerScale, PatchDropout, MyUnetBlock, EmbeddingDenseLayer,
     VariableMapping_Attention, to_2tuple, to_3tuple, trunc_normal_, get_act_layer, get_norm_layer, LayerType,
-    set_compute_dtype, _cd, _no_dropout, _assert, _draw_drop_path, _draw_dropout, _block_dropout, _block_gammas)
+    set_compute_dtype, _cd, _no_dropout, _assert, _draw_drop_path, _draw_dropout, _block_dropout, _block_gammas, _qk_norm_problem, _qk_norm_args)
 from UCF_VIT.simple import building_blocks as _S
 from UCF_VIT.utils.fused_attn import FusedAttn
 from UCF_VIT._hip import functional as HF
@@ -71,6 +71,10 @@ class Attention(nn.Module):
         self.scale = self.head_dim ** -0.5
         self.fused_attn = fused_attn
         self.tensor_par_size, self.tensor_par_group = tensor_par_size, tensor_par_group
+        if qk_norm and tensor_par_size > 1:
+            raise NotImplementedError(f"Attention(qk_norm=True) under a tensor-parallel group (tensor_par_group={tensor_par_group!r}, "
+                                      f"tensor_par_size={tensor_par_size}): the heads are sharded and the [head_dim] parameters replicated, so "
+                                      "their gradient would have to be summed over the group; not implemented")
         self.qkv = nn.Linear(dim, dim * 3 // tensor_par_size, bias=qkv_bias)
         self.q_norm = norm_layer(self.head_dim) if qk_norm else nn.Identity()
         self.k_norm = norm_layer(self.head_dim) if qk_norm else nn.Identity()
@@ -80,15 +84,16 @@ class Attention(nn.Module):
         _mark_sharded(self, tensor_par_size)
 
     def _fusable(self):
-        return isinstance(self.q_norm, nn.Identity) and isinstance(self.k_norm, nn.Identity)
+        return _qk_norm_problem(self) is None
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         _no_dropout(self.attn_drop.p, self.training, "attn_drop")
-        if not self._fusable():
-            raise NotImplementedError("qk_norm=True is not on the HIP hot path; reference configs use qk_norm=False")
+        qk = _qk_norm_args(self)                                       # raises for norms the hot path does not run, and under a group
         args = (x, self.qkv.weight, self.qkv.bias, self.proj.weight, self.proj.bias, self.num_heads, _cd(self),
                 _tp(self.tensor_par_size, self.tensor_par_group))
         d = _draw_dropout(self.proj_drop)
+        if qk:
+            return HF.AttentionFn.apply(*args, d, *qk, torch.is_grad_enabled())
         return HF.AttentionFn.apply(*args) if d is None else HF.AttentionFn.apply(*args, d)     # refused under a group (HF._site)
 
 
@@ -138,8 +143,9 @@ class Block(nn.Module):
             s1, s2 = _draw_drop_path(self.drop_path1, x), _draw_drop_path(self.drop_path2, x)      # None under a tensor-parallel group
             drop = _block_dropout(a, m)
             g1, g2 = _block_gammas(self)                                                           # None under a tensor-parallel group
-            if g1 is not None:
-                return HF.BlockFn.apply(*args, s1, s2, drop, g1, g2, torch.is_grad_enabled())
+            qk = _qk_norm_args(a)                                                                  # refused under a tensor-parallel group
+            if g1 is not None or qk:
+                return HF.BlockFn.apply(*args, s1, s2, drop, g1, g2, torch.is_grad_enabled(), *qk)
             if s1 is None and s2 is None and drop is None:
                 return HF.BlockFn.apply(*args)
             return HF.BlockFn.apply(*args, s1, s2, drop)

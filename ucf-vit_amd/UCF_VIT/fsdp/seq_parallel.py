@@ -299,6 +299,11 @@ class SeqParallelBlock(nn.Module):
                 raise NotImplementedError(f"Block(init_values=...) under a sequence-parallel group of {self.spg.size} ranks "
                                           f"(group {getattr(self.spg, 'sp_group', None)!r}): the gradient of LayerScale's gamma would need a sum over the "
                                           "group; not implemented")
+        attn = getattr(block, "attn", None)
+        if attn is not None and not isinstance(getattr(attn, "q_norm", nn.Identity()), nn.Identity):
+            raise NotImplementedError(f"Block(qk_norm=True) under a sequence-parallel group of {self.spg.size} ranks "
+                                      f"(group {getattr(self.spg, 'sp_group', None)!r}): the heads are sharded over the group and the gradient of "
+                                      "the [head_dim] parameters would need a sum over it; not implemented")
         for p in block.parameters():
             p._ucf_sharded = "sequence"     # gradients are per-token-shard partial sums: HipGradScaler refuses a per-rank skip decision
 

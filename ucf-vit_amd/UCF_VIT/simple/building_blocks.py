@@ -195,6 +195,40 @@ def _block_gammas(block):
     return None, None
 
 
+def _qk_norm_problem(attn):
+    """None when attn.q_norm / attn.k_norm are something the HIP hot path runs (both Identity, or both a plain affine LayerNorm over
+    head_dim with one eps), else the condition that failed"""
+    q, k = attn.q_norm, attn.k_norm
+    if isinstance(q, nn.Identity) and isinstance(k, nn.Identity):
+        return None
+    for name, m in (("q_norm", q), ("k_norm", k)):
+        if not isinstance(m, nn.LayerNorm):
+            return f"{name} is {type(m).__name__}; the HIP hot path runs nn.Identity or nn.LayerNorm (both norms alike)"
+        if tuple(m.normalized_shape) != (attn.head_dim,):
+            return f"{name} normalises over {tuple(m.normalized_shape)}, not over (head_dim,) = ({attn.head_dim},)"
+        if not m.elementwise_affine or m.weight is None or m.bias is None:
+            return f"{name} has no affine weight and bias"
+    if q.eps != k.eps:
+        return f"q_norm.eps = {q.eps} differs from k_norm.eps = {k.eps}"
+    return None
+
+
+def _qk_norm_args(attn):
+    """the trailing arguments of the fused Functions: (q_norm.weight, q_norm.bias, k_norm.weight, k_norm.bias, eps), or () without qk_norm;
+    raises with the failed condition for norms the hot path does not run"""
+    why = _qk_norm_problem(attn)
+    if why is not None:
+        raise NotImplementedError(f"qk_norm is not on the HIP hot path for this Attention: {why}")
+    if isinstance(attn.q_norm, nn.Identity):
+        return ()
+    tps = getattr(attn, "tensor_par_size", 1)
+    if tps > 1:
+        raise NotImplementedError(f"Attention(qk_norm=True) under a tensor-parallel group (tensor_par_group={getattr(attn, 'tensor_par_group', None)!r}, "
+                                  f"tensor_par_size={tps}): the heads are sharded and the [head_dim] parameters replicated, so their gradient "
+                                  "would have to be summed over the group; not implemented")
+    return (attn.q_norm.weight, attn.q_norm.bias, attn.k_norm.weight, attn.k_norm.bias, attn.q_norm.eps)
+
+
 class PatchDropout(nn.Module):
     def __init__(self, prob=0.0, num_prefix_tokens=1):
         super().__init__()
@@ -278,7 +312,10 @@ class Mlp(nn.Module):
 
 
 class Attention(nn.Module):
-    """Multi-head self-attention; every FusedAttn member runs the fused gfx950 kernel (see utils/fused_attn.py)."""
+    """Multi-head self-attention; every FusedAttn member runs the fused gfx950 kernel (see utils/fused_attn.py).  qk_norm: q_norm / k_norm
+    are norm_layer(head_dim) (LayerNorm; eps 1e-5 for a bare Attention, the Block's norm_layer eps inside a Block) and one row pass over the
+    qkv buffer normalises Q and K per head before the attention kernels (HF.AttentionFn); training keeps the un-normalised Q and K for
+    backward, two more D-wide token matrices."""
 
     def __init__(self, dim: int, fused_attn: FusedAttn = FusedAttn.NONE, num_heads: int = 8, qkv_bias: bool = False,
                  qk_norm: bool = False, attn_drop: float = 0.0, proj_drop: float = 0.0, norm_layer: nn.Module = nn.LayerNorm) -> None:
@@ -296,14 +333,15 @@ class Attention(nn.Module):
         self.proj_drop = HipDropout(proj_drop)
 
     def _fusable(self):
-        return isinstance(self.q_norm, nn.Identity) and isinstance(self.k_norm, nn.Identity)
+        return _qk_norm_problem(self) is None
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         _no_dropout(self.attn_drop.p, self.training, "attn_drop")
-        if not self._fusable():
-            raise NotImplementedError("qk_norm=True is not on the HIP hot path; reference configs use qk_norm=False")
+        qk = _qk_norm_args(self)                                       # raises, naming the condition, for norms the hot path does not run
         args = (x, self.qkv.weight, self.qkv.bias, self.proj.weight, self.proj.bias, self.num_heads, _cd(self))
         d = _draw_dropout(self.proj_drop)
+        if qk:
+            return HF.AttentionFn.apply(*args, None, d, *qk, torch.is_grad_enabled())
         return HF.AttentionFn.apply(*args) if d is None else HF.AttentionFn.apply(*args, None, d)
 
 
@@ -313,7 +351,9 @@ class Block(nn.Module):
     draw their per-sample scales and the node applies them (one row pass per branch and direction); proj_drop > 0 in training: the
     three HipDropout modules draw their seeds and the same row passes apply the masks (plus one pass over the activation).  Eval or
     rates 0 run the very launches of a Block without either.  init_values: ls1 / ls2 are LayerScale modules and the node folds their
-    gammas into the same row passes (a branch with a gamma always takes one); without it the launches are those of a Block without."""
+    gammas into the same row passes (a branch with a gamma always takes one); without it the launches are those of a Block without.
+    qk_norm: attn.q_norm / attn.k_norm are norm_layer(head_dim) and the node runs one row pass over the qkv buffer per direction
+    (ops.qk_norm_fwd / qk_norm_bwd); it acts inside the branch, so it composes with the three options above, which act at its exit."""
 
     def __init__(self, dim: int, num_heads: int, fused_attn: FusedAttn = FusedAttn.NONE, mlp_ratio: float = 4.0,
                  qkv_bias: bool = False, qk_norm: bool = False, proj_drop: float = 0.0, attn_drop: float = 0.0,
@@ -350,8 +390,9 @@ class Block(nn.Module):
             s1, s2 = _draw_drop_path(self.drop_path1, x), _draw_drop_path(self.drop_path2, x)      # two independent draws, s1 first
             drop = _block_dropout(a, m)
             g1, g2 = _block_gammas(self)
-            if g1 is not None:
-                return HF.BlockFn.apply(*args, s1, s2, drop, g1, g2, torch.is_grad_enabled())
+            qk = _qk_norm_args(a)
+            if g1 is not None or qk:
+                return HF.BlockFn.apply(*args, s1, s2, drop, g1, g2, torch.is_grad_enabled(), *qk)
             if s1 is None and s2 is None and drop is None:
                 return HF.BlockFn.apply(*args)
             return HF.BlockFn.apply(*args, s1, s2, drop)
@@ -369,8 +410,9 @@ class Block(nn.Module):
         s1, s2 = _draw_drop_path(self.drop_path1, x), _draw_drop_path(self.drop_path2, x)
         drop = _block_dropout(a, m)
         g1, g2 = _block_gammas(self)
-        if g1 is not None:
-            return HF.TailBlockFn.apply(*args, s1, s2, drop, g1, g2, torch.is_grad_enabled())
+        qk = _qk_norm_args(a)
+        if g1 is not None or qk:
+            return HF.TailBlockFn.apply(*args, s1, s2, drop, g1, g2, torch.is_grad_enabled(), *qk)
         if s1 is None and s2 is None and drop is None:
             return HF.TailBlockFn.apply(*args)
         return HF.TailBlockFn.apply(*args, s1, s2, drop)

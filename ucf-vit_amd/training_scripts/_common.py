@@ -46,6 +46,7 @@ def model_args(conf):
     adaptive = bool(a.get("adaptive_patching", False))
     return dict(img_size=a["tile_size"], patch_size=a["patch_size"], in_chans=chans, embed_dim=a["embed_dim"], depth=a["depth"],
                 num_heads=a["num_heads"], mlp_ratio=a["mlp_ratio"], drop_path_rate=a.get("drop_path", 0.0), init_values=a.get("init_values"),
+                qk_norm=bool(a.get("qk_norm", False)),
                 pos_drop_rate=a.get("pos_drop_rate", 0.0), proj_drop_rate=a.get("proj_drop_rate", 0.0), twoD=a["twoD"],
                 default_vars=a["default_vars"], single_channel=d.get("single_channel", False), use_varemb=bool(a.get("use_varemb", False)),
                 adaptive_patching=adaptive, fixed_length=a.get("fixed_length", 4096),
