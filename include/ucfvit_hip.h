@@ -658,6 +658,47 @@ int ucfvit_pad_channels8(const float* src, void* dst, int64_t B, int64_t C, int6
 int ucfvit_pad_rows8(const void* src, int src_dtype, void* dst, int64_t V, int64_t C, int64_t ld, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
+ * UNETR convolutional decoder in the plane (csrc/conv2d.hip).  Reference call sites: src/UCF_VIT/simple/arch.py:794-797 — with twoD the
+ * monai blocks are built with spatial_dims = 2: chains of Conv2d(kernel 3, stride 1, padding 1, no bias) and ConvTranspose2d(kernel 2,
+ * stride 2, no bias).  Activations are channels-last bf16 [B][X][Y][C] (= torch.channels_last memory of a [B, C, X, Y] tensor).  Only the
+ * neighbourhood arithmetic is new: the pointwise layers (residual 1x1 projections, the output head, the transposed convolution's channel
+ * mixing x[V][Cin] * w[Cin][4 Cout]) are geometry-free and go through ucfvit_conv3d_fwd / _wgrad with ksize 1 over a factorisation of
+ * X Y; the instance-norm family, ucfvit_pad_channels8, ucfvit_pad_rows8 and ucfvit_dice_ce take [B][S][C] as they are.
+ *
+ * ucfvit_conv2d_fwd: y[p ldy + co] = bias[co] + sum_{tap, ci} w[co][ci][tap] x[p + tap - 1][ci] for co < cout_store: 3 x 3, stride 1,
+ *   padding 1, zero outside the image, tap = dx 3 + dy; implicit GEMM on mfma_f32_16x16x32_bf16 with fp32 accumulation, the input halo
+ *   staged in LDS.  Cin in {8, 16, 32 k}, Cout = 16 k = the rows of w_packed; the output contract is that of ucfvit_conv3d_fwd: out_dtype
+ *   bf16 or fp32, row stride ldy, cout_store <= Cout channels written, accumulate (y += result), bias fp32 [Cout] or NULL.  No statistics
+ *   epilogue: the norm statistics of the output come from ucfvit_instnorm_cl_stats.
+ *   w_packed (bf16) is the 3-D definition with 9 taps: with CPC = min(Cin, 32), TPS = 32 / CPC taps per step and NTS = ceil(9 / TPS) steps
+ *   per channel chunk, w_packed[cc][ts][co][kk] = w[co][cc CPC + kk % CPC][tap] for tap = ts TPS + kk / CPC (zero when tap >= 9).  The
+ *   data gradient is the same call on dy with the flipped, transposed weights.
+ * ucfvit_conv2d_wgrad: dw[tap][co][ci] = sum_p dy[p][co] x[p + tap - 1][ci] in fp32, written as
+ *   [Cout / (16 MB)][Cin / CPC][9][16 MB][max(CPC, 16)] with MB = 2 when Cout % 32 == 0, else 1 (ucfvit_conv2d_wgrad_size floats; for
+ *   CPC = 8 columns 8..15 are scratch).  workspace: ucfvit_conv2d_wgrad_workspace bytes (one partial per workgroup, folded in a fixed
+ *   order by ucfvit_reduce_rows: no atomics, the same bits on every call).  Both size queries return 0 for a shape the kernels refuse.
+ * Dispatch: conv2d_fwd_route() / conv2d_wgrad_route() in csrc/conv2d_route.h decide once per call which instantiation runs and with what
+ *   geometry; the size queries return fields of the same route and ucfvit_conv2d_route names it.
+ * ucfvit_conv2d_route: which kernel ucfvit_conv2d_fwd (pass = 0; the data gradient is the same call) or ucfvit_conv2d_wgrad (pass = 1,
+ *   which ignores has_bias, out_dtype, ldy and cout_store) would run for these arguments, as text: "tile2d cpc32 nb4 8x16 bf16 grid64x2"
+ *   (channels per chunk, 16-channel output blocks per workgroup, the tile in pixels, the output type, the grid) or
+ *   "wgrad2d cpc16 mb1 n_wg8 tiles_per_wg1 n_out2304".  Host only, no HIP call; returns the length (the text is cut to cap - 1 characters),
+ *   or < 0 for arguments the entry points refuse.
+ * ucfvit_depth_to_space2_2d: the shuffle behind the 2 x 2 stride-2 transposed convolution, cols [B Xi Yi][(dx, dy)][C] into
+ *   out [B][2 Xi][2 Yi][C] (to_space = 1) or its inverse (0), with the row stride ld_space and the fused skip copy of ucfvit_depth_to_space2.
+ * ------------------------------------------------------------------------------------------------------ */
+int ucfvit_conv2d_fwd(const void* x, const void* w_packed, const float* bias, void* y, int64_t B, int64_t X, int64_t Y, int64_t Cin, int64_t Cout,
+                      int64_t ldy, int64_t cout_store, int out_dtype, int accumulate, void* stream);
+int64_t ucfvit_conv2d_wgrad_size(int64_t Cin, int64_t Cout);
+int64_t ucfvit_conv2d_wgrad_workspace(int64_t B, int64_t X, int64_t Y, int64_t Cin, int64_t Cout);
+int ucfvit_conv2d_wgrad(const void* x, const void* dy, float* dw_packed, void* workspace, int64_t B, int64_t X, int64_t Y, int64_t Cin,
+                        int64_t Cout, void* stream);
+int ucfvit_conv2d_route(int pass, int64_t B, int64_t X, int64_t Y, int64_t Cin, int64_t Cout, int has_bias, int out_dtype, int64_t ldy,
+                        int64_t cout_store, char* out, int64_t cap);
+int ucfvit_depth_to_space2_2d(const void* src, void* dst, int64_t B, int64_t Xi, int64_t Yi, int64_t C, int64_t ld_space, int to_space,
+                              const void* skip, int64_t Cs, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------
  * UNETR decoder, align-corners trilinear resampling (csrc/resample.hip).  Reference call sites: src/UCF_VIT/simple/arch.py:887-906, 942-943,
  * 989-991 — when the token grid times 16 is not the tile size (patch 4 / adaptive patching), dec1 goes through
  * nn.Upsample(size=img_size, mode='trilinear', align_corners=True) before decoder2.  Channels-last bf16 [B][X][Y][Z][C], C % 8 == 0; every

@@ -13,7 +13,15 @@ absent from the build container: PARITY UNPINNED against it; tests/test_conv3d.p
   resample_trilinear(x, size)   nn.Upsample(size, mode='trilinear', align_corners=True) by csrc/resample.hip (gather-form backward)
   tconv1x1x1_resample(x, w, size)   decoder2 of a UNETR whose token grid times 16 is not the tile size: the two above, commuted
   instnorm_act_cl        InstanceNorm3d (+ residual) + LeakyReLU on the channels-last layout
+
+The 2-D decoder (reference: simple/arch.py:794-797, spatial_dims = 2 under twoD) runs on csrc/conv2d.hip over [B, X, Y, C]:
+  conv3x3(x, w)          Conv2d(k=3, s=1, p=1, bias=False) by ucfvit_conv2d_fwd / ucfvit_conv2d_wgrad
+  tconv2x2(x, w)         ConvTranspose2d(k=2, s=2, bias=False): pointwise layer [V, Cin] -> [V, 4 Cout] + depth-to-space
+conv1x1x1, unet_res_block and instnorm_act_cl take either layout: the pointwise layers are geometry-free and go through the 1x1x1 kernels
+over a factorisation of the X Y pixels (pointwise_dims), the normalisations read [B][S][C].
 """
+import functools
+
 import torch
 
 from . import ops
@@ -44,14 +52,79 @@ def pack_conv_weight(w):
         raise ValueError(f"convolution kernels: Cin must be 8, 16 or a multiple of 32, got {cin}")
     if nt not in (1, 27):
         raise ValueError("convolution kernels: kernel size must be 1 or 3")
+    return _pack_taps(w.reshape(cout, cin, nt))
+
+
+def _pack_taps(w):
+    """w [Cout, Cin, taps] -> bf16 [Cin / CPC, NTS, Cout, 32]: the packing of every convolution kernel, whatever the taps' geometry"""
+    cout, cin, nt = w.shape
     cpc = min(cin, 32)
     tps = 32 // cpc
     nts = -(-nt // tps)
-    wt = w.reshape(cout, cin, nt).permute(2, 0, 1)                     # [taps, Cout, Cin]
+    wt = w.permute(2, 0, 1)                                            # [taps, Cout, Cin]
     if nts * tps > nt:
         wt = torch.cat((wt, wt.new_zeros((nts * tps - nt, cout, cin))), 0)
     wt = wt.reshape(nts, tps, cout, cin // cpc, cpc).permute(3, 0, 2, 1, 4)   # [chunk, step, Cout, tap in step, channel in chunk]
     return wt.reshape(cin // cpc, nts, cout, 32).to(torch.bfloat16).contiguous()
+
+
+def pack_conv2d_weight(w):
+    """w [Cout, Cin, 3, 3] (any float dtype) -> bf16 [Cin / CPC, NTS, Cout, 32] as ucfvit_conv2d_fwd reads it (include/ucfvit_hip.h): the
+    3-D definition with 9 taps, tap = dx 3 + dy, NTS = ceil(9 / TPS) = 9, 5 or 3 steps per chunk for CPC = 32, 16, 8"""
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3):
+        raise ValueError("conv2d kernels: weight must be [Cout, Cin, 3, 3]")
+    if not conv3_cin_supported(w.shape[1]):
+        raise ValueError(f"convolution kernels: Cin must be 8, 16 or a multiple of 32, got {w.shape[1]}")
+    return _pack_taps(w.reshape(w.shape[0], w.shape[1], 9))
+
+
+def pack_conv2d_weight_dgrad(w):
+    """the data gradient of a stride-1 'same' convolution is the convolution of dy with the flipped taps and swapped channel roles"""
+    return pack_conv2d_weight(w.transpose(0, 1).flip(2, 3))
+
+
+def unpack_conv2d_wgrad(packed, cin, cout):
+    """packed fp32 from ucfvit_conv2d_wgrad ([Cout / (16 MB)][Cin / CPC][9][16 MB][max(CPC, 16)]) -> [Cout, Cin, 3, 3]"""
+    cpc = min(cin, 32)
+    mb16 = 32 if cout % 32 == 0 else 16
+    nbk16 = max(cpc, 16)
+    t = packed.view(cout // mb16, cin // cpc, 9, mb16, nbk16)[..., :cpc]
+    return t.permute(0, 3, 1, 4, 2).reshape(cout, cin, 3, 3)
+
+
+@functools.lru_cache(maxsize=None)
+def pointwise_dims(S, tile=(2, 8, 16)):
+    """(X', Y', Z') with X' Y' Z' = S: the volume the 1x1x1 kernels walk for the S pixels of an image.  A pointwise layer does not care
+    which pixels are neighbours, so any factorisation computes the same thing; the kernels tile a volume in `tile`-shaped blocks
+    ((2, 8, 16) voxels forward, (2, 4, 32) for the weight gradient) and compute whole tiles, so the factorisation with the fewest padded
+    voxels wastes least.  Ties go to the z extent nearest 128 (the extent the column kernels were tuned at) and the y extent of one tile.
+    An image whose pixel count has the tile's voxel count as a factor (every 16 k x 16 k image) wastes nothing; pointwise_waste() tells
+    the rest."""
+    tx, ty, tz = tile
+    up = lambda n, m: -(-n // m) * m
+    divs = lambda n: [d for d in range(1, n + 1) if n % d == 0] if n < 4096 else sorted(
+        {d for i in range(1, int(n ** 0.5) + 1) if n % i == 0 for d in (i, n // i)})
+    best = None
+    for z in divs(S):
+        for y in divs(S // z):
+            x = S // (z * y)
+            key = (up(x, tx) * up(y, ty) * up(z, tz), abs(z - 128), abs(y - ty))
+            if best is None or key < best[0]:
+                best = (key, (x, y, z))
+    return best[1]
+
+
+def pointwise_waste(S, tile=(2, 8, 16)):
+    """voxels the 1x1x1 kernels compute per pixel of an S-pixel image under pointwise_dims (1.0: none wasted)"""
+    x, y, z = pointwise_dims(S, tile)
+    up = lambda n, m: -(-n // m) * m
+    return up(x, tile[0]) * up(y, tile[1]) * up(z, tile[2]) / S
+
+
+def _as_volume(t, tile=(2, 8, 16)):
+    """[B, X, Y, C] (dense, or a channel slice of a dense channels-last buffer) -> the [B, X', Y', Z', C] view the 1x1x1 kernels walk"""
+    B, X, Y, C = t.shape
+    return t.view((B,) + pointwise_dims(X * Y, tile) + (C,))
 
 
 pack_conv3_weight = pack_conv_weight
@@ -101,7 +174,14 @@ def _colsum_narrow(d2):
 
 def _pointwise_fwd(x, w2, bias, cout_store, out_dtype=torch.bfloat16, accumulate_into=None, stats_eps=None, out=None):
     """x [B, X, Y, Z, K] bf16 (K one of the kernels' input widths), w2 [N, K] float -> [B, X, Y, Z, cout_store] through the 1x1x1 kernel
-    (into `out`, a channel slice of a wider channels-last buffer, when given)"""
+    (into `out`, a channel slice of a wider channels-last buffer, when given).  x [B, X, Y, K]: the same layer over the image's pixels"""
+    if x.dim() == 4:
+        shape = tuple(x.shape[:3]) + (cout_store,)
+        r = _pointwise_fwd(_as_volume(x), w2, bias, cout_store, out_dtype, None if accumulate_into is None else _as_volume(accumulate_into),
+                           stats_eps, None if out is None else _as_volume(out))
+        if out is not None:
+            return out
+        return (r[0].view(shape),) + tuple(r[1:]) if stats_eps is not None else r.view(shape)
     n16 = _ceil_to(w2.shape[0], 16)
     if n16 != w2.shape[0]:
         w2 = torch.cat((w2, w2.new_zeros((n16 - w2.shape[0], w2.shape[1]))), 0)
@@ -116,6 +196,8 @@ def _pointwise_fwd(x, w2, bias, cout_store, out_dtype=torch.bfloat16, accumulate
 def _pointwise_wgrad(x, dy):
     """x [.., K], dy [.., N] channels-last bf16 (kernel input widths) -> fp32 [N, K] = sum over voxels of dy^T x"""
     K, N = x.shape[-1], dy.shape[-1]
+    if x.dim() == 4:
+        return _pointwise_wgrad(_as_volume(x, (2, 4, 32)), _as_volume(dy, (2, 4, 32)))
     if N % 16 == 0:
         return unpack_conv_wgrad(ops.conv3d_wgrad(x, dy, ksize=1), K, N, 1).reshape(N, K)
     if K % 16:
@@ -129,10 +211,29 @@ def conv3_wgrad(x, dy, cin_x, cout):
     = sum_u x[u][ci] dy[u - tap][co], i.e. the weight gradient of the convolution dy -> x with the taps mirrored and the channel roles
     exchanged.  The kernel shifts its INPUT operand per tap and loads its output-gradient operand once per voxel row, so the shifted
     operand should be the narrow one: 18 instead of 30 transposed LDS reads per 14 MFMAs for 32 -> 16 channels."""
+    if x.dim() == 4:                                                         # the same rule in the plane: [Cout, cin_x, 3, 3]
+        if cout == 16 and cin_x >= 32:
+            return unpack_conv2d_wgrad(ops.conv2d_wgrad(dy, x), cout, cin_x).flip(2, 3).transpose(0, 1)
+        return unpack_conv2d_wgrad(ops.conv2d_wgrad(x, dy), cin_x, cout)
     if cout == 16 and cin_x >= 32:
         t = unpack_conv_wgrad(ops.conv3d_wgrad(dy, x), cout, cin_x)          # [cin_x, Cout, 3, 3, 3] of the mirrored problem
         return t.flip(2, 3, 4).transpose(0, 1)
     return unpack_conv_wgrad(ops.conv3d_wgrad(x, dy), cin_x, cout)
+
+
+def _conv3_fwd(x, w, cout, dgrad=False, stats_eps=None, accumulate_into=None):
+    """the 3x3x3 / 3x3 convolution of x with the (unpacked) weight w, or with dgrad the data gradient of that convolution applied to x = dy;
+    the volume calls are those of the 3-D decoder, keyword for keyword; the plane has no statistics epilogue, so its statistics are one
+    ucfvit_instnorm_cl_stats pass over the output"""
+    kw = {}
+    if accumulate_into is not None:
+        kw["accumulate_into"] = accumulate_into
+    if x.dim() == 5:
+        if stats_eps is not None:
+            kw["stats_eps"] = stats_eps
+        return ops.conv3d_fwd(x, pack_conv3_weight_dgrad(w) if dgrad else pack_conv_weight(w), cout, **kw)
+    y = ops.conv2d_fwd(x, pack_conv2d_weight_dgrad(w) if dgrad else pack_conv2d_weight(w), cout, **kw)
+    return y if stats_eps is None else (y,) + ops.instnorm_cl_stats(y, stats_eps)
 
 
 class Conv3x3x3Fn(torch.autograd.Function):
@@ -228,6 +329,102 @@ class TConv2x2x2Fn(torch.autograd.Function):
                 dw2 = ops.linear_wgrad(dcols, x.reshape(-1, cin))                                            # [8 Cout, Cin] fp32
         if ctx.needs_input_grad[1]:
             dw = dw2.reshape(2, 2, 2, cout, cin).permute(4, 3, 0, 1, 2).contiguous()
+        return dx, dw, dskip
+
+
+class Conv3x3Fn(torch.autograd.Function):
+    """Conv2d(k=3, s=1, p=1, bias=False) over channels-last [B, X, Y, C]: Conv3x3x3Fn in the plane (csrc/conv2d.hip)"""
+
+    @staticmethod
+    def forward(ctx, x, w):
+        cout, cin = w.shape[0], w.shape[1]
+        if tuple(w.shape[2:]) != (3, 3):
+            raise ValueError("conv3x3: weight must be [Cout, Cin, 3, 3]")
+        if cout % 16:
+            raise ValueError(f"conv3x3: Cout must be a multiple of 16, got {cout}")
+        cin_x = x.shape[-1]
+        if cin_x != cin:
+            if not (cin < cin_x and cin_x == 8):
+                raise ValueError(f"conv3x3: input has {cin_x} channels, weight expects {cin}")
+            wk = torch.cat((w, w.new_zeros((cout, cin_x - cin, 3, 3))), 1)      # zero-padded input channels (ops.pad_channels8)
+        else:
+            wk = w
+        y = ops.conv2d_fwd(x, pack_conv2d_weight(wk.detach()), cout)
+        ctx.save_for_backward(x, w)
+        ctx.cin_x = cin_x
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        cout, cin = w.shape[0], w.shape[1]
+        dy = dy.contiguous()
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            if cin % 16 or ctx.cin_x != cin:
+                raise RuntimeError(f"conv3x3: no data gradient for a {cin}-channel input (the kernel writes multiples of 16 channels)")
+            dx = ops.conv2d_fwd(dy, pack_conv2d_weight_dgrad(w.detach()), cin)
+        if ctx.needs_input_grad[1]:
+            dw = conv3_wgrad(x, dy, ctx.cin_x, cout)[:, :cin].contiguous()
+        return dx, dw
+
+
+class TConv2x2Fn(torch.autograd.Function):
+    """ConvTranspose2d(k=2, s=2): out[2p + d][co] = sum_ci x[p][ci] w[ci][co][d] = a pointwise layer to 4 Cout channels + depth-to-space:
+    TConv2x2x2Fn in the plane, with the same in-place skip concatenation (ucfvit_depth_to_space2_2d writes (out, skip) as whole rows, the
+    backward pass reads the two halves of the concatenation's gradient in place)."""
+
+    @staticmethod
+    def forward(ctx, x, w, skip):
+        cin, cout = w.shape[0], w.shape[1]
+        if tuple(w.shape[2:]) != (2, 2) or x.dim() != 4 or x.shape[-1] != cin:
+            raise ValueError("tconv2x2: weight must be [Cin, Cout, 2, 2] with Cin = the channels of the input [B, X, Y, Cin]")
+        B, X, Y, _ = x.shape
+        w2 = w.detach().permute(2, 3, 1, 0).reshape(4 * cout, cin)                                           # rows (dx, dy, co)
+        ctx.small = cin < GEMM_MIN
+        if ctx.small:
+            if not conv3_cin_supported(cin) or (4 * cout) % 32:
+                raise ValueError(f"tconv2x2: unsupported channel counts {cin} -> {cout}")
+            cols = _pointwise_fwd(x, w2, None, 4 * cout)
+        else:
+            w2 = w2.to(torch.bfloat16).contiguous()
+            cols = ops.linear_fwd(x.reshape(-1, cin), w2)
+        ctx.save_for_backward(x, w2)
+        ctx.wshape = tuple(w.shape)
+        ctx.cs = 0
+        if skip is None:
+            return ops.depth_to_space2_2d(cols.view(-1, 4 * cout), B, X, Y, cout)
+        if tuple(skip.shape[:3]) != (B, 2 * X, 2 * Y) or skip.dim() != 4 or skip.dtype != torch.bfloat16 or cout % 8 or skip.shape[-1] % 8:
+            raise ValueError("tconv2x2: skip must be a channels-last bf16 map of the up-sampled extent")
+        ctx.cs = skip.shape[-1]
+        cat = torch.empty((B, 2 * X, 2 * Y, cout + ctx.cs), dtype=torch.bfloat16, device=x.device)
+        ops.depth_to_space2_2d(cols.view(-1, 4 * cout), B, X, Y, cout, out=cat[..., :cout], skip=skip.contiguous())   # whole rows in one pass
+        return cat
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w2 = ctx.saved_tensors
+        cin, cout = ctx.wshape[0], ctx.wshape[1]
+        dskip = None
+        if ctx.cs:
+            if ctx.needs_input_grad[2]:
+                dskip = dy[..., cout:]                      # a view: the consumer (normalisation backward) reads the slice in place
+            dy = dy[..., :cout]
+        dcols = ops.space_to_depth2_2d(dy)
+        dx = dw = None
+        if ctx.small:
+            dcols = dcols.view(tuple(x.shape[:-1]) + (4 * cout,))
+            if ctx.needs_input_grad[0]:
+                dx = _pointwise_fwd(dcols, w2.t(), None, cin)
+            if ctx.needs_input_grad[1]:
+                dw2 = _pointwise_wgrad(x, dcols)
+        else:
+            if ctx.needs_input_grad[0]:
+                dx = ops.linear_dgrad(dcols, w2).view(x.shape)
+            if ctx.needs_input_grad[1]:
+                dw2 = ops.linear_wgrad(dcols, x.reshape(-1, cin))                                            # [4 Cout, Cin] fp32
+        if ctx.needs_input_grad[1]:
+            dw = dw2.reshape(2, 2, cout, cin).permute(3, 2, 0, 1).contiguous()
         return dx, dw, dskip
 
 
@@ -332,6 +529,7 @@ class Conv1x1x1Fn(torch.autograd.Function):
                          out_dtype=odt).view(tuple(x.shape[:-1]) + (cout,))
         ctx.save_for_backward(x, w2)
         ctx.dims = (cout, cin, b is not None)
+        ctx.wshape = tuple(w.shape)                 # [Cout, Cin, 1, 1, 1], or [Cout, Cin, 1, 1] over an image
         return y
 
     @staticmethod
@@ -346,7 +544,7 @@ class Conv1x1x1Fn(torch.autograd.Function):
                 wt = torch.cat((w2.t(), w2.new_zeros((cin_x, dyp.shape[-1] - cout))), 1) if dyp.shape[-1] != cout else w2.t()
                 dx = _pointwise_fwd(dyp, wt, None, cin_x)
             if ctx.needs_input_grad[1]:
-                dw = _pointwise_wgrad(x, dyp)[:cout, :cin].reshape(cout, cin, 1, 1, 1).contiguous()
+                dw = _pointwise_wgrad(x, dyp)[:cout, :cin].reshape(ctx.wshape).contiguous()
             if has_b and ctx.needs_input_grad[2]:
                 db = _colsum_narrow(dyp.view(-1, dyp.shape[-1]))[:cout].contiguous()
         else:
@@ -354,7 +552,7 @@ class Conv1x1x1Fn(torch.autograd.Function):
             if ctx.needs_input_grad[0]:
                 dx = ops.linear_dgrad(d2, w2).view(x.shape)
             if ctx.needs_input_grad[1]:
-                dw = ops.linear_wgrad(d2, x.reshape(-1, cin_x))[:, :cin].reshape(cout, cin, 1, 1, 1).contiguous()
+                dw = ops.linear_wgrad(d2, x.reshape(-1, cin_x))[:, :cin].reshape(ctx.wshape).contiguous()
             if has_b and ctx.needs_input_grad[2]:
                 db = ops.colsum(d2)
         return dx, dw, db, None
@@ -371,17 +569,18 @@ class UnetResBlockFn(torch.autograd.Function):
     def forward(ctx, inp, w1, w2, w3, eps, slope):
         cout, cin = w1.shape[0], w1.shape[1]
         cin_x = inp.shape[-1]
-        if cout % 16 or tuple(w1.shape[2:]) != (3, 3, 3) or tuple(w2.shape) != (cout, cout, 3, 3, 3):
-            raise ValueError("UnetResBlock: 3x3x3 weights [Cout, Cin, 3, 3, 3] / [Cout, Cout, 3, 3, 3] with Cout a multiple of 16")
+        k3 = (3,) * (inp.dim() - 2)                 # [B, X, Y, Z, C] with 3x3x3 weights, or [B, X, Y, C] with 3x3 weights
+        if inp.dim() not in (4, 5) or cout % 16 or tuple(w1.shape[2:]) != k3 or tuple(w2.shape) != (cout, cout) + k3:
+            raise ValueError("UnetResBlock: 3x3x3 weights [Cout, Cin, 3, 3, 3] / [Cout, Cout, 3, 3, 3] (3x3 over an image) with Cout a multiple of 16")
         if cin_x != cin and not (cin < cin_x == 8):
             raise ValueError(f"UnetResBlock: input has {cin_x} channels, weight expects {cin}")
         if w3 is None and cin_x != cout:
             raise ValueError("UnetResBlock: an identity residual needs Cin == Cout")
-        w1k = w1.detach() if cin_x == cin else torch.cat((w1.detach(), w1.new_zeros((cout, cin_x - cin, 3, 3, 3))), 1)
+        w1k = w1.detach() if cin_x == cin else torch.cat((w1.detach(), w1.new_zeros((cout, cin_x - cin) + k3)), 1)
         # every convolution hands over the instance-norm statistics of its output (epilogue by-product where the kernel has one)
-        c1, m1, r1 = ops.conv3d_fwd(inp, pack_conv_weight(w1k), cout, stats_eps=eps)
+        c1, m1, r1 = _conv3_fwd(inp, w1k, cout, stats_eps=eps)
         y1 = ops.instnorm_cl_apply(c1, m1, r1, None, slope)
-        c2, m2, r2 = ops.conv3d_fwd(y1, pack_conv_weight(w2.detach()), cout, stats_eps=eps)
+        c2, m2, r2 = _conv3_fwd(y1, w2.detach(), cout, stats_eps=eps)
         c3 = m3 = r3 = w3k = None
         if w3 is not None:
             w3k = w3.detach().reshape(cout, cin)
@@ -410,7 +609,7 @@ class UnetResBlockFn(torch.autograd.Function):
         else:
             dc2, dres = ops.instnorm_cl_bwd(dout, out, c2, m2, r2, slope, want_dres=need_dinp, had_res=True)
         dw2 = conv3_wgrad(y1, dc2, cout, cout).contiguous() if ctx.needs_input_grad[2] else None
-        dy1 = ops.conv3d_fwd(dc2, pack_conv3_weight_dgrad(w2.detach()), cout)
+        dy1 = _conv3_fwd(dc2, w2.detach(), cout, dgrad=True)
         del dc2
         dc1, _ = ops.instnorm_cl_bwd(dy1, c1, c1, m1, r1, slope, want_dres=False, had_res=False)       # no residual: the output is not read
         del dy1
@@ -418,7 +617,7 @@ class UnetResBlockFn(torch.autograd.Function):
         dw3 = dinp = None
         if w3 is not None:
             if ctx.needs_input_grad[3]:
-                dw3 = _pointwise_wgrad(inp, dc3)[:cout, :cin].reshape(cout, cin, 1, 1, 1).contiguous()
+                dw3 = _pointwise_wgrad(inp, dc3)[:cout, :cin].reshape(w3.shape).contiguous()
             if need_dinp:
                 w3k = w3.detach().reshape(cout, cin)
                 dinp = _pointwise_fwd(dc3, w3k.t(), None, cin_x)
@@ -427,7 +626,7 @@ class UnetResBlockFn(torch.autograd.Function):
         if need_dinp:
             if cin % 16 or cin_x != cin:
                 raise RuntimeError(f"UnetResBlock: no data gradient for a {cin}-channel input")
-            ops.conv3d_fwd(dc1, pack_conv3_weight_dgrad(w1.detach()), cin, accumulate_into=dinp)            # dinp += the 3x3x3 branch
+            _conv3_fwd(dc1, w1.detach(), cin, dgrad=True, accumulate_into=dinp)                            # dinp += the 3x3x3 branch
         return dinp, dw1, dw2, dw3, None, None
 
 
@@ -454,6 +653,15 @@ class InstNormActCLFn(torch.autograd.Function):
 
 def conv3x3x3(x, w):
     return Conv3x3x3Fn.apply(x, w)
+
+
+def conv3x3(x, w):
+    return Conv3x3Fn.apply(x, w)
+
+
+def tconv2x2(x, w, skip=None):
+    """skip given: returns the channel concatenation (transposed convolution, skip) — see TConv2x2Fn"""
+    return TConv2x2Fn.apply(x, w, skip)
 
 
 def tconv2x2x2(x, w, skip=None):

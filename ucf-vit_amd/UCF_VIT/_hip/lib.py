@@ -131,6 +131,12 @@ SIGNATURES = {
     "ucfvit_depth_to_space2": (c_int, [_P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I, _P, _I64, _P]),
     "ucfvit_pad_channels8": (c_int, [_P, _P, _I64, _I64, _I64, _P]),
     "ucfvit_pad_rows8": (c_int, [_P, c_int, _P, _I64, _I64, _I64, _P]),
+    "ucfvit_conv2d_fwd": (c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I, _I, _P]),
+    "ucfvit_conv2d_wgrad_size": (_I64, [_I64, _I64]),
+    "ucfvit_conv2d_wgrad_workspace": (_I64, [_I64, _I64, _I64, _I64, _I64]),
+    "ucfvit_conv2d_wgrad": (c_int, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _P]),
+    "ucfvit_conv2d_route": (c_int, [_I, _I64, _I64, _I64, _I64, _I64, _I, _I, _I64, _I64, c_char_p, _I64]),
+    "ucfvit_depth_to_space2_2d": (c_int, [_P, _P, _I64, _I64, _I64, _I64, _I64, _I, _P, _I64, _P]),
     "ucfvit_resample_trilinear_fwd": (c_int, [_P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P, _I64, _P]),
     "ucfvit_resample_trilinear_bwd": (c_int, [_P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P]),
     "ucfvit_cross_entropy": (c_int, [_P, _P, _P, _P, _P, _I64, _I64, _F, _I, _P]),

@@ -1022,10 +1022,11 @@ def dice_bce_from_stats(logits, targets, stats, weight=0.5, smooth=1.0, grad_sca
 
 
 # ------------------------------------------------------------------------------------------------ UNETR decoder, channels-last bf16
-def _chk_cl(t, name, C=None):
+def _chk_cl(t, name, C=None, dims=(4, 5)):
     _chk(t, name)
-    if t.dtype != torch.bfloat16 or t.dim() != 5:
-        raise TypeError(f"{name}: expected a channels-last bf16 tensor [B, X, Y, Z, C], got {tuple(t.shape)} {t.dtype}")
+    if t.dtype != torch.bfloat16 or t.dim() not in dims:
+        want = " or ".join("[B, X, Y, C]" if d == 4 else "[B, X, Y, Z, C]" for d in dims)
+        raise TypeError(f"{name}: expected a channels-last bf16 tensor {want}, got {tuple(t.shape)} {t.dtype}")
     if C is not None and t.shape[-1] != C:
         raise ValueError(f"{name}: expected {C} channels, got {t.shape[-1]}")
     return t
@@ -1042,7 +1043,7 @@ def conv3d_fwd(x, w_packed, cout, ksize=3, bias=None, cout_store=None, out_dtype
     stride 1, zero padding 1; ksize 1: pointwise).  bias: fp32 [cout] or None.  out: a bf16 channel slice of a wider channels-last buffer
     to write y into (the first half of a concatenation)."""
     L = _l.load()
-    _chk_cl(x, "conv3d.x"), _chk(w_packed, "conv3d.w_packed")
+    _chk_cl(x, "conv3d.x", dims=(5,)), _chk(w_packed, "conv3d.w_packed")
     B, X, Y, Z, cin = x.shape
     if w_packed.dtype != torch.bfloat16 or w_packed.numel() != conv_packed_numel(cin, cout, ksize):
         raise ValueError("conv3d: w_packed does not match (Cin, Cout, ksize)")
@@ -1088,7 +1089,7 @@ def conv3d_fwd(x, w_packed, cout, ksize=3, bias=None, cout_store=None, out_dtype
 def conv3d_wgrad(x, dy, ksize=3):
     """-> packed fp32 weight gradient (conv.unpack_conv_wgrad turns it into [Cout, Cin, k, k, k])"""
     L = _l.load()
-    _chk_cl(x, "conv3d_wgrad.x"), _chk_cl(dy, "conv3d_wgrad.dy")
+    _chk_cl(x, "conv3d_wgrad.x", dims=(5,)), _chk_cl(dy, "conv3d_wgrad.dy", dims=(5,))
     B, X, Y, Z, cin = x.shape
     cout = dy.shape[-1]
     if dy.shape[:4] != x.shape[:4]:
@@ -1105,15 +1106,15 @@ def conv3d_wgrad(x, dy, ksize=3):
 
 
 def cl_row_stride(t):
-    """voxel-row stride (elements) of a channels-last bf16 tensor [B, X, Y, Z, C] that is dense or a channel slice of a dense
-    [B, X, Y, Z, ld] buffer (what torch.cat's backward and a pre-allocated concatenation hand around); None if it is neither"""
-    if t.dim() != 5 or t.dtype != torch.bfloat16 or not t.is_cuda or t.stride(-1) != 1:
+    """voxel-row stride (elements) of a channels-last bf16 tensor [B, X, Y, Z, C] (or [B, X, Y, C]) that is dense or a channel slice of a
+    dense [B, X, Y, Z, ld] buffer (what torch.cat's backward and a pre-allocated concatenation hand around); None if it is neither"""
+    if t.dim() not in (4, 5) or t.dtype != torch.bfloat16 or not t.is_cuda or t.stride(-1) != 1:
         return None
     ld = t.stride(-2)
     if ld < t.shape[-1] or ld % 8 or t.data_ptr() % 16:
         return None
     exp = ld
-    for d in (3, 2, 1):
+    for d in range(t.dim() - 2, 0, -1):
         if t.stride(d) != exp and t.shape[d] != 1:
             return None
         exp *= t.shape[d]
@@ -1136,7 +1137,7 @@ def depth_to_space2(cols, B, Xi, Yi, Zi, C, out=None, skip=None):
         raise ValueError("depth_to_space2: out must be [B, 2Xi, 2Yi, 2Zi, C], dense or a channel slice of a dense channels-last buffer")
     cs = 0
     if skip is not None:
-        _chk_cl(skip, "depth_to_space2.skip")
+        _chk_cl(skip, "depth_to_space2.skip", dims=(5,))
         cs = skip.shape[-1]
         if tuple(skip.shape[:4]) != tuple(out.shape[:4]) or ld < C + cs:
             raise ValueError("depth_to_space2: skip must cover the output's voxels and fit behind it in the buffer")
@@ -1149,8 +1150,10 @@ def space_to_depth2(y):
     L = _l.load()
     ld = cl_row_stride(y)
     if ld is None:
-        y = _chk_cl(y.contiguous(), "space_to_depth2.y")
+        y = _chk_cl(y.contiguous(), "space_to_depth2.y", dims=(5,))
         ld = y.shape[-1]
+    if y.dim() != 5:
+        raise TypeError("space_to_depth2: expected [B, 2Xi, 2Yi, 2Zi, C]")
     B, X2, Y2, Z2, C = y.shape
     if X2 % 2 or Y2 % 2 or Z2 % 2:
         raise ValueError("space_to_depth2: extents must be even")
@@ -1160,12 +1163,107 @@ def space_to_depth2(y):
     return cols
 
 
+# ---- the plane: 3x3 convolution, its weight gradient and the 2x2 transposed convolution's shuffle (csrc/conv2d.hip) ----
+def conv2d_packed_numel(cin, cout):
+    cpc = min(cin, 32)
+    tps = 32 // cpc
+    return (cin // cpc) * (-(-9 // tps)) * cout * 32
+
+
+def conv2d_fwd(x, w_packed, cout, bias=None, cout_store=None, out_dtype=torch.bfloat16, accumulate_into=None, out=None):
+    """x [B, X, Y, Cin] bf16, w_packed from conv.pack_conv2d_weight (cout rows, a multiple of 16) -> y [B, X, Y, cout_store]: 3x3, stride 1,
+    zero padding 1.  bias: fp32 [cout] or None.  out: a bf16 channel slice of a wider channels-last buffer to write y into."""
+    L = _l.load()
+    _chk_cl(x, "conv2d.x", dims=(4,)), _chk(w_packed, "conv2d.w_packed")
+    B, X, Y, cin = x.shape
+    if w_packed.dtype != torch.bfloat16 or w_packed.numel() != conv2d_packed_numel(cin, cout):
+        raise ValueError("conv2d: w_packed does not match (Cin, Cout)")
+    if bias is not None:
+        _chk(bias, "conv2d.bias")
+        if bias.dtype != torch.float32 or bias.numel() != cout:
+            raise ValueError("conv2d: bias must be fp32 [Cout]")
+    cs = cout if cout_store is None else cout_store
+    ldy = cs
+    if out is not None:
+        ldy = cl_row_stride(out)
+        if ldy is None or tuple(out.shape) != (B, X, Y, cs) or out_dtype != torch.bfloat16 or accumulate_into is not None:
+            raise ValueError("conv2d: out must be a bf16 [B, X, Y, cout_store] map, dense or a channel slice of a channels-last buffer")
+        y = out
+    elif accumulate_into is not None:                          # y += result: the second data gradient of an input two layers consume
+        y = _chk(accumulate_into, "conv2d.accumulate_into")
+        if tuple(y.shape) != (B, X, Y, cs) or y.dtype != out_dtype:
+            raise ValueError("conv2d: accumulate_into must have the output's shape and dtype")
+    else:
+        y = torch.empty((B, X, Y, cs), dtype=out_dtype, device=x.device)
+    _l.check(L.ucfvit_conv2d_fwd(x.data_ptr(), w_packed.data_ptr(), _p(bias), y.data_ptr(), B, X, Y, cin, cout, ldy, cs, dt(y),
+                                 0 if accumulate_into is None else 1, _stream()), "ucfvit_conv2d_fwd")
+    return y
+
+
+def conv2d_wgrad(x, dy):
+    """-> packed fp32 weight gradient (conv.unpack_conv2d_wgrad turns it into [Cout, Cin, 3, 3])"""
+    L = _l.load()
+    _chk_cl(x, "conv2d_wgrad.x", dims=(4,)), _chk_cl(dy, "conv2d_wgrad.dy", dims=(4,))
+    B, X, Y, cin = x.shape
+    cout = dy.shape[-1]
+    if dy.shape[:3] != x.shape[:3]:
+        raise ValueError("conv2d_wgrad: x and dy must cover the same pixels")
+    n = L.ucfvit_conv2d_wgrad_size(cin, cout)
+    nbytes = L.ucfvit_conv2d_wgrad_workspace(B, X, Y, cin, cout)
+    if n <= 0 or nbytes <= 0:
+        raise ValueError(f"conv2d_wgrad: unsupported channel counts Cin={cin} Cout={cout}")
+    dw = torch.empty(n, dtype=torch.float32, device=x.device)
+    ws = workspace(nbytes, x.device)
+    _l.check(L.ucfvit_conv2d_wgrad(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), ws.data_ptr(), B, X, Y, cin, cout, _stream()), "ucfvit_conv2d_wgrad")
+    return dw
+
+
+def depth_to_space2_2d(cols, B, Xi, Yi, C, out=None, skip=None):
+    """cols [B Xi Yi, 4 C] (column blocks (dx, dy)) -> [B, 2Xi, 2Yi, C]; `out` may be a channel slice of a wider channels-last buffer; with
+    `skip` (dense [B, 2Xi, 2Yi, Cs]) the buffer behind `out` must be C + Cs wide and receives the skip behind the C channels"""
+    L = _l.load()
+    _chk(cols, "depth_to_space2_2d.cols")
+    if cols.dtype != torch.bfloat16 or cols.numel() != B * Xi * Yi * 4 * C:
+        raise ValueError("depth_to_space2_2d: bad operand")
+    if out is None:
+        out = torch.empty((B, 2 * Xi, 2 * Yi, C), dtype=torch.bfloat16, device=cols.device)
+    ld = cl_row_stride(out)
+    if ld is None or tuple(out.shape) != (B, 2 * Xi, 2 * Yi, C):
+        raise ValueError("depth_to_space2_2d: out must be [B, 2Xi, 2Yi, C], dense or a channel slice of a dense channels-last buffer")
+    cs = 0
+    if skip is not None:
+        _chk_cl(skip, "depth_to_space2_2d.skip", dims=(4,))
+        cs = skip.shape[-1]
+        if tuple(skip.shape[:3]) != tuple(out.shape[:3]) or ld < C + cs:
+            raise ValueError("depth_to_space2_2d: skip must cover the output's pixels and fit behind it in the buffer")
+    _l.check(L.ucfvit_depth_to_space2_2d(cols.data_ptr(), out.data_ptr(), B, Xi, Yi, C, ld, 1, _p(skip), cs, _stream()), "ucfvit_depth_to_space2_2d")
+    return out
+
+
+def space_to_depth2_2d(y):
+    """[B, 2Xi, 2Yi, C] (dense or a channel slice of a dense channels-last buffer) -> [B Xi Yi, 4 C]"""
+    L = _l.load()
+    ld = cl_row_stride(y)
+    if ld is None:
+        y = _chk_cl(y.contiguous(), "space_to_depth2_2d.y", dims=(4,))
+        ld = y.shape[-1]
+    if y.dim() != 4:
+        raise TypeError("space_to_depth2_2d: expected [B, 2Xi, 2Yi, C]")
+    B, X2, Y2, C = y.shape
+    if X2 % 2 or Y2 % 2:
+        raise ValueError("space_to_depth2_2d: extents must be even")
+    Xi, Yi = X2 // 2, Y2 // 2
+    cols = torch.empty((B * Xi * Yi, 4 * C), dtype=torch.bfloat16, device=y.device)
+    _l.check(L.ucfvit_depth_to_space2_2d(y.data_ptr(), cols.data_ptr(), B, Xi, Yi, C, ld, 0, None, 0, _stream()), "ucfvit_depth_to_space2_2d")
+    return cols
+
+
 def resample_trilinear(x, size, out=None, skip=None):
     """align-corners trilinear resampling (nn.Upsample(size, mode='trilinear', align_corners=True)) of a dense channels-last bf16 map
     x [B, Xi, Yi, Zi, C] (C % 8 == 0) -> [B, *size, C]; `out` may be a channel slice of a wider channels-last buffer; with `skip` (dense
     [B, *size, Cs]) the buffer behind `out` must be C + Cs wide and receives the skip behind the C channels"""
     L = _l.load()
-    _chk_cl(x, "resample_trilinear.x")
+    _chk_cl(x, "resample_trilinear.x", dims=(5,))
     B, Xi, Yi, Zi, C = x.shape
     Xo, Yo, Zo = (int(s) for s in size)
     if C % 8:
@@ -1192,8 +1290,10 @@ def resample_trilinear_bwd(dy, in_size):
     L = _l.load()
     ld = cl_row_stride(dy)
     if ld is None:
-        dy = _chk_cl(dy.contiguous(), "resample_trilinear_bwd.dy")
+        dy = _chk_cl(dy.contiguous(), "resample_trilinear_bwd.dy", dims=(5,))
         ld = dy.shape[-1]
+    if dy.dim() != 5:
+        raise TypeError("resample_trilinear_bwd: expected [B, Xo, Yo, Zo, C]")
     B, Xo, Yo, Zo, C = dy.shape
     Xi, Yi, Zi = (int(s) for s in in_size)
     dx = torch.empty((B, Xi, Yi, Zi, C), dtype=torch.bfloat16, device=dy.device)
@@ -1203,11 +1303,11 @@ def resample_trilinear_bwd(dy, in_size):
 
 
 def pad_channels8(vol):
-    """fp32 [B, C, X, Y, Z] with C <= 8 -> channels-last bf16 [B, X, Y, Z, 8] (channels C..7 zero)"""
+    """fp32 [B, C, X, Y, Z] (or [B, C, X, Y]) with C <= 8 -> channels-last bf16 [B, X, Y, Z, 8] ([B, X, Y, 8]), channels C..7 zero"""
     L = _l.load()
     _chk(vol, "pad_channels8.vol")
-    if vol.dtype != torch.float32 or vol.dim() != 5 or vol.shape[1] > 8:
-        raise TypeError("pad_channels8: expected an fp32 [B, C <= 8, X, Y, Z] volume")
+    if vol.dtype != torch.float32 or vol.dim() not in (4, 5) or vol.shape[1] > 8:
+        raise TypeError("pad_channels8: expected an fp32 [B, C <= 8, X, Y, Z] volume or [B, C <= 8, X, Y] image")
     B, C = vol.shape[0], vol.shape[1]
     out = torch.empty((B,) + tuple(vol.shape[2:]) + (8,), dtype=torch.bfloat16, device=vol.device)
     _l.check(L.ucfvit_pad_channels8(vol.data_ptr(), out.data_ptr(), B, C, vol.numel() // (B * C), _stream()), "ucfvit_pad_channels8")

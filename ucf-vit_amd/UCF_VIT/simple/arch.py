@@ -469,8 +469,11 @@ class UNETR(VIT):
     resamples dec1 to img_size (self.upsample: trilinear, align_corners=True) and decoder2's transposed convolution is pointwise; both
     run on the HIP kernels too (csrc/resample.hip, unetr_blocks.UnetrUpBlock.forward_cl).
 
-    ONE backend: a configuration the HIP decoder kernels do not cover (2-D, feature sizes other than 16 / 32 k, the pooling decoder
-    without skip connections) raises in forward() unless the caller asked for torch's own convolutions explicitly with the constructor
+    A twoD model (spatial_dims = 2 in the reference, :794-797) runs the same decoder over [B, X, Y, C] on csrc/conv2d.hip when every axis
+    has feat_size * 16 == img_size.
+
+    ONE backend: a configuration the HIP decoder kernels do not cover (2-D resampling geometries, feature sizes other than 16 / 32 k, the
+    pooling decoder without skip connections) raises in forward() unless the caller asked for torch's own convolutions explicitly with the constructor
     argument allow_torch_decoder=True (an extension of the reference's signature; default False).  That argument is a permission to fall
     back, not a request: a covered configuration runs on the HIP kernels whether or not it is set."""
 
@@ -572,7 +575,9 @@ class UNETR(VIT):
         if self.force_torch_decoder or self.linear_decoder or not self.skip_connection:
             return False
         full = all(self.feat_size[i] * 16 == self.img_size[i] for i in range(len(self.feat_size)))
-        return (full or self.resamples_dec1()) and hip_decoder_supported(2 if self.twoD else 3, self.in_chans, self.embed_dim, self.feature_size)
+        if self.twoD and not full:
+            return False                      # the plane has no resampling kernel (bilinear, align_corners): patch 4 / adaptive grids stay on torch
+        return (full or self.resamples_dec1()) and hip_decoder_supported(2 if self.twoD else 3, self.in_chans, self.embed_dim, self.feature_size, conv2d=True)
 
     def resamples_dec1(self):
         """the reference's test (:989-991): dec1 is resampled to img_size and decoder2's transposed convolution is pointwise"""
@@ -590,8 +595,9 @@ class UNETR(VIT):
         dec1 = self.decoder3.forward_cl(dec2, self.encoder2.forward_cl(self._tokens_cl(intermediates[n - 3])))
         # self.upsample(dec1) of the reference: resampled to img_size inside decoder2, behind its pointwise transposed convolution
         size = tuple(self.img_size) if self.resamples_dec1() else None
-        logits = self.out.forward_cl(self.decoder2.forward_cl(dec1, enc1, size))      # [B, X, Y, Z, classes] fp32
-        return logits.permute(0, 4, 1, 2, 3)                                          # the reference's [B, classes, X, Y, Z] as a view
+        logits = self.out.forward_cl(self.decoder2.forward_cl(dec1, enc1, size))      # [B, X, Y, Z, classes] fp32 ([B, X, Y, classes] in 2-D)
+        nd = logits.dim() - 2
+        return logits.permute(0, nd + 1, *range(1, nd + 1))                           # the reference's [B, classes, X, Y(, Z)] as a view
 
     def forward(self, x, variables, seq_ps=None, x_seq=None):
         tokens_in = x_seq if self.adaptive_patching else x
@@ -614,8 +620,8 @@ class UNETR(VIT):
     def _require_torch_decoder_opt_in(self):
         if not self.allow_torch_decoder:
             raise RuntimeError(
-                "UNETR: this configuration's convolutional decoder is not covered by the HIP convolution kernels (they need 3-D volumes, the "
-                "skip-connection decoder, feature_size 16 or a power-of-two multiple of 32, 1-8 input channels, an embed_dim of "
+                "UNETR: this configuration's convolutional decoder is not covered by the HIP convolution kernels (they need 3-D volumes, or 2-D "
+                "images whose token grid times 16 is the image size, the skip-connection decoder, feature_size 16 or a power-of-two multiple of 32, 1-8 input channels, an embed_dim of "
                 "8, 16 or a multiple of 32). Construct the model with allow_torch_decoder=True to run its convolutions on torch instead.")
 
 

@@ -9,11 +9,13 @@ Two execution paths over the SAME parameters (nn.Conv3d / nn.ConvTranspose3d mod
                    3x3x3 convolutions as implicit GEMMs on MFMA, transposed convolutions as GEMM + depth-to-space (kernel 2) or as a
                    pointwise layer (kernel 1, followed by the align-corners trilinear resampling of csrc/resample.hip where the reference
                    up-samples dec1), instance norm + LeakyReLU (+ residual) fused, csrc/conv3d.hip + csrc/unetr_decoder.hip +
-                   csrc/resample.hip through UCF_VIT/_hip/conv.py.  UNETR uses it whenever hip_decoder_supported() holds (3-D, kernel 3 /
-                   stride 1 / upsample 2, channel counts the kernels tile).
+                   csrc/resample.hip through UCF_VIT/_hip/conv.py.  UNETR uses it whenever hip_decoder_supported() holds (kernel 3 /
+                   stride 1 / upsample 2, channel counts the kernels tile).  The 2-D decoder (twoD models, spatial_dims = 2) takes the
+                   same path over [B, X, Y, C]: 3x3 convolutions and the 2x2 transposed convolutions' shuffle on csrc/conv2d.hip,
+                   the pointwise layers and the normalisations on the kernels of the volumes, which are geometry-free.
   forward(...)     N C (D) H W tensors: torch's own convolutions with the fused HIP instance-norm kernels between them — ONLY for models
-                   built with UNETR(allow_torch_decoder=True) (2-D, unusual channel counts); without that opt-in UNETR.forward raises
-                   instead of dropping to a second backend.
+                   built with UNETR(allow_torch_decoder=True) (2-D resampling geometries, unusual channel counts); without that opt-in
+                   UNETR.forward raises instead of dropping to a second backend.
 """
 import torch
 import torch.nn as nn
@@ -58,7 +60,8 @@ class UnetResBlock(nn.Module):
         return HF.instnorm_act(out, residual, self.norm2.eps, ns)
 
     def forward_cl(self, inp):
-        """inp channels-last bf16 [B, X, Y, Z, Cin] -> [B, X, Y, Z, Cout]: the whole block as one autograd node (_hip/conv.py:UnetResBlockFn)"""
+        """inp channels-last bf16 [B, X, Y, Z, Cin] -> [B, X, Y, Z, Cout] (2-D blocks: [B, X, Y, Cin] -> [B, X, Y, Cout]): the whole block as
+        one autograd node (_hip/conv.py:UnetResBlockFn)"""
         if self.norm1.eps != self.norm2.eps or (self.downsample and self.norm3.eps != self.norm1.eps):
             raise ValueError("UnetResBlock: the fused block takes one eps for its normalisations")
         return HC.unet_res_block(inp, self.conv1.conv.weight, self.conv2.conv.weight, self.conv3.conv.weight if self.downsample else None,
@@ -95,9 +98,10 @@ class UnetrPrUpBlock(nn.Module):
         return x
 
     def forward_cl(self, x):
-        x = HC.tconv2x2x2(x, self.transp_conv_init.conv.weight)
+        tconv = HC.tconv2x2 if x.dim() == 4 else HC.tconv2x2x2            # [B, X, Y, C] of a 2-D block, [B, X, Y, Z, C] of a 3-D one
+        x = tconv(x, self.transp_conv_init.conv.weight)
         for blk in self.blocks:
-            x = blk[1].forward_cl(HC.tconv2x2x2(x, blk[0].conv.weight))
+            x = blk[1].forward_cl(tconv(x, blk[0].conv.weight))
         return x
 
 
@@ -119,6 +123,8 @@ class UnetrUpBlock(nn.Module):
         k = tuple(w.shape[2:])
         if k == (2, 2, 2) and size is None:
             cat = HC.tconv2x2x2(inp, w, skip)                                   # (up-sampled, skip) concatenated in place
+        elif k == (2, 2) and size is None:
+            cat = HC.tconv2x2(inp, w, skip)                                     # the same over [B, X, Y, C]
         elif k == (1, 1, 1):
             if size is None or tuple(size) == tuple(inp.shape[1:4]):
                 cat = HC.tconv1x1x1(inp, w, skip)
@@ -138,16 +144,20 @@ class UnetOutBlock(nn.Module):
         return self.conv(inp)
 
     def forward_cl(self, inp):
-        """-> fp32 logits [B, X, Y, Z, n]: a view of a buffer whose voxel rows are padded to 8 columns (ops.dice_ce reads it in place)"""
+        """-> fp32 logits [B, X, Y, Z, n] ([B, X, Y, n] of a 2-D block): a view of a buffer whose voxel rows are padded to 8 columns
+        (ops.dice_ce reads it in place)"""
         return HC.conv1x1x1(inp, self.conv.conv.weight, self.conv.conv.bias, out_fp32=True)
 
 
-def hip_decoder_supported(spatial_dims, in_chans, embed_dim, feature_size, kernel_size=3, upsample_kernel_size=2):
+def hip_decoder_supported(spatial_dims, in_chans, embed_dim, feature_size, kernel_size=3, upsample_kernel_size=2, conv2d=False):
     """can the whole skip-connection decoder run on csrc/conv3d.hip?  3-D, 3x3x3 / 2x2x2 kernels, an input of <= 8 channels (zero-padded to the
     8-channel MFMA operand), feature_size a multiple of 16 whose multiples (x2, x4, x8, and the concatenations x2 .. x16) the kernels tile
     (16, or any multiple of 32), embed_dim one of the input widths the transposed-convolution / pointwise kernels tile (8, 16, or a
-    multiple of 32: _hip/conv.py conv3_cin_supported — 72 or 120 would pass a plain "% 8" rule and then fail inside forward)"""
+    multiple of 32: _hip/conv.py conv3_cin_supported — 72 or 120 would pass a plain "% 8" rule and then fail inside forward).
+    conv2d=True counts the kernels of the plane (csrc/conv2d.hip: 3x3 / 2x2) as well, as UNETR.hip_decoder() does: spatial_dims 2 then
+    passes under the same channel rules.  The default answers for the 3-D kernels alone (the benchmark's host logic, tests/test_bench_cpu.py,
+    asks that question and expects False for 2)."""
     fs = feature_size
-    return (spatial_dims == 3 and kernel_size == 3 and upsample_kernel_size == 2 and 1 <= in_chans <= 8
+    return (spatial_dims in ((2, 3) if conv2d else (3,)) and kernel_size == 3 and upsample_kernel_size == 2 and 1 <= in_chans <= 8
             and (embed_dim in (8, 16) or (embed_dim > 0 and embed_dim % 32 == 0))
             and fs % 16 == 0 and (fs == 16 or fs % 32 == 0) and (fs & (fs - 1)) == 0)

@@ -7,7 +7,8 @@ entry point here: the reference dataloaders are out of scope).  The logits never
 one-hot, monai DiceMetric(include_background=False, MEAN, get_not_nans); parity unpinned, monai is not vendored).
 
 Prints `acc` (Dice per non-background class; nan where the label volume lacks the class) and the aggregate, and writes
-pred_volume0.npy / true_volume0.npy (uint8, the tile's shape) into checkpoint_path.
+pred_volume0.npy / true_volume0.npy (uint8, the tile's shape: a 2-D array for a `twoD: True` config such as configs/unetr2d_smoke.yaml, whose
+decoder runs on csrc/conv2d.hip) into checkpoint_path.
 
 Deliberate departure: the reference always writes one matplotlib PNG per slice for prediction and label (2 Z figures at 200 dpi, minutes for
 a 128-slice volume, into the working directory).  Here the volumes go to the two .npy files and the PNG slices are written (into

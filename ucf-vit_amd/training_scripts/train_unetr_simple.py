@@ -5,8 +5,10 @@ LeakyReLU / residual chains on csrc/unetr_decoder.hip) and the Dice+CE loss (mon
 reference, :38; parity unpinned: monai is not vendored) all run on the HIP kernels — the reference's basic_ct/unetr key set (64^3 tile,
 patch 4, adaptive patching with fixed_length 729) included: its 9^3 token grid times 16 is not the tile size, so dec1 is resampled to the
 tile (csrc/resample.hip) in front of decoder2's pointwise transposed convolution, and the config runs as it is, without extra keys.  A
-configuration those kernels do not cover (2-D, feature sizes other than 16 / 32 k, ...) needs `allow_torch_decoder: True` in
-model.net.init_args, else UNETR.forward raises.
+`twoD: True` config whose token grid times 16 is the tile (configs/unetr2d_smoke.yaml: 32 x 32, patch 16) runs the same decoder in the plane
+(3x3 / 2x2 convolutions on csrc/conv2d.hip): labels [B, 1, X, Y], the same loss and accuracy calls.  A configuration those kernels do not
+cover (2-D resampling geometries, feature sizes other than 16 / 32 k, ...) needs `allow_torch_decoder: True` in model.net.init_args, else
+UNETR.forward raises.
 Every step also feeds the raw logits and the labels to a Dice accuracy (reference :399-401,453-460: argmax, one-hot, monai DiceMetric(
 include_background=False, MEAN, get_not_nans)): one HIP pass over the logits in place (ucfvit_seg_counts), accumulated on the device and read
 with the loss once per epoch: `... epoch_loss L volumes/s R dice D`."""
