@@ -444,7 +444,9 @@ def adaptive_pos_bwd(dout, seq_ps, w, bias, B, S, D, has_cls, want_dx=True, dw=N
     _chk(dout, "adaptive_pos_bwd.dout")
     kin = _chk_seq_ps(seq_ps, B, S, "adaptive_pos_bwd.seq_ps")
     pre = 1 if has_cls else 0
-    if tuple(dout.shape) != (B, S + pre, D) or tuple(w.shape) != (D, kin) or w.dtype != dout.dtype:
+    _chk(w, "adaptive_pos_bwd.w"), _chk(bias, "adaptive_pos_bwd.bias")
+    if (tuple(dout.shape) != (B, S + pre, D) or tuple(w.shape) != (D, kin) or bias.numel() != D or w.dtype != dout.dtype
+            or bias.dtype != dout.dtype):
         raise ValueError("adaptive_pos_bwd: shape / dtype mismatch")
     dev = dout.device
     dx = torch.empty((B * S, D), dtype=dout.dtype, device=dev) if want_dx else None

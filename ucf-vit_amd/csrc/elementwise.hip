@@ -175,7 +175,9 @@ __global__ __launch_bounds__(256) void ordered_sum_kernel(const float* __restric
 }
 
 // ===================================================================================================
-// MAE random masking index math: stable rank by counting (bit-exact with argsort for distinct keys).
+// MAE random masking index math: stable rank by counting, bit-exact with a stable argsort for every key: the total order is
+// numbers by value (-0 == +0), NaN above every number (inf included), equal keys and NaNs among themselves by index.  A rank is
+// then a permutation of [0, L) whatever the noise holds, so every slot of ids_shuffle is written.
 // ===================================================================================================
 __global__ __launch_bounds__(256) void mae_mask_kernel(const float* __restrict__ noise, int64_t* __restrict__ ids_shuffle,
                                                        int64_t* __restrict__ ids_restore, float* __restrict__ mask, int L,
@@ -187,10 +189,14 @@ __global__ __launch_bounds__(256) void mae_mask_kernel(const float* __restrict__
     __syncthreads();
     for (int i = threadIdx.x; i < L; i += blockDim.x) {
         const float x = nz[i];
+        const bool xnan = x != x;
         int rank = 0;
         for (int j = 0; j < L; ++j) {
             const float y = nz[j];
-            rank += (y < x) || (y == x && j < i);
+            const bool ynan = y != y;
+            const bool before = xnan ? !ynan : y < x;          // y < x is false for a NaN y
+            const bool same = xnan ? ynan : y == x;
+            rank += before || (same && j < i);
         }
         ids_restore[b * L + i] = rank;
         ids_shuffle[b * L + rank] = i;
