@@ -8,7 +8,8 @@ q_norm.bias gradient, the size of the terms that cancel in it.
 Shapes: (dim, heads, tokens) = (64, 2, 10), (128, 2, 197) (head width 64, the fused short-sequence route in bf16) and (64, 2, 300) (above
 256 tokens: the streaming route), so the qkv bias gradient (Q and K thirds from qk_norm_bwd's column sums, V third from the proj
 data-gradient epilogue) is checked on both attention routes.  Exact statements: activation checkpointing and a second run reproduce every
-bit; a Block without qk_norm issues the launches of the plain node."""
+bit; a Block without qk_norm issues the launches of the plain node; a group of same-shaped parameters that requires no gradient gets none
+while every other gradient stays right (B = 2: a gradient filed under the wrong argument would have the right shape)."""
 import ctypes
 from functools import partial
 
@@ -55,9 +56,9 @@ def _make_block(D, H, seed, dtype, qk_norm=True, **kw):
     return blk
 
 
-def _input(D, N, seed, dtype):
+def _input(D, N, seed, dtype, b=B):
     g = torch.Generator().manual_seed(seed)
-    return torch.randn(B, N, D, generator=g).to(DEV, dtype), torch.randn(B, N, D, generator=g).to(DEV, dtype)
+    return torch.randn(b, N, D, generator=g).to(DEV, dtype), torch.randn(b, N, D, generator=g).to(DEV, dtype)
 
 
 def _args(blk, x):
@@ -113,10 +114,10 @@ def _compare(mod, x, y, ref, x64grad, y64, tol):
             assert float(ref[k].abs().max()) > 0, k
 
 
-def _masks(N, D, on):
+def _masks(N, D, on, b=B):
     if not on:
         return None, None, None
-    mk = lambda seed, width: (torch.from_numpy(R.keep_mask(seed, B * N, width, P_DROP)).to(DEV).double().view(B, N, width)
+    mk = lambda seed, width: (torch.from_numpy(R.keep_mask(seed, b * N, width, P_DROP)).to(DEV).double().view(b, N, width)
                               * R.inv_keep(P_DROP))
     return mk(SEEDS[0], D), mk(SEEDS[1], 4 * D), mk(SEEDS[2], D)
 
@@ -263,6 +264,61 @@ def test_tail_block_class_rows(combo, dtype):
         assert torch.equal(g, g0[k]), k
 
 
+# The [D]-shaped parameters of a Block, in the groups that are frozen one at a time below (the qk_norm ones are [head_dim], alike among
+# themselves): a gradient that the node files under the wrong argument has the right shape, so only the parameter it lands on can tell.
+FROZEN = {"norm1": ("norm1.weight", "norm1.bias"), "norm2": ("norm2.weight", "norm2.bias"), "exit-biases": ("attn.proj.bias", "mlp.fc2.bias"),
+          "gammas": ("ls1.gamma", "ls2.gamma"), "qk_norms": QK}
+_FROZEN_CASES = {}
+
+
+def _frozen_case(dtype, tail):
+    """the all-features Block at B = 2 (sample 1 dropped in both branches) and its float64 gradients, built once per dtype and node"""
+    if (dtype, tail) not in _FROZEN_CASES:
+        D, H, N = CONFIGS["D64-N10"]
+        blk = _make_block(D, H, 30, dtype, init_values=0.5)
+        x, gy = _input(D, N, 31, dtype, 2)
+        gy = gy[:, 0].contiguous() if tail else gy
+        s = torch.tensor([2.0, 0.0], device=DEV)
+        P = QR.p64(blk.named_parameters())
+        x64 = x.double().requires_grad_(True)
+        y64 = QR.block64_qkn(x64, P, H, 1e-6, s, s, *_masks(N, D, True, 2))
+        y64 = y64[:, 0] if tail else y64
+        y64.backward(gy.double())
+        _FROZEN_CASES[dtype, tail] = (blk, x, gy, s, {k: v.grad for k, v in P.items()}, x64.grad, y64.detach())
+    return _FROZEN_CASES[dtype, tail]
+
+
+@pytest.mark.parametrize("recompute", [False, True], ids=["keep", "recompute"])
+@pytest.mark.parametrize("tail", [False, True], ids=["BlockFn", "TailBlockFn"])
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+def test_frozen_parameter_groups_get_no_gradient_and_the_rest_is_right(dtype, tail, recompute):
+    """qk_norm, LayerScale, drop path and dropout on one Block; one group of same-shaped parameters at a time does not require a gradient:
+    it gets none, and the output, dx and every other gradient meet the file's bound against float64, as with nothing frozen"""
+    blk, x, gy, s, ref, dx64, y64 = _frozen_case(dtype, tail)
+    tol = TOL[dtype]
+    run = _run_tail if tail else _run
+    for group, names in FROZEN.items():
+        xg = x.clone().requires_grad_(True)
+        for k, p in blk.named_parameters():
+            p.requires_grad_(k not in names)
+            p.grad = None
+        try:
+            y = run(blk, xg, s, s, (P_DROP,) + SEEDS, recompute=recompute)
+            y.backward(gy)
+            _mods()[1].flush_wgrads()
+        finally:
+            for p in blk.parameters():
+                p.requires_grad_(True)
+        assert rel_err(y.float(), y64) < tol, group
+        assert rel_err(xg.grad.float(), dx64) < tol, group
+        for k, p in blk.named_parameters():
+            if k in names:
+                assert p.grad is None, (group, k)
+            else:
+                assert p.grad is not None and p.grad.dtype == torch.float32, (group, k)
+                assert _grad_err(k, p.grad, ref) < tol, (group, k)
+
+
 def _record_ops(monkeypatch, HF):
     """every call the nodes make into the operator layer, by name (not the calls the operator layer makes into itself)"""
     seen, depth = [], [0]
@@ -285,7 +341,7 @@ def _record_ops(monkeypatch, HF):
 
 
 def test_block_without_qk_norm_issues_the_launches_it_issued(monkeypatch):
-    """qk_norm=False: the module takes the plain node (no trailing arguments), whose operator calls are those of an explicit plain call,
+    """qk_norm=False: the module hands the node every optional argument as None, and its operator calls are those of an explicit plain call,
     none of them qk_norm's, and the bits are the same; with qk_norm the same list grows by exactly one qk_norm_fwd behind the qkv GEMM and
     one qk_norm_bwd behind the attention backward (whose bias-gradient shortcut it replaces)"""
     BB, HF = _mods()

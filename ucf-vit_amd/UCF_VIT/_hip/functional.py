@@ -9,6 +9,8 @@ HipParamStore when there is one (see params.py); the view is handed to autograd 
 """
 import os
 import weakref
+from collections import namedtuple
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -314,8 +316,52 @@ def _qkn_of(qnw, qnb, knw, knb, eps):
     return (qnw, qnb, knw, knb, float(eps))
 
 
-def _attn_fwd(x2, B, N, H, wqkv, bqkv, wproj, bproj, residual, tp=None, qkn=None, save_qk=True):
-    """-> y, (qkv, o, lse, saved_qk, mean_qk, rstd_qk); the last three are None without qkn, or with save_qk false (no backward follows)"""
+class _DenseCore:
+    """the attention of a Block over every token: N rows per sample from the qkv GEMM to the Block's exit"""
+    rows = False
+    # Whether the UCFVIT_BIAS_FROM_EPILOGUE switch gates (a) the proj bias gradient taken from the LayerNorm-2 backward and (b) the V
+    # third of the qkv bias gradient taken from the proj data-gradient epilogue in the qk_norm arm of _attn_bwd.  The dense core gates
+    # both, the class-row core neither: they were written apart and drifted.  Kept as found: aligning them changes bits under the switch.
+    bias_switch_gates = True
+
+    @staticmethod
+    def fwd(qkv, B, N, H, dh):
+        return ops.attention_fwd(qkv, B, N, H, dh, dh ** -0.5)            # K5: fused softmax(QKᵀ)V over the local heads
+
+    @staticmethod
+    def bwd(qkv, o, do, lse, B, N, H, dh, **kw):
+        return ops.attention_bwd(qkv, o, do, lse, B, N, H, dh, dh ** -0.5, **kw)
+
+    @staticmethod
+    def colsum_supported(B, N, H, dh, dtype):
+        return ops.attention_bwd_colsum_supported(B, N, H, dh, dtype)
+
+
+class _ClassRowCore:
+    """the attention of the last Block for the class token alone: one query per head and sample (token 0), so 1 row per sample from the
+    attention on; the gradient turns dense again at dK / dV"""
+    rows = True
+    bias_switch_gates = False                                             # see _DenseCore
+
+    @staticmethod
+    def fwd(qkv, B, N, H, dh):
+        return ops.attention_rows_fwd(qkv, B, N, H, dh, dh ** -0.5, 0)
+
+    @staticmethod
+    def bwd(qkv, o, do, lse, B, N, H, dh, **kw):
+        return ops.attention_rows_bwd(qkv, o, do, lse, B, N, H, dh, dh ** -0.5, 0, **kw)
+
+    @staticmethod
+    def colsum_supported(B, N, H, dh, dtype):
+        return True
+
+
+_QKN_NAMES = ("qnw", "qnb", "knw", "knb")
+
+
+def _attn_fwd(x2, B, N, H, wqkv, bqkv, wproj, bproj, residual, tp=None, qkn=None, save_qk=True, core=_DenseCore):
+    """-> y, (qkv, o, lse, saved_qk, mean_qk, rstd_qk); the last three are None without qkn, or with save_qk false (no backward follows).
+    With the class-row core y and the residual have one row per sample; the whole qkv buffer is normalised (its queries need every key)"""
     dh = wproj.shape[0] // H
     Hl = H // tp.size if tp else H
     qkv = ops.linear_fwd(x2, wqkv, bqkv)                               # K4: qkv GEMM + bias
@@ -323,7 +369,7 @@ def _attn_fwd(x2, B, N, H, wqkv, bqkv, wproj, bproj, residual, tp=None, qkn=None
     if qkn is not None:
         _refuse_group_qk_norm(tp, qkn)
         sq = ops.qk_norm_fwd(qkv, qkn[0], qkn[1], qkn[2], qkn[3], Hl, dh, qkn[4], save=save_qk)      # in place: Q, K <- LayerNorm over dh
-    o, lse = ops.attention_fwd(qkv, B, N, Hl, dh, dh ** -0.5)          # K5: fused softmax(QKᵀ)V over the local heads
+    o, lse = core.fwd(qkv, B, N, Hl, dh)
     if tp and tp.rank != 0:
         residual = None
     y = ops.linear_fwd(o, wproj, bproj, residual=residual)             # K6: proj GEMM + bias (+ residual)
@@ -341,20 +387,21 @@ def _qkn_bwd(dqkv, sq, qkn, H, dh, qkn_needs, gb2, gb2_acc):
     return tuple(_bgrad_from(qkn[i], pg[i]) if qkn_needs[i] else None for i in range(4))
 
 
-def _attn_bwd(dy2, x2, saved, B, N, H, wqkv, wproj, p_qkvw, p_qkvb, p_projw, p_projb, needs, tp=None, wq=None, projb_done=None, qkn=None,
-              qkn_needs=(False,) * 4):
-    """projb_done: (grad,) when the producer of dy2 (LayerNorm backward) has already written the proj bias gradient
-    qkn: as in _attn_fwd; then -> dx, grads, (the gradients of gamma_q, beta_q, gamma_k, beta_k)"""
+def _attn_bwd(dy2, x2, saved, B, N, H, wqkv, wproj, p_qkvw, p_qkvb, p_projw, p_projb, need, tp=None, wq=None, projb_done=None, qkn=None,
+              core=_DenseCore):
+    """need: {forward argument name: requires a gradient} of the calling node (qkvw, qkvb, projw, projb and, with qkn, qnw, qnb, knw, knb);
+    projb_done: (grad,) when the producer of dy2 (LayerNorm backward, a branch exit) has already written the proj bias gradient;
+    qkn: as in _attn_fwd.  -> dx, {name: gradient} under the same names"""
     qkv, o, lse, *sq = saved
     dh = wproj.shape[0] // H
     H = H // tp.size if tp else H
-    g_projw = _wgrad(p_projw, dy2, o, wq) if needs[2] else None
+    g = {}
+    g["projw"] = _wgrad(p_projw, dy2, o, wq) if need["projw"] else None
     if projb_done is not None:
-        g_projb = projb_done[0]
+        g["projb"] = projb_done[0]
     else:
-        g_projb = _bgrad(p_projb, dy2) if (p_projb is not None and needs[3]) else None
-    want_b = p_qkvb is not None and needs[1]
-    g_qkn = None
+        g["projb"] = _bgrad(p_projb, dy2) if (p_projb is not None and need["projb"]) else None
+    want_b = p_qkvb is not None and need["qkvb"]
     if qkn is not None:
         # with a LayerNorm between the bias and the scores the shortcut below does not hold for the Q and K thirds (the K third is not 0, the Q
         # third not the sum of dQ): they are the column sums of what qk_norm_bwd writes; the V third is still the column sum of dO
@@ -362,14 +409,14 @@ def _attn_bwd(dy2, x2, saved, B, N, H, wqkv, wproj, p_qkvw, p_qkvb, p_projw, p_p
         gb, acc = grad_target(p_qkvb) if want_b else (None, False)
         if want_b and gb is None:
             gb, acc = torch.empty(3 * Dl, dtype=torch.float32, device=dy2.device), False
-        from_epi = want_b and _BIAS_FROM_EPILOGUE
+        from_epi = want_b and (_BIAS_FROM_EPILOGUE or not core.bias_switch_gates)
         do = _dgrad(dy2, p_projw, wproj, c_colsum=gb[2 * Dl:] if from_epi else None, c_colsum_accumulate=acc)
-        dqkv = ops.attention_bwd(qkv, o, do, lse, B, N, H, dh, dh ** -0.5)
+        dqkv = core.bwd(qkv, o, do, lse, B, N, H, dh)
         if want_b and not from_epi:
             ops.colsum(dqkv[:, 2 * Dl:], out=gb[2 * Dl:], accumulate=acc)
-        g_qkn = _qkn_bwd(dqkv, sq, qkn, H, dh, qkn_needs, gb[:2 * Dl] if want_b else None, acc)
-        g_qkvb = (None if acc else gb) if want_b else None
-    elif want_b and ops.attention_bwd_colsum_supported(B, N, H, dh, qkv.dtype):
+        g.update(zip(_QKN_NAMES, _qkn_bwd(dqkv, sq, qkn, H, dh, [need[k] for k in _QKN_NAMES], gb[:2 * Dl] if want_b else None, acc)))
+        g["qkvb"] = (None if acc else gb) if want_b else None
+    elif want_b and core.colsum_supported(B, N, H, dh, qkv.dtype):
         # the qkv bias gradient without a second read of dqkv (include/ucfvit_hip.h, ucfvit_attention_bwd_colsum): Q third = the per-image
         # column sums the backward kernel hands out, summed over the images; K third = 0 exactly; V third = the column sums of dO, taken in
         # the epilogue of the GEMM that produces dO
@@ -378,20 +425,18 @@ def _attn_bwd(dy2, x2, saved, B, N, H, wqkv, wproj, p_qkvw, p_qkvb, p_projw, p_p
         if gb is None:
             gb, acc = torch.empty(3 * Dl, dtype=torch.float32, device=dy2.device), False
         do = _dgrad(dy2, p_projw, wproj, c_colsum=gb[2 * Dl:], c_colsum_accumulate=acc)
-        dqkv, part = ops.attention_bwd(qkv, o, do, lse, B, N, H, dh, dh ** -0.5, want_colsum=True)
+        dqkv, part = core.bwd(qkv, o, do, lse, B, N, H, dh, want_colsum=True)
         ops.reduce_rows(part, gb[:2 * Dl], accumulate=acc)
-        g_qkvb = None if acc else gb
+        g["qkvb"] = None if acc else gb
     else:
         do = _dgrad(dy2, p_projw, wproj)
-        dqkv = ops.attention_bwd(qkv, o, do, lse, B, N, H, dh, dh ** -0.5)
-        g_qkvb = _bgrad(p_qkvb, dqkv) if want_b else None
-    g_qkvw = _wgrad(p_qkvw, dqkv, x2, wq) if needs[0] else None
+        dqkv = core.bwd(qkv, o, do, lse, B, N, H, dh)
+        g["qkvb"] = _bgrad(p_qkvb, dqkv) if want_b else None
+    g["qkvw"] = _wgrad(p_qkvw, dqkv, x2, wq) if need["qkvw"] else None
     dx = _dgrad(dqkv, p_qkvw, wqkv)
     if tp:
         tp.all_reduce(dx)                                              # C2: entry gradient all-reduce
-    if qkn is not None:
-        return dx, (g_qkvw, g_qkvb, g_projw, g_projb), g_qkn
-    return dx, (g_qkvw, g_qkvb, g_projw, g_projb)
+    return dx, g
 
 
 def _mlp_fwd(x2, w1, b1, w2, b2, residual, tp=None, drop1=None):
@@ -409,18 +454,19 @@ def _mlp_fwd(x2, w1, b1, w2, b2, residual, tp=None, drop1=None):
     return y, (h, a)
 
 
-def _mlp_bwd(dy2, x2, saved, w1, w2, p_w1, p_b1, p_w2, p_b2, needs, tp=None, wq=None, dy2_colsum=None, drop1=None):
-    """dy2_colsum: column sums of dy2 when its producer (a LayerNorm backward) published them: the fc2 bias gradient;
+def _mlp_bwd(dy2, x2, saved, w1, w2, p_w1, p_b1, p_w2, p_b2, need, tp=None, wq=None, dy2_colsum=None, drop1=None):
+    """need: {forward argument name: requires a gradient} of the calling node (f1w, f1b, f2w, f2b); -> dx, {name: gradient};
+    dy2_colsum: column sums of dy2 when its producer (a LayerNorm backward) published them: the fc2 bias gradient;
     drop1: the dropout site behind the activation: dh is masked in place after the fused gelu' epilogue, and the column sums of the masked
     dh (the fc1 bias gradient) come from that pass, not from the epilogue"""
     h, a = saved
-    g_w2 = _wgrad(p_w2, dy2, a, wq) if needs[2] else None
-    if p_b2 is not None and needs[3]:
+    g_w2 = _wgrad(p_w2, dy2, a, wq) if need["f2w"] else None
+    if p_b2 is not None and need["f2b"]:
         g_b2 = _bgrad_from(p_b2, dy2_colsum) if dy2_colsum is not None else _bgrad(p_b2, dy2)
     else:
         g_b2 = None
     # dgrad fused with gelu'(pre-activation); the fc1 bias gradient = column sums of dh comes out of the same epilogue
-    need_b1 = p_b1 is not None and needs[1]
+    need_b1 = p_b1 is not None and need["f1b"]
     if drop1 is not None:
         dh = _dgrad(dy2, p_w2, w2, aux=h, aux_is_deriv=_saves_gelu_deriv(h.dtype))
         cs = torch.empty(dh.shape[1], dtype=torch.float32, device=dy2.device) if need_b1 else None
@@ -435,11 +481,11 @@ def _mlp_bwd(dy2, x2, saved, w1, w2, p_w1, p_b1, p_w2, p_b2, needs, tp=None, wq=
     else:
         dh = _dgrad(dy2, p_w2, w2, aux=h, aux_is_deriv=_saves_gelu_deriv(h.dtype))
         g_b1 = _bgrad(p_b1, dh) if need_b1 else None
-    g_w1 = _wgrad(p_w1, dh, x2, wq) if needs[0] else None
+    g_w1 = _wgrad(p_w1, dh, x2, wq) if need["f1w"] else None
     dx = _dgrad(dh, p_w1, w1)
     if tp:
         tp.all_reduce(dx)                                              # C4: entry gradient all-reduce
-    return dx, (g_w1, g_b1, g_w2, g_b2)
+    return dx, dict(f1w=g_w1, f1b=g_b1, f2w=g_w2, f2b=g_b2)
 
 
 # ---------------------------------------------------------------------------------------------- Functions
@@ -491,8 +537,30 @@ class LayerNormFn(torch.autograd.Function):
         return _ret_grad(dx.view(ctx.in_shape), ctx.in_dtype), dg, db, None, None
 
 
+class _Slots:
+    """the forward argument names of one autograd node (ctx left out), declared once: backward reads needs_input_grad and files its
+    gradients under these names, so no position is counted by hand"""
+
+    def __init__(self, *names):
+        self.names = names
+        self.index = {n: i for i, n in enumerate(names)}
+
+    def needs(self, ctx):
+        """{name: requires a gradient}; needs_input_grad covers the arguments apply() was given, the defaulted rest needs none"""
+        given = ctx.needs_input_grad
+        return dict(zip(self.names, given + (False,) * (len(self.names) - len(given))))
+
+    def grads(self, **by_name):
+        """the tuple backward returns: None but for the gradients given; a name that is no forward argument raises KeyError"""
+        out = [None] * len(self.names)
+        for k, g in by_name.items():
+            out[self.index[k]] = g
+        return tuple(out)
+
+
 class AttentionFn(torch.autograd.Function):
     """Attention.forward (building_blocks.py:157-192): qkv Linear -> fused SDPA -> proj Linear."""
+    ARGS = _Slots("x", "qkvw", "qkvb", "projw", "projb", "num_heads", "cdtype", "tp", "drop", "qnw", "qnb", "knw", "knb", "qk_eps", "save_qk")
 
     @staticmethod
     def forward(ctx, x, qkvw, qkvb, projw, projb, num_heads, cdtype, tp=None, drop=None, qnw=None, qnb=None, knw=None, knb=None, qk_eps=None,
@@ -502,7 +570,7 @@ class AttentionFn(torch.autograd.Function):
         Q and K thirds of the qkv buffer are LayerNormed per head in place before the attention kernels.  When a backward pass can follow
         the un-normalised Q and K are kept (two more D-wide token matrices) with the fp32 statistics; save_qk: whether one can (the caller
         passes torch.is_grad_enabled(), as for BlockFn's save_branch); None: decided from needs_input_grad alone"""
-        drop = _site(drop, tp)
+        ctx.exit = _Exit(site=_site(drop, tp))
         qkn = _qkn_of(qnw, qnb, knw, knb, qk_eps)
         _refuse_group_qk_norm(tp, qkn)
         keep = any(ctx.needs_input_grad) and (save_qk is None or bool(save_qk))
@@ -511,60 +579,53 @@ class AttentionFn(torch.autograd.Function):
         x2 = xin.view(B * N, D)
         c = lambda p: compute_param(p, cdtype)
         y, saved = _attn_fwd(x2, B, N, num_heads, c(qkvw), c(qkvb), c(projw), c(projb), None, tp, qkn, keep)
-        if drop is not None:
-            _dropout(y, drop, out=y)
+        y, _ = ctx.exit.forward(None, y, False)
         ctx.save_for_backward(x2, *saved, qkvw, qkvb, projw, projb, qnw, qnb, knw, knb)
-        ctx.meta = (B, N, num_heads, cdtype, x.dtype, tp)
-        ctx.qk_eps = qk_eps
-        ctx.drop = drop
+        ctx.meta = (B, N, num_heads, cdtype, x.dtype, tp, qk_eps)
         return y.view(B, N, D)
 
     @staticmethod
     def backward(ctx, dy):
-        x2, qkv, o, lse, sqk, mqk, rqk, qkvw, qkvb, projw, projb, qnw, qnb, knw, knb = ctx.saved_tensors
-        B, N, H, cdtype, in_dtype, tp = ctx.meta
-        qkn = _qkn_of(qnw, qnb, knw, knb, ctx.qk_eps)
+        x2, *saved, qkvw, qkvb, projw, projb, qnw, qnb, knw, knb = ctx.saved_tensors
+        B, N, H, cdtype, in_dtype, tp, qk_eps = ctx.meta
+        need = AttentionFn.ARGS.needs(ctx)
+        qkn = _qkn_of(qnw, qnb, knw, knb, qk_eps)
         dy2 = _as(dy, cdtype).reshape(x2.shape)
         c = lambda p: compute_param(p, cdtype)
-        projb_done = None
-        if ctx.drop is not None:                               # the gradient of proj's output, and its column sums: proj's bias gradient
-            dy2, cs = _branch_grad(dy2, None, 1, ctx.drop, projb is not None and ctx.needs_input_grad[4])
-            projb_done = (_bgrad_from(projb, cs) if cs is not None else None,)
-        dx, g, *gq = _attn_bwd(dy2, x2, (qkv, o, lse, sqk, mqk, rqk), B, N, H, c(qkvw), c(projw), qkvw, qkvb, projw, projb,
-                               ctx.needs_input_grad[1:5], tp, projb_done=projb_done, qkn=qkn, qkn_needs=ctx.needs_input_grad[9:13])
-        return (_ret_grad(dx.view(B, N, -1), in_dtype),) + g + (None, None, None, None) + (gq[0] if gq else (None,) * 4) + (None, None)
+        # behind proj_drop: the gradient of proj's output, and its column sums: proj's bias gradient
+        dy2, cs, _ = ctx.exit.backward(dy2, None, projb is not None and need["projb"], False)
+        projb_done = None if ctx.exit.plain else (_bgrad_from(projb, cs) if cs is not None else None,)
+        dx, g = _attn_bwd(dy2, x2, saved, B, N, H, c(qkvw), c(projw), qkvw, qkvb, projw, projb, need, tp, projb_done=projb_done, qkn=qkn)
+        return AttentionFn.ARGS.grads(x=_ret_grad(dx.view(B, N, -1), in_dtype), **g)
 
 
 class MlpFn(torch.autograd.Function):
     """Mlp.forward (building_blocks.py:122-129): fc1 -> erf-GELU -> drop1 -> fc2 -> drop2 (norm=Identity; the drops only in training)."""
+    ARGS = _Slots("x", "f1w", "f1b", "f2w", "f2b", "cdtype", "tp", "drop1", "drop2")
 
     @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, cdtype, tp=None, drop1=None, drop2=None):
+    def forward(ctx, x, f1w, f1b, f2w, f2b, cdtype, tp=None, drop1=None, drop2=None):
         """drop1, drop2: (p, seed) of the dropout behind the activation and behind fc2 in training, or None"""
-        drop1, drop2 = _site(drop1, tp), _site(drop2, tp)
+        drop1, ctx.exit = _site(drop1, tp), _Exit(site=_site(drop2, tp))
         xin = _as(x, cdtype)
         x2 = xin.reshape(-1, xin.shape[-1])
         c = lambda p: compute_param(p, cdtype)
-        y, saved = _mlp_fwd(x2, c(w1), c(b1), c(w2), c(b2), None, tp, drop1=drop1)
-        if drop2 is not None:
-            _dropout(y, drop2, out=y)
-        ctx.save_for_backward(x2, *saved, w1, b1, w2, b2)
-        ctx.meta = (cdtype, x.dtype, x.shape, tp)
-        ctx.drops = (drop1, drop2)
+        y, saved = _mlp_fwd(x2, c(f1w), c(f1b), c(f2w), c(f2b), None, tp, drop1=drop1)
+        y, _ = ctx.exit.forward(None, y, False)
+        ctx.save_for_backward(x2, *saved, f1w, f1b, f2w, f2b)
+        ctx.meta = (cdtype, x.dtype, x.shape, tp, drop1)
         return y.view(*x.shape[:-1], y.shape[-1])
 
     @staticmethod
     def backward(ctx, dy):
-        x2, h, a, w1, b1, w2, b2 = ctx.saved_tensors
-        cdtype, in_dtype, in_shape, tp = ctx.meta
+        x2, h, a, f1w, f1b, f2w, f2b = ctx.saved_tensors
+        cdtype, in_dtype, in_shape, tp, drop1 = ctx.meta
+        need = MlpFn.ARGS.needs(ctx)
         dy2 = _as(dy, cdtype).reshape(-1, dy.shape[-1])
         c = lambda p: compute_param(p, cdtype)
-        drop1, drop2 = ctx.drops
-        cs = None
-        if drop2 is not None:
-            dy2, cs = _branch_grad(dy2, None, 1, drop2, b2 is not None and ctx.needs_input_grad[4])
-        dx, g = _mlp_bwd(dy2, x2, (h, a), c(w1), c(w2), w1, b1, w2, b2, ctx.needs_input_grad[1:5], tp, dy2_colsum=cs, drop1=drop1)
-        return (_ret_grad(dx.view(in_shape), in_dtype),) + g + (None, None, None, None)
+        dy2, cs, _ = ctx.exit.backward(dy2, None, f2b is not None and need["f2b"], False)
+        dx, g = _mlp_bwd(dy2, x2, (h, a), c(f1w), c(f2w), f1w, f1b, f2w, f2b, need, tp, dy2_colsum=cs, drop1=drop1)
+        return MlpFn.ARGS.grads(x=_ret_grad(dx.view(in_shape), in_dtype), **g)
 
 
 class DropPathFn(torch.autograd.Function):
@@ -611,53 +672,72 @@ def _dropout(x2, site, s=None, rows_per_sample=1, out=None, c_colsum=None):
     return ops.dropout(x2, p, seed, s=s, rows_per_sample=rows_per_sample, row_step=row_step, out=out, c_colsum=c_colsum)
 
 
-def _branch_exit(res, y, s, rows_per_sample, site):
-    """the exit of a residual branch whose GEMM ran without the residual: y <- res + s ⊙ m ⊙ y / keep in place (site None: drop path only)"""
-    if site is None:
-        return ops.drop_path_add(res, y, s, rows_per_sample)
-    p, seed, row_step = site
-    if p >= 1.0:
-        return y.copy_(res)
-    return ops.dropout_add(res, y, p, seed, s=s, rows_per_sample=rows_per_sample, row_step=row_step)
+class _Exit(NamedTuple):
+    """The exit of a residual branch: stream = res + s ⊙ m ⊙ (γ ⊙ branch) / keep, and its gradient.
+    s: the drop-path scale per sample (fp32 [B]) or None; site: the dropout site (mask m, rate 1 - keep) or None; gamma: the LayerScale
+    parameter (fp32 [D] master) or None; rows_per_sample: rows of the branch that share one entry of s.
 
+    plain (none of the three): the residual stays in the epilogue of the branch's exit GEMM and there is nothing to do here, launch for
+    launch a Block without any of them.  Otherwise that GEMM runs without the residual and one row pass applies what is there:
+    drop path alone ops.drop_path_add, with dropout ops.dropout_add, both over the branch; with a gamma ops.layer_scale_add (the scale
+    and the site riding along).  Backward of a gamma needs the UNSCALED branch output (gamma's gradient is the column sums of g ⊙ branch):
+    with keep the sum goes to a new buffer and the branch output is saved; without (no_grad, nothing that requires a gradient, the first
+    pass of a checkpointed Block) it overwrites the branch.  The column sums of the branch's output gradient s ⊙ m ⊙ γ ⊙ dy / keep are the
+    bias gradient of proj / fc2 — not those of the stream gradient that the LayerNorm backward kernels hand out."""
+    s: Optional[torch.Tensor] = None
+    site: Optional[tuple] = None
+    gamma: Optional[torch.Tensor] = None
+    rows_per_sample: int = 1
 
-def _branch_grad(dy2, s, rows_per_sample, site, want_sums):
-    """-> (s ⊙ m ⊙ dy2 / keep, its fp32 [D] column sums or None): the gradient of a branch's exit GEMM output and that GEMM's bias gradient"""
-    if site is None:
-        return _scaled_grad(dy2, s, rows_per_sample, want_sums)
-    cs = torch.empty(dy2.shape[1], dtype=torch.float32, device=dy2.device) if want_sums else None
-    return _dropout(dy2, site, s, rows_per_sample, c_colsum=cs), cs
+    @property
+    def plain(self):
+        return self.s is None and self.site is None and self.gamma is None
 
+    def forward(self, res, y, keep):
+        """y: the exit GEMM's output (without the residual unless plain); res None: no residual (a module on its own)
+        -> (the stream, the branch output to save for backward or None)"""
+        if self.plain:
+            return y, None
+        p, seed, row_step = self.site if self.site is not None else (0.0, 0, 1)
+        if self.gamma is not None:
+            out = torch.empty_like(y) if keep else y
+            if p >= 1.0:
+                out.copy_(res)
+            else:
+                ops.layer_scale_add(res, y, self.gamma, s=self.s, rows_per_sample=self.rows_per_sample, p=p, seed=seed, row_step=row_step, out=out)
+            return out, (y if keep else None)
+        if res is None:
+            _dropout(y, self.site, self.s, self.rows_per_sample, out=y)
+        elif self.site is None:
+            ops.drop_path_add(res, y, self.s, self.rows_per_sample)
+        elif p >= 1.0:
+            y.copy_(res)
+        else:
+            ops.dropout_add(res, y, p, seed, s=self.s, rows_per_sample=self.rows_per_sample, row_step=row_step)
+        return y, None
 
-# LayerScale inside the fused Blocks.  A branch with a gamma (the fp32 master parameter of ls1 / ls2) is never "plain": its exit GEMM runs
-# without the residual and ops.layer_scale_add writes res + s ⊙ m ⊙ (gamma ⊙ branch) / keep, the drop-path scale and the dropout site riding
-# along.  Backward needs the UNSCALED branch output (gamma's gradient is the column sums of g ⊙ branch), so with keep the sum goes to a new
-# buffer and the branch output is saved; without (no_grad, nothing that requires a gradient, the first pass of a checkpointed Block) it
-# overwrites the branch.
-def _ls_branch_exit(res, y, gamma, s, rows_per_sample, site, keep):
-    """-> res + s ⊙ m ⊙ (gamma ⊙ y) / keep: in a new buffer when keep (y stays the branch output), else over y"""
-    out = torch.empty_like(y) if keep else y
-    p, seed, row_step = site if site is not None else (0.0, 0, 1)
-    if p >= 1.0:
-        return out.copy_(res)
-    return ops.layer_scale_add(res, y, gamma, s=s, rows_per_sample=rows_per_sample, p=p, seed=seed, row_step=row_step, out=out)
-
-
-def _ls_branch_grad(dy2, branch, gamma, s, rows_per_sample, site, want_sums, want_gamma):
-    """-> (gamma ⊙ g, its fp32 [D] column sums or None, the fp32 [D] column sums of g ⊙ branch or None) with g = s ⊙ m ⊙ dy2 / keep: the
-    gradient of the branch's exit GEMM output, that GEMM's bias gradient, and gamma's gradient"""
-    D, dev = dy2.shape[1], dy2.device
-    cs = torch.empty(D, dtype=torch.float32, device=dev) if want_sums else None
-    gs = torch.empty(D, dtype=torch.float32, device=dev) if want_gamma else None
-    p, seed, row_step = site if site is not None else (0.0, 0, 1)
-    if p >= 1.0:
-        for t in (cs, gs):
-            if t is not None:
-                t.zero_()
-        return torch.zeros_like(dy2), cs, gs
-    d = ops.layer_scale_grad(dy2, branch if want_gamma else None, gamma, s=s, rows_per_sample=rows_per_sample, p=p, seed=seed,
-                             row_step=row_step, c_colsum=cs, c_gamma=gs)
-    return d, cs, gs
+    def backward(self, dy2, branch, want_sums, want_gamma):
+        """dy2: the stream gradient; branch: what forward handed back to save
+        -> (the gradient of the exit GEMM's output, its fp32 [D] column sums = that GEMM's bias gradient or None, the fp32 [D] column sums
+        of g ⊙ branch = gamma's gradient or None); plain: dy2 itself and no sums"""
+        if self.plain:
+            return dy2, None, None
+        D, dev = dy2.shape[1], dy2.device
+        cs = torch.empty(D, dtype=torch.float32, device=dev) if want_sums else None
+        if self.gamma is None:
+            if self.site is None:
+                return ops.drop_path_scale(dy2, self.s, self.rows_per_sample, c_colsum=cs), cs, None
+            return _dropout(dy2, self.site, self.s, self.rows_per_sample, c_colsum=cs), cs, None
+        gs = torch.empty(D, dtype=torch.float32, device=dev) if want_gamma else None
+        p, seed, row_step = self.site if self.site is not None else (0.0, 0, 1)
+        if p >= 1.0:
+            for t in (cs, gs):
+                if t is not None:
+                    t.zero_()
+            return torch.zeros_like(dy2), cs, gs
+        d = ops.layer_scale_grad(dy2, branch if want_gamma else None, self.gamma, s=self.s, rows_per_sample=self.rows_per_sample, p=p,
+                                 seed=seed, row_step=row_step, c_colsum=cs, c_gamma=gs)
+        return d, cs, gs
 
 
 def _refuse_group_layer_scale(tp, g1, g2):
@@ -674,14 +754,14 @@ class LayerScaleFn(torch.autograd.Function):
         xc = x if x.is_contiguous() else x.contiguous()
         x2 = xc.view(-1, xc.shape[-1])
         ctx.save_for_backward(x2, gamma)
-        return ops.layer_scale_add(None, x2, gamma, out=torch.empty_like(x2)).view(x.shape)
+        return _Exit(gamma=gamma).forward(None, x2, True)[0].view(x.shape)
 
     @staticmethod
     def backward(ctx, dy):
         x2, gamma = ctx.saved_tensors
         dc = dy if dy.is_contiguous() else dy.contiguous()
         want_gamma = ctx.needs_input_grad[1]
-        dx, _, gs = _ls_branch_grad(dc.view(x2.shape), x2, gamma, None, 1, None, False, want_gamma)
+        dx, _, gs = _Exit(gamma=gamma).backward(dc.view(x2.shape), x2, False, want_gamma)
         return dx.view(dy.shape), (_bgrad_from(gamma, gs) if want_gamma else None)
 
 
@@ -708,20 +788,110 @@ class DropoutFn(torch.autograd.Function):
         return _dropout(dc.view(-1, dc.shape[-1]), ctx.site).view(dy.shape), None, None
 
 
-# Stochastic depth inside the fused Blocks.  A branch with a scale tensor s (fp32 [B], DropPath.draw) runs its exit GEMM without the
-# residual and ops.drop_path_add writes res + s ⊙ branch over the branch; a branch without one (s = None: eval, rate 0) keeps the residual
-# in the GEMM epilogue, launch for launch what it was.  Backward: the branch's output gradient is s ⊙ (stream gradient), and ITS column
-# sums are the bias gradient of proj / fc2 — not the column sums of the stream gradient that the LayerNorm backward kernels hand out.
-def _scaled_grad(dy2, s, rows_per_sample, want_sums):
-    """-> (s ⊙ dy2, its fp32 [D] column sums or None)"""
-    cs = torch.empty(dy2.shape[1], dtype=torch.float32, device=dy2.device) if want_sums else None
-    return ops.drop_path_scale(dy2, s, rows_per_sample, c_colsum=cs), cs
-
-
 def _refuse_group_drop_path(tp, s1, s2):
     if tp is not None and (s1 is not None or s2 is not None):
         raise NotImplementedError(f"drop_path under a tensor-parallel group (tp group {tp.group!r}, size {tp.size}): every rank of the group "
                                   "would need the same draw; not implemented")
+
+
+# ---------------------------------------------------------------------------------------------- the fused Block
+# One skeleton, x1 = x + exit1(proj(attn(norm1(x)))) ; y = x1 + exit2(fc2(gelu(fc1(norm2(x1))))), for two attention cores (_DenseCore,
+# _ClassRowCore).  Every token runs LayerNorm 1 and the qkv GEMM; with the class-row core everything from the attention on has one row
+# per sample: the residual of branch 1 is the strided class rows of x (ldr = N D), the dropout masks are those of dense row b N (site
+# row step N), and the class rows' residual gradient joins the dense dx inside the LayerNorm-1 backward (dres_period = N).
+_BlockIn = namedtuple("_BlockIn", "n1w n1b qkvw qkvb projw projb n2w n2b f1w f1b f2w f2b s1 s2 gamma1 gamma2 qnw qnb knw knb")
+_BlockIn.__doc__ = "the tensor arguments of a Block node besides x, under their forward names: what both nodes save whole"
+_BlockSaved = namedtuple("_BlockSaved", "mean1 rstd1 ln1 qkv o lse sqk mqk rqk x1 mean2 rstd2 ln2 h a b1 b2")
+_BlockSaved.__doc__ = ("what _block_forward keeps for backward (sqk, mqk, rqk: qk_norm's; b1, b2: the unscaled branch outputs under LayerScale); "
+                       "not saved under recompute, rebuilt bit for bit")
+
+
+def _block_exits(core, N, p, sites):
+    rows_per_sample = 1 if core.rows else N
+    return _Exit(p.s1, sites[0], p.gamma1, rows_per_sample), _Exit(p.s2, sites[2], p.gamma2, rows_per_sample)
+
+
+def _block_forward(core, x2, B, N, H, eps, c, p, tp, sites, keep, qkn):
+    """p: _BlockIn; c: parameter -> its compute-dtype tensor; sites: the dropout sites (proj, drop1, drop2); keep: a backward pass follows
+    -> y, _BlockSaved"""
+    exit1, exit2 = _block_exits(core, N, p, sites)
+    ln1, mean1, rstd1 = ops.layernorm_fwd(x2, c(p.n1w), c(p.n1b), eps)
+    # class rows of the stream: a [B, D] view, row stride N D (explicit D: an empty batch has no elements to infer it from)
+    res = x2.view(B, N, x2.shape[1])[:, 0] if core.rows else x2
+    x1, sa = _attn_fwd(ln1, B, N, H, c(p.qkvw), c(p.qkvb), c(p.projw), c(p.projb), res if exit1.plain else None, tp, qkn, keep, core)
+    x1, b1 = exit1.forward(res, x1, keep)
+    ln2, mean2, rstd2 = ops.layernorm_fwd(x1, c(p.n2w), c(p.n2b), eps)
+    y, sm = _mlp_fwd(ln2, c(p.f1w), c(p.f1b), c(p.f2w), c(p.f2b), x1 if exit2.plain else None, tp, drop1=sites[1])
+    y, b2 = exit2.forward(x1, y, keep)
+    return y, _BlockSaved(mean1, rstd1, ln1, *sa, x1, mean2, rstd2, ln2, *sm, b1, b2)
+
+
+def _block_enter(ctx, core, x, p, num_heads, eps, cdtype, tp, recompute, drop, save_branch, qk_eps):
+    """forward of both Block nodes: refusals, the skeleton, what is saved -> y ([B N, D], or [B, D] with the class-row core), (B, N, D)"""
+    _refuse_group_drop_path(tp, p.s1, p.s2)
+    _refuse_group_layer_scale(tp, p.gamma1, p.gamma2)
+    qkn = _qkn_of(p.qnw, p.qnb, p.knw, p.knb, qk_eps)
+    _refuse_group_qk_norm(tp, qkn)
+    xin = _as(x, cdtype)
+    B, N, D = xin.shape
+    ctx.sites = _block_sites(drop, tp, N if core.rows else 1)
+    x2 = xin.view(B * N, D)
+    keep = not recompute and any(ctx.needs_input_grad) and (save_branch is None or bool(save_branch))
+    y, saved = _block_forward(core, x2, B, N, num_heads, eps, lambda t: compute_param(t, cdtype), p, tp, ctx.sites, keep, qkn)
+    ctx.save_for_backward(x2, *(() if recompute else saved), *p)
+    ctx.meta = (B, N, num_heads, eps, cdtype, x.dtype, tp, qk_eps)
+    return y, (B, N, D)
+
+
+def _block_backward(ctx, core, dy, need):
+    """backward of both Block nodes; need: {forward argument name: requires a gradient} -> {name: gradient}"""
+    B, N, H, eps, cdtype, in_dtype, tp, qk_eps = ctx.meta
+    c = lambda t: compute_param(t, cdtype)
+    x2, *saved = ctx.saved_tensors
+    p = _BlockIn(*saved[-len(_BlockIn._fields):])
+    qkn = _qkn_of(p.qnw, p.qnb, p.knw, p.knb, qk_eps)
+    if len(saved) == len(p):                              # recompute: only the input was kept; the same launches rebuild the rest
+        _, v = _block_forward(core, x2, B, N, H, eps, c, p, tp, ctx.sites, True, qkn)
+    else:
+        v = _BlockSaved(*saved[:-len(p)])
+    exit1, exit2 = _block_exits(core, N, p, ctx.sites)
+    D = x2.shape[1]
+    dy2 = _as(dy, cdtype).reshape(B if core.rows else B * N, D)
+    wq = _queue_for(p.qkvw)
+    g = {}
+    # The column sums of the stream gradient dy that its producer (a LayerNorm backward) published are fc2's bias gradient for a plain
+    # exit; otherwise they are dropped (always taken: the slot is cleared) and the exit's own pass sums s ⊙ m ⊙ γ ⊙ dy / keep
+    published = _take_stream_colsum(wq, dy2)
+    dt2, cs2, gs2 = exit2.backward(dy2, v.b2, p.f2b is not None and need["f2b"], need["gamma2"])
+    g["gamma2"] = _bgrad_from(p.gamma2, gs2) if gs2 is not None else None
+    dln2, gm = _mlp_bwd(dt2, v.ln2, (v.h, v.a), c(p.f1w), c(p.f2w), p.f1w, p.f1b, p.f2w, p.f2b, need, tp, wq,
+                        dy2_colsum=published if exit2.plain else cs2, drop1=ctx.sites[1])
+    # LayerNorm backward also sums its output (the residual-stream gradient) over the tokens: proj's bias gradient for a plain exit ...
+    want_projb = p.projb is not None and need["projb"]
+    projb_done, pb_out, pb_acc = None, None, False
+    if exit1.plain and want_projb and (_BIAS_FROM_EPILOGUE or not core.bias_switch_gates):
+        pb_out, pb_acc = grad_target(p.projb)
+        if pb_out is None:
+            pb_out = torch.empty(p.projb.shape, dtype=torch.float32, device=dy2.device)
+        projb_done = (None if pb_acc else pb_out,)
+    dx1, g["n2w"], g["n2b"] = _ln_bwd(dln2, v.x1, c(p.n2w), v.mean2, v.rstd2, p.n2w, p.n2b, dres=dy2, dx_colsum=pb_out,     # + residual branch
+                                      dx_colsum_accumulate=pb_acc)
+    # ... unless the branch is scaled or masked: then the sums of the exit's pass are, and the LayerNorm backward above was not asked for any
+    dt1, cs1, gs1 = exit1.backward(dx1, v.b1, want_projb, need["gamma1"])
+    if not exit1.plain:
+        projb_done = (_bgrad_from(p.projb, cs1) if cs1 is not None else None,)
+    g["gamma1"] = _bgrad_from(p.gamma1, gs1) if gs1 is not None else None
+    dln1, ga = _attn_bwd(dt1, v.ln1, (v.qkv, v.o, v.lse, v.sqk, v.mqk, v.rqk), B, N, H, c(p.qkvw), c(p.projw), p.qkvw, p.qkvb, p.projw, p.projb,
+                         need, tp, wq, projb_done=projb_done, qkn=qkn, core=core)
+    # ... and, published for whoever receives dx, the fc2 bias gradient of the Block before this one
+    cs0 = torch.empty(D, dtype=torch.float32, device=dy2.device) if _BIAS_FROM_EPILOGUE else None
+    dx, g["n1w"], g["n1b"] = _ln_bwd(dln1, x2, c(p.n1w), v.mean1, v.rstd1, p.n1w, p.n1b, dres=dx1, dx_colsum=cs0,
+                                     dres_period=N if core.rows else 1)
+    if cs0 is not None and in_dtype == cdtype:
+        _publish_stream_colsum(wq, dx, cs0)
+    wq.end_block()                                   # the Block's 4 weight gradients: grouped launch now, or with the next Blocks'
+    g.update(ga, **gm, x=_ret_grad(dx.view(B, N, D), in_dtype))
+    return g
 
 
 class BlockFn(torch.autograd.Function):
@@ -729,31 +899,8 @@ class BlockFn(torch.autograd.Function):
     x1 = x + s1 ⊙ γ1 ⊙ proj(attn(norm1(x))) ; y = x1 + s2 ⊙ γ2 ⊙ fc2(gelu(fc1(norm2(x1)))) (γ: LayerScale, absent = Identity).  Without drop path (s1 = s2 = None): 7 forward
     launches, residual adds and the activation fused into GEMM epilogues; the residual-branch gradients are fused into the LayerNorm
     backward.  With a scale a branch costs one row pass more forward (drop_path_add) and one backward (drop_path_scale)."""
-
-    @staticmethod
-    def _run_forward(x2, B, N, num_heads, eps, c, params, tp, s1=None, s2=None, sites=(None, None, None), g1=None, g2=None, keep=False,
-                     qkn=None):
-        """g1, g2: the LayerScale gammas of the two branches or None; keep: their unscaled branch outputs b1, b2 are kept for backward, and
-        with qkn (see _attn_fwd) the un-normalised Q and K and their statistics"""
-        n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b = params
-        dproj, d1, d2 = sites
-        plain1, plain2 = s1 is None and dproj is None and g1 is None, s2 is None and d2 is None and g2 is None
-        b1 = b2 = None
-        ln1, mean1, rstd1 = ops.layernorm_fwd(x2, c(n1w), c(n1b), eps)
-        x1, sa = _attn_fwd(ln1, B, N, num_heads, c(qkvw), c(qkvb), c(projw), c(projb), x2 if plain1 else None, tp, qkn, keep)
-        if g1 is not None:
-            b1 = x1 if keep else None
-            x1 = _ls_branch_exit(x2, x1, g1, s1, N, dproj, keep)            # x1 = x + s1 ⊙ m ⊙ (gamma1 ⊙ branch) / keep
-        elif not plain1:
-            _branch_exit(x2, x1, s1, N, dproj)                              # x1 = x + s1 ⊙ m ⊙ branch / keep, over the branch
-        ln2, mean2, rstd2 = ops.layernorm_fwd(x1, c(n2w), c(n2b), eps)
-        y, sm = _mlp_fwd(ln2, c(f1w), c(f1b), c(f2w), c(f2b), x1 if plain2 else None, tp, drop1=d1)
-        if g2 is not None:
-            b2 = y if keep else None
-            y = _ls_branch_exit(x1, y, g2, s2, N, d2, keep)
-        elif not plain2:
-            _branch_exit(x1, y, s2, N, d2)
-        return y, (mean1, rstd1, ln1, *sa, x1, mean2, rstd2, ln2, *sm, b1, b2)
+    ARGS = _Slots("x", "n1w", "n1b", "qkvw", "qkvb", "projw", "projb", "n2w", "n2b", "f1w", "f1b", "f2w", "f2b", "num_heads", "eps", "cdtype",
+                  "tp", "recompute", "s1", "s2", "drop", "gamma1", "gamma2", "save_branch", "qnw", "qnb", "knw", "knb", "qk_eps")
 
     @staticmethod
     def forward(ctx, x, n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b, num_heads, eps, cdtype, tp=None, recompute=False,
@@ -779,85 +926,13 @@ class BlockFn(torch.autograd.Function):
         rebuild ln1, qkv, o, lse, x1, ln2, h, a (15 of the 16 token matrices a Block otherwise keeps), then proceeds as usual.  The
         rebuilt tensors are bit-identical (no atomics, fixed reduction orders), so gradients equal the non-checkpointed ones exactly;
         the scales are kept with the input, so the rebuilt forward uses the same draw."""
-        _refuse_group_drop_path(tp, s1, s2)
-        _refuse_group_layer_scale(tp, gamma1, gamma2)
-        qkn = _qkn_of(qnw, qnb, knw, knb, qk_eps)
-        _refuse_group_qk_norm(tp, qkn)
-        ctx.qk_eps = qk_eps
-        ctx.sites = sites = _block_sites(drop, tp, 1)
-        xin = _as(x, cdtype)
-        B, N, D = xin.shape
-        x2 = xin.view(B * N, D)
-        c = lambda p: compute_param(p, cdtype)
-        params = (n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b)
-        keep = not recompute and any(ctx.needs_input_grad) and (save_branch is None or bool(save_branch))
-        y, saved = BlockFn._run_forward(x2, B, N, num_heads, eps, c, params, tp, s1, s2, sites, gamma1, gamma2, keep, qkn)
-        if recompute:
-            ctx.save_for_backward(x2, *params, s1, s2, gamma1, gamma2, qnw, qnb, knw, knb)
-        else:
-            ctx.save_for_backward(x2, *saved, *params, s1, s2, gamma1, gamma2, qnw, qnb, knw, knb)
-        ctx.meta = (B, N, num_heads, cdtype, x.dtype, tp)
-        ctx.recompute, ctx.eps = recompute, eps
-        return y.view(B, N, D)
+        p = _BlockIn(n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b, s1, s2, gamma1, gamma2, qnw, qnb, knw, knb)
+        y, shape = _block_enter(ctx, _DenseCore, x, p, num_heads, eps, cdtype, tp, recompute, drop, save_branch, qk_eps)
+        return y.view(shape)
 
     @staticmethod
     def backward(ctx, dy):
-        B, N, H, cdtype, in_dtype, tp = ctx.meta
-        c = lambda p: compute_param(p, cdtype)
-        if ctx.recompute:
-            x2, *params, s1, s2, g1, g2, qnw, qnb, knw, knb = ctx.saved_tensors
-            _, saved = BlockFn._run_forward(x2, B, N, H, ctx.eps, c, tuple(params), tp, s1, s2, ctx.sites, g1, g2, True,
-                                            _qkn_of(qnw, qnb, knw, knb, ctx.qk_eps))
-            (mean1, rstd1, ln1, qkv, o, lse, sqk, mqk, rqk, x1, mean2, rstd2, ln2, h, a, b1, b2) = saved
-            n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b = params
-        else:
-            (x2, mean1, rstd1, ln1, qkv, o, lse, sqk, mqk, rqk, x1, mean2, rstd2, ln2, h, a, b1, b2,
-             n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b, s1, s2, g1, g2, qnw, qnb, knw, knb) = ctx.saved_tensors
-        qkn = _qkn_of(qnw, qnb, knw, knb, ctx.qk_eps)
-        need = ctx.needs_input_grad
-        dproj, d1, d2 = ctx.sites
-        dy2 = _as(dy, cdtype).reshape(x2.shape)
-        wq = _queue_for(qkvw)
-        g_g1 = g_g2 = None
-        dt2, cs2 = dy2, _take_stream_colsum(wq, dy2)       # always taken: the slot is cleared
-        if g2 is not None:
-            # as below, and the sums are those of gamma2 ⊙ g; gamma2's own gradient comes out of the same pass
-            dt2, cs2, gs2 = _ls_branch_grad(dy2, b2, g2, s2, N, d2, f2b is not None and need[12], need[22])
-            g_g2 = _bgrad_from(g2, gs2) if gs2 is not None else None
-        elif s2 is not None or d2 is not None:
-            # the published sums are those of the unscaled, unmasked dy: not this fc2's bias gradient; the sums of s2 ⊙ m ⊙ dy / keep are
-            dt2, cs2 = _branch_grad(dy2, s2, N, d2, f2b is not None and need[12])
-        dln2, gm = _mlp_bwd(dt2, ln2, (h, a), c(f1w), c(f2w), f1w, f1b, f2w, f2b, need[9:13], tp, wq, dy2_colsum=cs2, drop1=d1)
-        # LayerNorm backward also sums its output (the residual-stream gradient) over the tokens: proj's bias gradient here ...
-        projb_done = None
-        pb_out, pb_acc = None, False
-        if s1 is None and dproj is None and g1 is None and _BIAS_FROM_EPILOGUE and projb is not None and need[6]:
-            pb_out, pb_acc = grad_target(projb)
-            if pb_out is None:
-                pb_out = torch.empty(projb.shape, dtype=torch.float32, device=dy2.device)
-            projb_done = (None if pb_acc else pb_out,)
-        dx1, g_n2w, g_n2b = _ln_bwd(dln2, x1, c(n2w), mean2, rstd2, n2w, n2b, dres=dy2, dx_colsum=pb_out,       # + residual branch
-                                    dx_colsum_accumulate=pb_acc)
-        dt1 = dx1
-        if g1 is not None:
-            dt1, cs1, gs1 = _ls_branch_grad(dx1, b1, g1, s1, N, dproj, projb is not None and need[6], need[21])
-            projb_done = (_bgrad_from(projb, cs1) if cs1 is not None else None,)
-            g_g1 = _bgrad_from(g1, gs1) if gs1 is not None else None
-        elif s1 is not None or dproj is not None:
-            # ... unless the branch is scaled or masked: then the sums of s1 ⊙ m ⊙ dx1 / keep are, and the LayerNorm backward above was not
-            # asked for any
-            dt1, cs1 = _branch_grad(dx1, s1, N, dproj, projb is not None and need[6])
-            projb_done = (_bgrad_from(projb, cs1) if cs1 is not None else None,)
-        dln1, ga, *gq = _attn_bwd(dt1, ln1, (qkv, o, lse, sqk, mqk, rqk), B, N, H, c(qkvw), c(projw), qkvw, qkvb, projw, projb, need[3:7], tp,
-                                  wq, projb_done=projb_done, qkn=qkn, qkn_needs=need[24:28])
-        # ... and, published for whoever receives dx, the fc2 bias gradient of the Block before this one
-        cs0 = torch.empty(x2.shape[1], dtype=torch.float32, device=dy2.device) if _BIAS_FROM_EPILOGUE else None
-        dx, g_n1w, g_n1b = _ln_bwd(dln1, x2, c(n1w), mean1, rstd1, n1w, n1b, dres=dx1, dx_colsum=cs0)
-        if cs0 is not None and in_dtype == cdtype:
-            _publish_stream_colsum(wq, dx, cs0)
-        wq.end_block()                                   # the Block's 4 weight gradients: grouped launch now, or with the next Blocks'
-        return ((_ret_grad(dx.view(B, N, -1), in_dtype), g_n1w, g_n1b) + ga + (g_n2w, g_n2b) + gm + (None,) * 8 + (g_g1, g_g2, None)
-                + (gq[0] if gq else (None,) * 4) + (None,))
+        return BlockFn.ARGS.grads(**_block_backward(ctx, _DenseCore, dy, BlockFn.ARGS.needs(ctx)))
 
 
 TAIL_ROWS = os.environ.get("UCFVIT_TAIL_ROWS", "1") != "0"     # A/B switch: 0 = the last Block runs dense like every other
@@ -872,36 +947,7 @@ class TailBlockFn(torch.autograd.Function):
     class rows of x (ldr = N D).  Backward: the same compact chain, weight gradients queued with B reduction rows; the gradient turns
     dense again at dK / dV (ops.attention_rows_bwd) and the class rows' residual gradient joins the dense dx inside the LayerNorm-1
     backward (dres_period = N), rounded once like the dense Block's."""
-
-    @staticmethod
-    def _run_forward(x2, B, N, num_heads, eps, c, params, s1=None, s2=None, sites=(None, None, None), g1=None, g2=None, keep=False, qkn=None):
-        n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b = params
-        dproj, d1, d2 = sites
-        plain1, plain2 = s1 is None and dproj is None and g1 is None, s2 is None and d2 is None and g2 is None
-        b1 = b2 = None
-        D = x2.shape[1]
-        dh = D // num_heads
-        ln1, mean1, rstd1 = ops.layernorm_fwd(x2, c(n1w), c(n1b), eps)
-        qkv = ops.linear_fwd(ln1, c(qkvw), c(qkvb))
-        sq = (None, None, None)
-        if qkn is not None:                                                          # the whole buffer: the class rows' queries need every key
-            sq = ops.qk_norm_fwd(qkv, qkn[0], qkn[1], qkn[2], qkn[3], num_heads, dh, qkn[4], save=keep)
-        o, lse = ops.attention_rows_fwd(qkv, B, N, num_heads, dh, dh ** -0.5, 0)
-        xc = x2.view(B, N, D)[:, 0]                                                  # class rows of the stream: a [B, D] view, row stride N D
-        x1 = ops.linear_fwd(o, c(projw), c(projb), residual=xc if plain1 else None)
-        if g1 is not None:
-            b1 = x1 if keep else None
-            x1 = _ls_branch_exit(xc, x1, g1, s1, 1, dproj, keep)                     # ldr = N D, one row per sample, row_step = N in the site
-        elif not plain1:
-            _branch_exit(xc, x1, s1, 1, dproj)                                       # one row per sample; the mask of dense row b N
-        ln2, mean2, rstd2 = ops.layernorm_fwd(x1, c(n2w), c(n2b), eps)
-        y, (h, a) = _mlp_fwd(ln2, c(f1w), c(f1b), c(f2w), c(f2b), x1 if plain2 else None, drop1=d1)
-        if g2 is not None:
-            b2 = y if keep else None
-            y = _ls_branch_exit(x1, y, g2, s2, 1, d2, keep)
-        elif not plain2:
-            _branch_exit(x1, y, s2, 1, d2)
-        return y, (mean1, rstd1, ln1, qkv, o, lse, *sq, x1, mean2, rstd2, ln2, h, a, b1, b2)
+    ARGS = _Slots(*(n for n in BlockFn.ARGS.names if n != "tp"))
 
     @staticmethod
     def forward(ctx, x, n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b, num_heads, eps, cdtype, recompute=False,
@@ -911,101 +957,12 @@ class TailBlockFn(torch.autograd.Function):
         gamma1, gamma2, save_branch: the LayerScale parameters and the grad-mode flag as in BlockFn, applied to the class rows;
         s1, s2: the drop-path scales of the two branches as in BlockFn, one row per sample from the attention on;
         drop: BlockFn's dropout argument; the mask index steps by N rows, so class row b draws the mask of row b N of the dense Block"""
-        xin = _as(x, cdtype)
-        B, N, D = xin.shape
-        ctx.sites = sites = _block_sites(drop, None, N)
-        qkn = _qkn_of(qnw, qnb, knw, knb, qk_eps)
-        ctx.qk_eps = qk_eps
-        x2 = xin.view(B * N, D)
-        c = lambda p: compute_param(p, cdtype)
-        params = (n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b)
-        keep = not recompute and any(ctx.needs_input_grad) and (save_branch is None or bool(save_branch))
-        y, saved = TailBlockFn._run_forward(x2, B, N, num_heads, eps, c, params, s1, s2, sites, gamma1, gamma2, keep, qkn)
-        if recompute:
-            ctx.save_for_backward(x2, *params, s1, s2, gamma1, gamma2, qnw, qnb, knw, knb)
-        else:
-            ctx.save_for_backward(x2, *saved, *params, s1, s2, gamma1, gamma2, qnw, qnb, knw, knb)
-        ctx.meta = (B, N, num_heads, cdtype, x.dtype)
-        ctx.recompute, ctx.eps = recompute, eps
-        return y
+        p = _BlockIn(n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b, s1, s2, gamma1, gamma2, qnw, qnb, knw, knb)
+        return _block_enter(ctx, _ClassRowCore, x, p, num_heads, eps, cdtype, None, recompute, drop, save_branch, qk_eps)[0]
 
     @staticmethod
     def backward(ctx, dy):
-        B, N, H, cdtype, in_dtype = ctx.meta
-        c = lambda p: compute_param(p, cdtype)
-        if ctx.recompute:
-            x2, *params, s1, s2, g1, g2, qnw, qnb, knw, knb = ctx.saved_tensors
-            _, saved = TailBlockFn._run_forward(x2, B, N, H, ctx.eps, c, tuple(params), s1, s2, ctx.sites, g1, g2, True,
-                                                _qkn_of(qnw, qnb, knw, knb, ctx.qk_eps))
-            (mean1, rstd1, ln1, qkv, o, lse, sqk, mqk, rqk, x1, mean2, rstd2, ln2, h, a, b1, b2) = saved
-            n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b = params
-        else:
-            (x2, mean1, rstd1, ln1, qkv, o, lse, sqk, mqk, rqk, x1, mean2, rstd2, ln2, h, a, b1, b2,
-             n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, f1w, f1b, f2w, f2b, s1, s2, g1, g2, qnw, qnb, knw, knb) = ctx.saved_tensors
-        qkn = _qkn_of(qnw, qnb, knw, knb, ctx.qk_eps)
-        g_qkn = (None,) * 4
-        need = ctx.needs_input_grad
-        D = x2.shape[1]
-        dh = D // H
-        dy2 = _as(dy, cdtype).reshape(B, D)
-        wq = _queue_for(qkvw)
-        dproj, d1, d2 = ctx.sites
-        g_g1 = g_g2 = None
-        dt2, cs2 = dy2, _take_stream_colsum(wq, dy2)
-        if g2 is not None:
-            dt2, cs2, gs2 = _ls_branch_grad(dy2, b2, g2, s2, 1, d2, f2b is not None and need[12], need[21])
-            g_g2 = _bgrad_from(g2, gs2) if gs2 is not None else None
-        elif s2 is not None or d2 is not None:             # as in BlockFn: the published sums of the unscaled dy are dropped
-            dt2, cs2 = _branch_grad(dy2, s2, 1, d2, f2b is not None and need[12])
-        dln2, gm = _mlp_bwd(dt2, ln2, (h, a), c(f1w), c(f2w), f1w, f1b, f2w, f2b, need[9:13], None, wq, dy2_colsum=cs2, drop1=d1)
-        pb_out, pb_acc, g_projb = None, False, None
-        if s1 is None and dproj is None and g1 is None and projb is not None and need[6]:
-            pb_out, pb_acc = grad_target(projb)
-            if pb_out is None:
-                pb_out = torch.empty(projb.shape, dtype=torch.float32, device=dy2.device)
-            g_projb = None if pb_acc else pb_out
-        dx1, g_n2w, g_n2b = _ln_bwd(dln2, x1, c(n2w), mean2, rstd2, n2w, n2b, dres=dy2, dx_colsum=pb_out, dx_colsum_accumulate=pb_acc)
-        dt1 = dx1
-        if g1 is not None:
-            dt1, cs1, gs1 = _ls_branch_grad(dx1, b1, g1, s1, 1, dproj, projb is not None and need[6], need[20])
-            g_projb = _bgrad_from(projb, cs1) if cs1 is not None else None
-            g_g1 = _bgrad_from(g1, gs1) if gs1 is not None else None
-        elif s1 is not None or dproj is not None:
-            dt1, cs1 = _branch_grad(dx1, s1, 1, dproj, projb is not None and need[6])
-            g_projb = _bgrad_from(projb, cs1) if cs1 is not None else None
-        g_projw = _wgrad(projw, dt1, o, wq) if need[5] else None
-        want_b = qkvb is not None and need[4]
-        if qkn is not None:
-            # as in _attn_bwd: the Q and K thirds of the bias gradient are the column sums of what qk_norm_bwd writes, the V third those of dO
-            gb, acc = grad_target(qkvb) if want_b else (None, False)
-            if want_b and gb is None:
-                gb, acc = torch.empty(3 * D, dtype=torch.float32, device=dy2.device), False
-            do = _dgrad(dt1, projw, c(projw), c_colsum=gb[2 * D:] if want_b else None, c_colsum_accumulate=acc)
-            dqkv = ops.attention_rows_bwd(qkv, o, do, lse, B, N, H, dh, dh ** -0.5, 0)
-            g_qkn = _qkn_bwd(dqkv, (sqk, mqk, rqk), qkn, H, dh, need[23:27], gb[:2 * D] if want_b else None, acc)
-            g_qkvb = (None if acc else gb) if want_b else None
-        elif want_b:
-            # Q third: dq of every image, summed; K third: 0 exactly; V third: the column sums of the compact dO (see _attn_bwd)
-            gb, acc = grad_target(qkvb)
-            if gb is None:
-                gb, acc = torch.empty(3 * D, dtype=torch.float32, device=dy2.device), False
-            do = _dgrad(dt1, projw, c(projw), c_colsum=gb[2 * D:], c_colsum_accumulate=acc)
-            dqkv, part = ops.attention_rows_bwd(qkv, o, do, lse, B, N, H, dh, dh ** -0.5, 0, want_colsum=True)
-            ops.reduce_rows(part, gb[:2 * D], accumulate=acc)
-            g_qkvb = None if acc else gb
-        else:
-            do = _dgrad(dt1, projw, c(projw))
-            dqkv = ops.attention_rows_bwd(qkv, o, do, lse, B, N, H, dh, dh ** -0.5, 0)
-            g_qkvb = None
-        g_qkvw = _wgrad(qkvw, dqkv, ln1, wq) if need[3] else None
-        dln1 = _dgrad(dqkv, qkvw, c(qkvw))
-        cs0 = torch.empty(D, dtype=torch.float32, device=dy2.device) if _BIAS_FROM_EPILOGUE else None
-        dx, g_n1w, g_n1b = _ln_bwd(dln1, x2, c(n1w), mean1, rstd1, n1w, n1b, dres=dx1, dx_colsum=cs0, dres_period=N)
-        if cs0 is not None and in_dtype == cdtype:
-            _publish_stream_colsum(wq, dx, cs0)           # the fc2 bias gradient of the Block before this one
-        wq.end_block()
-        return ((_ret_grad(dx.view(B, N, D), in_dtype), g_n1w, g_n1b, g_qkvw, g_qkvb, g_projw, g_projb, g_n2w, g_n2b) + gm + (None,) * 7
-                + (g_g1, g_g2, None) + g_qkn + (None,))
+        return TailBlockFn.ARGS.grads(**_block_backward(ctx, _ClassRowCore, dy, TailBlockFn.ARGS.needs(ctx)))
 
 
 class PatchEmbedFn(torch.autograd.Function):

@@ -50,14 +50,8 @@ class Mlp(_S.Mlp):
         self.tensor_par_size, self.tensor_par_group = tensor_par_size, tensor_par_group
         _mark_sharded(self, tensor_par_size)
 
-    def forward(self, x):
-        if not self._fusable():
-            raise NotImplementedError("HIP Mlp implements fc1 -> exact GELU -> fc2 (the reference configuration)")
-        args = (x, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, _cd(self), _tp(self.tensor_par_size, self.tensor_par_group))
-        d1, d2 = _draw_dropout(self.drop1), _draw_dropout(self.drop2)
-        if d1 is None and d2 is None:
-            return HF.MlpFn.apply(*args)
-        return HF.MlpFn.apply(*args, d1, d2)                       # refused under a tensor-parallel group (HF._site)
+    def _tp(self):
+        return _tp(self.tensor_par_size, self.tensor_par_group)    # dropout is refused under a tensor-parallel group (HF._site)
 
 
 class Attention(nn.Module):
@@ -87,14 +81,8 @@ class Attention(nn.Module):
         return _qk_norm_problem(self) is None
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        _no_dropout(self.attn_drop.p, self.training, "attn_drop")
-        qk = _qk_norm_args(self)                                       # raises for norms the hot path does not run, and under a group
-        args = (x, self.qkv.weight, self.qkv.bias, self.proj.weight, self.proj.bias, self.num_heads, _cd(self),
-                _tp(self.tensor_par_size, self.tensor_par_group))
-        d = _draw_dropout(self.proj_drop)
-        if qk:
-            return HF.AttentionFn.apply(*args, d, *qk, torch.is_grad_enabled())
-        return HF.AttentionFn.apply(*args) if d is None else HF.AttentionFn.apply(*args, d)     # refused under a group (HF._site)
+        # qk_norm and dropout are refused under a group (_qk_norm_args, HF._site)
+        return _S._attention_apply(self, x, _tp(self.tensor_par_size, self.tensor_par_group))
 
 
 class Block(nn.Module):
@@ -130,24 +118,14 @@ class Block(nn.Module):
                 and type(self.attn) is Attention and self.attn._fusable() and type(self.mlp) is Mlp and self.mlp._fusable()
                 and self.mlp.fc1.out_features % 8 == 0)
 
+    _fused_args = _S.Block._fused_args                   # the same argument list and draws; forward adds the group's handle
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self._fusable() and x.dim() == 3:
-            a, m = self.attn, self.mlp
-            _no_dropout(a.attn_drop.p, self.training, "attn_drop")
+            _no_dropout(self.attn.attn_drop.p, self.training, "attn_drop")
             if self.training:
-                _refuse_group_dropout(a.proj_drop.p, self.tensor_par_size, self.tensor_par_group, "proj_drop")
-            args = (x, self.norm1.weight, self.norm1.bias, a.qkv.weight, a.qkv.bias, a.proj.weight, a.proj.bias,
-                    self.norm2.weight, self.norm2.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias,
-                    a.num_heads, self.norm1.eps, _cd(self), _tp(self.tensor_par_size, self.tensor_par_group),
-                    getattr(self, "activation_checkpointing", False) and torch.is_grad_enabled())
-            s1, s2 = _draw_drop_path(self.drop_path1, x), _draw_drop_path(self.drop_path2, x)      # None under a tensor-parallel group
-            drop = _block_dropout(a, m)
-            g1, g2 = _block_gammas(self)                                                           # None under a tensor-parallel group
-            qk = _qk_norm_args(a)                                                                  # refused under a tensor-parallel group
-            if g1 is not None or qk:
-                return HF.BlockFn.apply(*args, s1, s2, drop, g1, g2, torch.is_grad_enabled(), *qk)
-            if s1 is None and s2 is None and drop is None:
-                return HF.BlockFn.apply(*args)
-            return HF.BlockFn.apply(*args, s1, s2, drop)
+                _refuse_group_dropout(self.attn.proj_drop.p, self.tensor_par_size, self.tensor_par_group, "proj_drop")
+            # drop path, LayerScale and qk_norm do not exist under a tensor-parallel group (refused in __init__): None there
+            return HF.BlockFn.apply(*self._fused_args(x, False, _tp(self.tensor_par_size, self.tensor_par_group)))
         x = x + self.drop_path1(self.ls1(self.attn(self.norm1(x))))
         return x + self.drop_path2(self.ls2(self.mlp(self.norm2(x))))

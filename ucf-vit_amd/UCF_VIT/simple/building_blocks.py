@@ -214,13 +214,13 @@ def _qk_norm_problem(attn):
 
 
 def _qk_norm_args(attn):
-    """the trailing arguments of the fused Functions: (q_norm.weight, q_norm.bias, k_norm.weight, k_norm.bias, eps), or () without qk_norm;
-    raises with the failed condition for norms the hot path does not run"""
+    """the qk_norm arguments of the fused Functions: (q_norm.weight, q_norm.bias, k_norm.weight, k_norm.bias, eps), five Nones without
+    qk_norm; raises with the failed condition for norms the hot path does not run"""
     why = _qk_norm_problem(attn)
     if why is not None:
         raise NotImplementedError(f"qk_norm is not on the HIP hot path for this Attention: {why}")
     if isinstance(attn.q_norm, nn.Identity):
-        return ()
+        return (None,) * 5
     tps = getattr(attn, "tensor_par_size", 1)
     if tps > 1:
         raise NotImplementedError(f"Attention(qk_norm=True) under a tensor-parallel group (tensor_par_group={getattr(attn, 'tensor_par_group', None)!r}, "
@@ -301,14 +301,23 @@ class Mlp(nn.Module):
         return (isinstance(self.act, nn.GELU) and getattr(self.act, "approximate", "none") == "none"
                 and isinstance(self.norm, nn.Identity))
 
+    def _tp(self):
+        """the tensor-parallel handle of HF.MlpFn: none here, fsdp.Mlp has one"""
+        return None
+
     def forward(self, x):
         if not self._fusable():
             raise NotImplementedError("HIP Mlp implements fc1 -> exact GELU -> fc2 (the reference configuration)")
-        args = (x, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, _cd(self))
         d1, d2 = _draw_dropout(self.drop1), _draw_dropout(self.drop2)           # two seeds, drop1 first
-        if d1 is None and d2 is None:
-            return HF.MlpFn.apply(*args)
-        return HF.MlpFn.apply(*args, None, d1, d2)
+        return HF.MlpFn.apply(x, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, _cd(self), self._tp(), d1, d2)
+
+
+def _attention_apply(attn, x, tp):
+    """HF.AttentionFn for simple.Attention (tp None) and fsdp.Attention (its tensor-parallel handle): one spelling of the call"""
+    _no_dropout(attn.attn_drop.p, attn.training, "attn_drop")
+    qk = _qk_norm_args(attn)                                           # raises, naming the condition, for norms the hot path does not run
+    return HF.AttentionFn.apply(x, attn.qkv.weight, attn.qkv.bias, attn.proj.weight, attn.proj.bias, attn.num_heads, _cd(attn), tp,
+                                _draw_dropout(attn.proj_drop), *qk, torch.is_grad_enabled())
 
 
 class Attention(nn.Module):
@@ -336,13 +345,7 @@ class Attention(nn.Module):
         return _qk_norm_problem(self) is None
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        _no_dropout(self.attn_drop.p, self.training, "attn_drop")
-        qk = _qk_norm_args(self)                                       # raises, naming the condition, for norms the hot path does not run
-        args = (x, self.qkv.weight, self.qkv.bias, self.proj.weight, self.proj.bias, self.num_heads, _cd(self))
-        d = _draw_dropout(self.proj_drop)
-        if qk:
-            return HF.AttentionFn.apply(*args, None, d, *qk, torch.is_grad_enabled())
-        return HF.AttentionFn.apply(*args) if d is None else HF.AttentionFn.apply(*args, None, d)
+        return _attention_apply(self, x, None)
 
 
 class Block(nn.Module):
@@ -380,42 +383,28 @@ class Block(nn.Module):
                 and type(self.mlp) is Mlp and self.mlp._fusable()
                 and self.mlp.fc1.out_features % 8 == 0)
 
+    def _fused_args(self, x, tail, tp=None):
+        """the argument list of HF.TailBlockFn (tail) or of HF.BlockFn (tp: its tensor-parallel handle, fsdp.Block passes one).  This
+        pass's draws are made here, in a fixed order: the drop-path scales s1, s2, then the seeds of proj_drop, Mlp.drop1, Mlp.drop2"""
+        a, m = self.attn, self.mlp
+        _no_dropout(a.attn_drop.p, self.training, "attn_drop")
+        recompute = getattr(self, "activation_checkpointing", False) and torch.is_grad_enabled()
+        s1, s2 = _draw_drop_path(self.drop_path1, x), _draw_drop_path(self.drop_path2, x)      # two independent draws, s1 first
+        drop = _block_dropout(a, m)
+        return ((x, self.norm1.weight, self.norm1.bias, a.qkv.weight, a.qkv.bias, a.proj.weight, a.proj.bias,
+                 self.norm2.weight, self.norm2.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias, a.num_heads, self.norm1.eps, _cd(self))
+                + (() if tail else (tp,)) + (recompute, s1, s2, drop, *_block_gammas(self), torch.is_grad_enabled(), *_qk_norm_args(a)))
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self._fusable() and x.dim() == 3:
-            a, m = self.attn, self.mlp
-            _no_dropout(a.attn_drop.p, self.training, "attn_drop")
-            args = (x, self.norm1.weight, self.norm1.bias, a.qkv.weight, a.qkv.bias, a.proj.weight, a.proj.bias,
-                    self.norm2.weight, self.norm2.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias,
-                    a.num_heads, self.norm1.eps, _cd(self), None, self.activation_checkpointing and torch.is_grad_enabled())
-            s1, s2 = _draw_drop_path(self.drop_path1, x), _draw_drop_path(self.drop_path2, x)      # two independent draws, s1 first
-            drop = _block_dropout(a, m)
-            g1, g2 = _block_gammas(self)
-            qk = _qk_norm_args(a)
-            if g1 is not None or qk:
-                return HF.BlockFn.apply(*args, s1, s2, drop, g1, g2, torch.is_grad_enabled(), *qk)
-            if s1 is None and s2 is None and drop is None:
-                return HF.BlockFn.apply(*args)
-            return HF.BlockFn.apply(*args, s1, s2, drop)
+            return HF.BlockFn.apply(*self._fused_args(x, False))
         x = x + self.drop_path1(self.ls1(self.attn(self.norm1(x))))
         x = x + self.drop_path2(self.ls2(self.mlp(self.norm2(x))))
         return x
 
     def forward_class_rows(self, x: torch.Tensor) -> torch.Tensor:
         """forward(x)[:, 0] computed without the other rows (HF.TailBlockFn); the caller checked _fusable()"""
-        a, m = self.attn, self.mlp
-        _no_dropout(a.attn_drop.p, self.training, "attn_drop")
-        args = (x, self.norm1.weight, self.norm1.bias, a.qkv.weight, a.qkv.bias, a.proj.weight, a.proj.bias,
-                self.norm2.weight, self.norm2.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias,
-                a.num_heads, self.norm1.eps, _cd(self), self.activation_checkpointing and torch.is_grad_enabled())
-        s1, s2 = _draw_drop_path(self.drop_path1, x), _draw_drop_path(self.drop_path2, x)
-        drop = _block_dropout(a, m)
-        g1, g2 = _block_gammas(self)
-        qk = _qk_norm_args(a)
-        if g1 is not None or qk:
-            return HF.TailBlockFn.apply(*args, s1, s2, drop, g1, g2, torch.is_grad_enabled(), *qk)
-        if s1 is None and s2 is None and drop is None:
-            return HF.TailBlockFn.apply(*args)
-        return HF.TailBlockFn.apply(*args, s1, s2, drop)
+        return HF.TailBlockFn.apply(*self._fused_args(x, True))
 
 
 class MyUnetBlock(nn.Module):
