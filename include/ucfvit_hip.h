@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define UCFVIT_ABI_VERSION 24 /* still 24 with the dropout, LayerScale and QK-norm entry points (ucfvit_dropout*, ucfvit_layer_scale_*, ucfvit_qk_norm_*): symbols were only added */
+#define UCFVIT_ABI_VERSION 24 /* still 24 with the dropout, LayerScale, QK-norm and DDPM entry points (ucfvit_dropout*, ucfvit_layer_scale_*, ucfvit_qk_norm_*, ucfvit_ddpm_*, ucfvit_time_tokens_*, ucfvit_relu_dropout*): symbols were only added */
 
 #define UCFVIT_OK 0
 #define UCFVIT_ERR_INVALID_ARGUMENT (-1)
@@ -833,6 +833,52 @@ int ucfvit_qk_norm_fwd(void* qkv, const float* gamma_q, const float* beta_q, con
                        float* mean, float* rstd, int64_t rows, int64_t H, int64_t dh, float eps, int dtype, void* stream);
 int ucfvit_qk_norm_bwd(void* dqkv, const void* saved_qk, const float* gamma_q, const float* gamma_k, const float* mean, const float* rstd,
                        float* param_partial, float* colsum_partial, int64_t rows, int64_t H, int64_t dh, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * DDPM training and sampling around the DiffusionVIT (csrc/diffusion.hip; the token kernels in csrc/elementwise.hip).  Streaming passes:
+ * fp32 arithmetic with every product and sum rounded on its own in the order written below (no fma contraction), one rounding to the
+ * output type; 16-byte accesses where the sizes and pointers allow, else an element path with the same bits; no atomics, the same bits on
+ * every call.  Arguments are checked on the host before any HIP call.
+ *
+ * ucfvit_ddpm_q_sample: the forward noising out[b][i] = fl(fl(sqrt_ab[t[b]] * x0[b][i]) + fl(sqrt_1mab[t[b]] * eps[b][i])) of B samples of
+ *   n_per_sample fp32 elements each (an NCHW(D) image flattened per sample).  t is int64 [B] ON THE DEVICE, the tables fp32 [T] on the
+ *   device.  The host cannot see t, so the kernel clamps every t[b] into [0, T - 1]: an out-of-range step reads the first / last table
+ *   entry and never outside the tables.  out may be x0 (or eps).  The 16-byte path needs n_per_sample % 4 == 0 and 16-byte aligned x0, eps,
+ *   out.  Checked: null pointers, B < 0, n_per_sample < 1, B n_per_sample >= 2^40, T < 1, pointers not aligned to their element.
+ *
+ * ucfvit_time_tokens_fwd / _bwd: ucfvit_tokens_fwd / _bwd with one more operand, the time row temb [B][D] of the dtype, one per sample:
+ *   out[b][0] = (cls + pos[0]) + temb[b] if has_cls, out[b][j + pre] = (patches[b][j] + pos[j + pre]) + temb[b]; the parentheses are the
+ *   order of the fp32 adds; pos may be NULL (then one add).  With temb == 0 the result is ucfvit_tokens_fwd's bit for bit.
+ *   bwd: dpatches = dout[:, pre:] (may be NULL), dpos / dcls (may be NULL) exactly as ucfvit_tokens_bwd writes them, `accumulate` included
+ *   (it does not apply to dtemb), and dtemb fp32 [B][D] = sum_n dout[b][n][:] over all L + pre rows: the 8 rows of a chunk are added by a
+ *   fixed butterfly (rows r and r ^ 1, then ^ 2, then ^ 4), the chunk sums go to `workspace` (ucfvit_time_tokens_bwd_workspace bytes, fp32 [chunks][B][D]) and ucfvit_reduce_rows folds
+ *   them in chunk order.  dout is read once for all four results.  Same shape rules as the token kernels (D a multiple of 4 (fp32) / 8
+ *   (bf16), 16-byte aligned token pointers), B D < 2^31.  The workspace query returns 0 for sizes the kernel refuses.
+ *
+ * ucfvit_relu_dropout / _bwd: the hidden layer of the time MLP on [rows][D]: y = f * m(r, c) * relu(x), dx = f * m(r, c) * [x > 0] * dy,
+ *   with EXACTLY the mask m and the factor f = 1.0f / (1.0f - (float)p) of the dropout section above at row_step = 1 and without a
+ *   drop-path scale (index r D + c, Philox4x32-10, dropped iff w < T).  p must be inside [0, 1); p == 0 is plain ReLU (eval): no mask is
+ *   generated and no product by f is made.  relu(x) is x where x > 0 and +0 elsewhere, so x = NaN gives 0 in both directions; a dropped or
+ *   inactive element is a select: NaN / Inf under it do not pass.  out may be x, dx may be dy.  The backward pass reads the pre-activation x
+ *   and recomputes the mask from the seed.  Checked: null pointers, D, rows (rows < 2^30), p, dtype.
+ *
+ * ucfvit_ddpm_step: one reverse (ancestral) step on the image without materialising unpatchify(pred):
+ *   out = fl(fl(c1 * fl(x - fl(c2 * e))) + fl(sigma * z)), e[b][c][pixel] read from pred [B][L][p^nd C] (`dtype`) in the patch order that
+ *   ucfvit_patch_mse documents, (ph, pw[, pd], c): the reference's unpatchify.  x, z, out are fp32 NCHW(D); dims = {H, W[, Dz]}, nd = 2 | 3.
+ *   z may be NULL (step 0; sigma must then be 0, and out = fl(c1 * fl(x - fl(c2 * e)))).  out may be x.  Checked: null pointers, nd, dtype,
+ *   sizes (every dim a multiple of p, C pixels < 2^31 per sample), sigma != 0 without z, pointers not aligned to their element.
+ * ------------------------------------------------------------------------------------------------------ */
+int ucfvit_ddpm_q_sample(const float* x0, const float* eps, const int64_t* t, const float* sqrt_ab, const float* sqrt_1mab, float* out,
+                         int64_t B, int64_t n_per_sample, int64_t T, void* stream);
+int ucfvit_time_tokens_fwd(const void* patches, const void* cls, const void* pos, const void* temb, void* out, int64_t B, int64_t L, int64_t D,
+                           int has_cls, int dtype, void* stream);
+int64_t ucfvit_time_tokens_bwd_workspace(int64_t B, int64_t L, int64_t D, int has_cls);
+int ucfvit_time_tokens_bwd(const void* dout, void* dpatches, float* dpos, float* dcls, float* dtemb, int64_t B, int64_t L, int64_t D,
+                           int has_cls, int accumulate, float* workspace, int dtype, void* stream);
+int ucfvit_relu_dropout(const void* x, void* out, int64_t rows, int64_t D, double p, uint64_t seed, int dtype, void* stream);
+int ucfvit_relu_dropout_bwd(const void* x, const void* dy, void* dx, int64_t rows, int64_t D, double p, uint64_t seed, int dtype, void* stream);
+int ucfvit_ddpm_step(const float* x, const void* pred, const float* z, float* out, int64_t B, int64_t C, const int64_t* dims, int nd, int64_t p,
+                     float c1, float c2, float sigma, int dtype, void* stream);
 
 #ifdef __cplusplus
 }

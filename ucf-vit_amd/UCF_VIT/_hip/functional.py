@@ -993,6 +993,33 @@ class PatchEmbedFn(torch.autograd.Function):
         return None, gw, gb, None, None   # no gradient w.r.t. the image (leaf input of the training step)
 
 
+def _tokens_backward(ctx, dout, cls, pos, B, Lp, D, cdtype, in_dtype, bwd_op):
+    """The backward pass TokensFn and TimeTokensFn share: where dpos / dcls go (the flat gradient buffer or fresh tensors) and whether they
+    accumulate, then one launch of `bwd_op` (ops.tokens_bwd | ops.time_tokens_bwd).  -> (gx, g_cls, g_pos, what bwd_op returns beyond the
+    three gradients: dtemb or None)"""
+    d = _as(dout, cdtype)
+    want_pos = pos is not None and ctx.needs_input_grad[2]
+    has_cls = cls is not None
+    op = oc = None
+    ap = ac = False
+    if want_pos:
+        op, ap = grad_target(pos)
+    if has_cls:
+        oc, ac = grad_target(cls)
+    if (want_pos and has_cls and ap != ac) or (want_pos and has_cls and ((op is None) != (oc is None))):
+        op = oc = None
+        ap = ac = False
+    acc = ap or ac
+    dpatches, dpos, dcls, *rest = bwd_op(d, B, Lp, D, has_cls, want_pos,
+                                         dpos=op.view(-1, D) if op is not None else None,
+                                         dcls=oc.view(-1) if oc is not None else None, accumulate=acc,
+                                         want_patches=ctx.needs_input_grad[0])
+    g_pos = None if (not want_pos or acc) else (op if op is not None else dpos.view(pos.shape))
+    g_cls = None if (not has_cls or acc) else (oc if oc is not None else dcls.view(cls.shape))
+    gx = _ret_grad(dpatches.view(B, Lp, D), in_dtype) if dpatches is not None else None
+    return gx, g_cls, g_pos, rest[0] if rest else None
+
+
 class TokensFn(torch.autograd.Function):
     """VIT._pos_embed (arch.py:367-393): cat(cls, x) + pos_embed."""
 
@@ -1009,27 +1036,49 @@ class TokensFn(torch.autograd.Function):
     def backward(ctx, dout):
         cls, pos = ctx.saved_tensors
         B, Lp, D, cdtype, in_dtype = ctx.meta
-        d = _as(dout, cdtype)
-        want_pos = pos is not None and ctx.needs_input_grad[2]
-        has_cls = cls is not None
-        op = oc = None
-        ap = ac = False
-        if want_pos:
-            op, ap = grad_target(pos)
-        if has_cls:
-            oc, ac = grad_target(cls)
-        if (want_pos and has_cls and ap != ac) or (want_pos and has_cls and ((op is None) != (oc is None))):
-            op = oc = None
-            ap = ac = False
-        acc = ap or ac
-        dpatches, dpos, dcls = ops.tokens_bwd(d, B, Lp, D, has_cls, want_pos,
-                                              dpos=op.view(-1, D) if op is not None else None,
-                                              dcls=oc.view(-1) if oc is not None else None, accumulate=acc,
-                                              want_patches=ctx.needs_input_grad[0])
-        g_pos = None if (not want_pos or acc) else (op if op is not None else dpos.view(pos.shape))
-        g_cls = None if (not has_cls or acc) else (oc if oc is not None else dcls.view(cls.shape))
-        gx = _ret_grad(dpatches.view(B, Lp, D), in_dtype) if dpatches is not None else None
+        gx, g_cls, g_pos, _ = _tokens_backward(ctx, dout, cls, pos, B, Lp, D, cdtype, in_dtype, ops.tokens_bwd)
         return gx, g_cls, g_pos, None
+
+
+class TimeTokensFn(torch.autograd.Function):
+    """DiffusionVIT's token assembly: (cat(cls, x) + pos_embed) + temb[:, None, :], one pass (ucfvit_time_tokens_fwd).  temb [B, D] is the
+    time MLP's output; its gradient (the sum of dout over a sample's rows) comes out of the same backward pass as dpatches, dpos, dcls.
+    Gradient targets and accumulation of cls and pos are TokensFn's."""
+
+    @staticmethod
+    def forward(ctx, x, cls, pos, temb, cdtype):
+        xin = _as(x, cdtype)
+        B, Lp, D = xin.shape
+        out = ops.time_tokens_fwd(xin.view(B * Lp, D), compute_param(cls, cdtype), compute_param(pos, cdtype), _as(temb, cdtype), B, Lp, D)
+        ctx.save_for_backward(cls, pos)
+        ctx.meta = (B, Lp, D, cdtype, x.dtype, temb.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        cls, pos = ctx.saved_tensors
+        B, Lp, D, cdtype, in_dtype, temb_dtype = ctx.meta
+        gx, g_cls, g_pos, dtemb = _tokens_backward(ctx, dout, cls, pos, B, Lp, D, cdtype, in_dtype, ops.time_tokens_bwd)
+        return gx, g_cls, g_pos, _ret_grad(dtemb, temb_dtype) if ctx.needs_input_grad[3] else None, None
+
+
+class ReluDropoutFn(torch.autograd.Function):
+    """The hidden layer of DiffusionVIT's time MLP: y = m * relu(x) / keep in one pass (ucfvit_relu_dropout); p == 0 (eval) is plain ReLU.
+    The mask is that of HipDropout (seed, element index) and is never stored: backward reads the pre-activation and the seed."""
+
+    @staticmethod
+    def forward(ctx, x, p, seed):
+        xc = x if x.is_contiguous() else x.contiguous()
+        ctx.save_for_backward(xc)
+        ctx.site = (float(p), int(seed))
+        return ops.relu_dropout(xc.view(-1, xc.shape[-1]), *ctx.site).view(x.shape)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (xc,) = ctx.saved_tensors
+        dc = dy if dy.is_contiguous() else dy.contiguous()
+        dc = dc if dc.dtype == xc.dtype else _as(dc, xc.dtype)
+        return ops.relu_dropout_bwd(xc.view(-1, xc.shape[-1]), dc.view(-1, dc.shape[-1]), *ctx.site).view(dy.shape), None, None
 
 
 class SeqPatchesFn(torch.autograd.Function):
@@ -1369,3 +1418,19 @@ def cross_entropy(logits, labels):
 
 def patch_mse(pred, img, patch_size, mask=None):
     return PatchMSEFn.apply(pred, img, mask, patch_size)
+
+
+def q_sample(x0, t, eps, sqrt_ab, sqrt_1mab, out=None):
+    """DDPM forward noising x_t = sqrt(abar_t) x0 + sqrt(1 - abar_t) eps on the device (no gradient: x0 and eps are data); t int64 [B] on the
+    device, the two tables fp32 [T] (DDPM_Scheduler.sqrt_ab / sqrt_1mab)"""
+    with torch.no_grad():
+        x0 = x0 if x0.is_contiguous() else x0.contiguous()
+        eps = eps if eps.is_contiguous() else eps.contiguous()
+        return ops.ddpm_q_sample(x0, eps, t, sqrt_ab, sqrt_1mab, out=out)
+
+
+def ddpm_step(x, pred, z, patch_size, c1, c2, sigma, out=None):
+    """one ancestral reverse step x_{i-1} = c1 (x_i - c2 unpatchify(pred)) + sigma z on the image (no gradient)"""
+    with torch.no_grad():
+        pred = pred if pred.is_contiguous() else pred.contiguous()
+        return ops.ddpm_step(x, pred, z, int(patch_size), c1, c2, sigma, out=out)

@@ -163,6 +163,13 @@ SIGNATURES = {
     "ucfvit_qk_norm_partial_rows": (c_int64, [_I64, _I64, _I64]),
     "ucfvit_qk_norm_fwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _F, _I, _P]),
     "ucfvit_qk_norm_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I, _P]),
+    "ucfvit_ddpm_q_sample": (c_int, [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _P]),
+    "ucfvit_time_tokens_fwd": (c_int, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I, _I, _P]),
+    "ucfvit_time_tokens_bwd_workspace": (c_int64, [_I64, _I64, _I64, _I]),
+    "ucfvit_time_tokens_bwd": (c_int, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I, _I, _P, _I, _P]),
+    "ucfvit_relu_dropout": (c_int, [_P, _P, _I64, _I64, _D, c_uint64, _I, _P]),
+    "ucfvit_relu_dropout_bwd": (c_int, [_P, _P, _P, _I64, _I64, _D, c_uint64, _I, _P]),
+    "ucfvit_ddpm_step": (c_int, [_P, _P, _P, _P, _I64, _I64, POINTER(c_int64), _I, _I64, _F, _F, _F, _I, _P]),
 }
 
 _lib = None

@@ -1840,3 +1840,129 @@ def linear_dgrad_t(dy2, wT, act_grad_aux=None, out=None, aux_is_deriv=False, c_c
     K = wT.shape[0]
     return gemm(dy2, wT, M, K, N, LAYOUT_KC, LAYOUT_KC, out=out, act=_dgrad_act(act_grad_aux, aux_is_deriv), aux_in=act_grad_aux,
                 c_colsum=c_colsum, c_colsum_accumulate=c_colsum_accumulate)
+
+
+# ------------------------------------------------------------------------------------------------ DDPM (csrc/diffusion.hip)
+def _chk_f32(t, name):
+    _chk(t, name)
+    if t.dtype != torch.float32:
+        raise TypeError(f"{name}: expected a float32 tensor, got {t.dtype}")
+    return t
+
+
+def ddpm_q_sample(x0, eps, t, sqrt_ab, sqrt_1mab, out=None):
+    """out[b] = sqrt_ab[t[b]] * x0[b] + sqrt_1mab[t[b]] * eps[b]; x0, eps fp32 [B, ...]; t int64 [B] on the device (clamped into the tables
+    by the kernel); the tables fp32 [T] on the device.  out may be x0."""
+    L = _l.load()
+    _chk_f32(x0, "ddpm_q_sample.x0"), _chk_f32(eps, "ddpm_q_sample.eps")
+    _chk_f32(sqrt_ab, "ddpm_q_sample.sqrt_ab"), _chk_f32(sqrt_1mab, "ddpm_q_sample.sqrt_1mab")
+    _chk(t, "ddpm_q_sample.t")
+    B = x0.shape[0]
+    if t.dtype != torch.int64 or t.numel() != B:
+        raise TypeError(f"ddpm_q_sample: t must be an int64 tensor of B = {B} steps, got {t.dtype} {tuple(t.shape)}")
+    if eps.shape != x0.shape or sqrt_ab.dim() != 1 or sqrt_1mab.shape != sqrt_ab.shape:
+        raise ValueError("ddpm_q_sample: eps must have x0's shape and the two tables one length")
+    out = torch.empty_like(x0) if out is None else _chk_f32(out, "ddpm_q_sample.out")
+    if out.shape != x0.shape:
+        raise ValueError("ddpm_q_sample: out must have x0's shape")
+    n = x0.numel() // B if B else 1
+    _l.check(L.ucfvit_ddpm_q_sample(x0.data_ptr(), eps.data_ptr(), t.data_ptr(), sqrt_ab.data_ptr(), sqrt_1mab.data_ptr(), out.data_ptr(),
+                                    B, n, sqrt_ab.numel(), _stream()), "ucfvit_ddpm_q_sample")
+    return out
+
+
+def time_tokens_fwd(patches, cls, pos, temb, B, Lp, D):
+    """tokens_fwd plus the time row temb [B, D] of every sample (include/ucfvit_hip.h)"""
+    L = _l.load()
+    _chk(patches, "time_tokens.patches"), _chk(temb, "time_tokens.temb")
+    if temb.dtype != patches.dtype or tuple(temb.shape) != (B, D):
+        raise TypeError(f"time_tokens: temb must be [B={B}, D={D}] of the tokens' dtype, got {temb.dtype} {tuple(temb.shape)}")
+    pre = 0 if cls is None else 1
+    out = torch.empty((B, Lp + pre, D), dtype=patches.dtype, device=patches.device)
+    _l.check(L.ucfvit_time_tokens_fwd(patches.data_ptr(), _p(cls), _p(pos), temb.data_ptr(), out.data_ptr(), B, Lp, D, pre, dt(patches),
+                                      _stream()), "ucfvit_time_tokens_fwd")
+    return out
+
+
+def time_tokens_bwd(dout, B, Lp, D, has_cls, want_pos, dpos=None, dcls=None, accumulate=False, want_patches=True):
+    """tokens_bwd plus dtemb fp32 [B, D] = the sum of dout over a sample's rows; -> (dpatches, dpos, dcls, dtemb)"""
+    L = _l.load()
+    _chk(dout, "time_tokens_bwd.dout")
+    dev = dout.device
+    dpatches = torch.empty((B * Lp, D), dtype=dout.dtype, device=dev) if want_patches else None
+    pre = 1 if has_cls else 0
+    if want_pos and dpos is None:
+        dpos = torch.empty((Lp + pre, D), dtype=torch.float32, device=dev)
+    if has_cls and dcls is None:
+        dcls = torch.empty(D, dtype=torch.float32, device=dev)
+    dtemb = torch.empty((B, D), dtype=torch.float32, device=dev)
+    nbytes = L.ucfvit_time_tokens_bwd_workspace(B, Lp, D, pre)
+    if nbytes <= 0 and B > 0:
+        raise ValueError(f"time_tokens_bwd: sizes B={B} L={Lp} D={D} are refused by the kernel")
+    ws = workspace(nbytes, dev)
+    _l.check(L.ucfvit_time_tokens_bwd(dout.data_ptr(), _p(dpatches), _p(dpos) if want_pos else None, _p(dcls) if has_cls else None,
+                                      dtemb.data_ptr(), B, Lp, D, pre, 1 if accumulate else 0, ws.data_ptr(), dt(dout), _stream()),
+             "ucfvit_time_tokens_bwd")
+    return dpatches, dpos, dcls, dtemb
+
+
+def _chk_relu_dropout(p, seed, name):
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"{name}: the kernels take 0 <= p < 1 (0: plain ReLU, no mask), got p={p}")
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"{name}: the seed must be an unsigned 64-bit integer, got {seed}")
+
+
+def relu_dropout(x, p=0.0, seed=0, out=None):
+    """y = m * relu(x) / keep on x [rows, D] with the dropout mask of (seed, element index) at row_step 1; p == 0: plain ReLU.  out may be x"""
+    L = _l.load()
+    _chk(x, "relu_dropout.x")
+    rows, D = x.shape
+    out = torch.empty_like(x) if out is None else _chk(out, "relu_dropout.out")
+    if out.shape != x.shape or out.dtype != x.dtype:
+        raise TypeError("relu_dropout: out must have x's shape and dtype")
+    _chk_relu_dropout(p, seed, "relu_dropout")
+    _l.check(L.ucfvit_relu_dropout(x.data_ptr(), out.data_ptr(), rows, D, float(p), int(seed), dt(x), _stream()), "ucfvit_relu_dropout")
+    return out
+
+
+def relu_dropout_bwd(x, dy, p=0.0, seed=0, out=None):
+    """dx = m * [x > 0] * dy / keep, the mask recomputed from the seed; x is the pre-activation.  out may be dy"""
+    L = _l.load()
+    _chk(x, "relu_dropout_bwd.x"), _chk(dy, "relu_dropout_bwd.dy")
+    rows, D = x.shape
+    out = torch.empty_like(dy) if out is None else _chk(out, "relu_dropout_bwd.out")
+    if dy.shape != x.shape or dy.dtype != x.dtype or out.shape != x.shape or out.dtype != x.dtype:
+        raise TypeError("relu_dropout_bwd: x, dy and out must be [rows, D] of one dtype")
+    _chk_relu_dropout(p, seed, "relu_dropout_bwd")
+    _l.check(L.ucfvit_relu_dropout_bwd(x.data_ptr(), dy.data_ptr(), out.data_ptr(), rows, D, float(p), int(seed), dt(x), _stream()),
+             "ucfvit_relu_dropout_bwd")
+    return out
+
+
+def ddpm_step(x, pred, z, patch, c1, c2, sigma, out=None):
+    """out = c1 * (x - c2 * unpatchify(pred)) + sigma * z without the unpatchified tensor: x, z, out fp32 NCHW(D), pred [B, L, p^nd C] in
+    fp32 or bf16; z None: no noise (sigma must be 0).  out may be x."""
+    L = _l.load()
+    _chk_f32(x, "ddpm_step.x"), _chk(pred, "ddpm_step.pred")
+    if z is not None:
+        _chk_f32(z, "ddpm_step.z")
+        if z.shape != x.shape:
+            raise ValueError("ddpm_step: z must have x's shape")
+    B, C = x.shape[0], x.shape[1]
+    sp = list(x.shape[2:])
+    nd = len(sp)
+    if nd not in (2, 3):
+        raise ValueError(f"ddpm_step: x must be NCHW or NCHWD, got {tuple(x.shape)}")
+    Lp = 1
+    for s in sp:
+        Lp *= s // patch
+    if tuple(pred.shape) != (B, Lp, C * patch ** nd):
+        raise ValueError(f"ddpm_step: pred {tuple(pred.shape)} is not [B, L, p^nd C] = {(B, Lp, C * patch ** nd)} of x {tuple(x.shape)}")
+    out = torch.empty_like(x) if out is None else _chk_f32(out, "ddpm_step.out")
+    if out.shape != x.shape:
+        raise ValueError("ddpm_step: out must have x's shape")
+    dims = (ctypes.c_int64 * 3)(*(sp + [1] * (3 - nd)))
+    _l.check(L.ucfvit_ddpm_step(x.data_ptr(), pred.data_ptr(), _p(z), out.data_ptr(), B, C, dims, nd, int(patch), float(c1), float(c2),
+                                float(sigma), dt(pred), _stream()), "ucfvit_ddpm_step")
+    return out

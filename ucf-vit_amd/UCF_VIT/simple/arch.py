@@ -626,9 +626,11 @@ class UNETR(VIT):
 
 
 class DiffusionVIT(VIT):
-    """Noise-prediction ViT (reference :1115-1283).  API surface and state_dict layout only: the reference's own forward path is
-    broken upstream (forward_features calls self._pos_embed(x) without seq_ps -> TypeError) and diffusion training
-    is out of scope.  forward(x, t, variables) here follows the evident intent: tokens + time embedding -> blocks."""
+    """Noise-prediction ViT of DDPM training (reference :1115-1283): tokens + position + the time row of every sample -> Blocks -> norm ->
+    decoder -> one prediction per patch.  The reference's forward_features calls self._pos_embed(x) without seq_ps and raises TypeError
+    (SURVEY.md §0); this class follows the evident intent, seq_ps=None.  Everything diffusion-specific runs on the library: the time
+    table is gathered on the device, the time MLP is two HIP GEMMs around HF.ReluDropoutFn, and token assembly, position and the
+    broadcast time row are one pass (HF.TimeTokensFn); t may live on the device.  Training: training_scripts/train_diffusion_simple.py."""
 
     def __init__(self, *args, **kwargs):
         self.linear_decoder = kwargs.pop('linear_decoder', '')
@@ -662,21 +664,41 @@ class DiffusionVIT(VIT):
 
     init_weights = MAE.init_weights
 
+    def _refuse_unsupported(self):
+        if self.use_adaptive_pos_emb:
+            raise NotImplementedError("DiffusionVIT: use_adaptive_pos_emb needs seq_ps, which no caller of this class passes (the reference's "
+                                      "own forward raises TypeError there); not implemented")
+        if self.timeEmbeddingMap.dropout.active():
+            for kind in ("tensor", "seq"):
+                size = getattr(self, kind + "_par_size", 1)
+                if size > 1:
+                    group = getattr(self, "tensor_par_group", None) if kind == "tensor" else getattr(self, "_spg", None)
+                    raise NotImplementedError(f"time-MLP dropout p={self.timeEmbeddingMap.dropout.p} under a "
+                                              f"{'tensor' if kind == 'tensor' else 'sequence'}-parallel group ({group!r}, {size} ranks): every "
+                                              "rank of the group would need the same seed; not implemented")
+
     def forward_features(self, x, t, variables):
+        self._refuse_unsupported()
         self._prepare()
         x = self._embed_tokens(x, variables)
-        x = self._pos_embed(x, None)
-        time_emb = self.timeEmbeddingMap(self.temporalEmbeddings(x, t).float())[:, None, :]
-        x = x + time_emb.to(x.dtype)
+        temb = self.timeEmbeddingMap(self.temporalEmbeddings(x, t))                                  # [B, D]
+        if self.pos_embed is not None and not self.pos_drop.active() and type(self.patch_drop) is nn.Identity:
+            x = HF.TimeTokensFn.apply(x, self.cls_token, self.pos_embed, temb, _cd(self))            # (cat(cls, x) + pos) + temb: one pass
+        else:   # the reference's order: position (and its dropout), patch_drop, then the time row
+            x = self.patch_drop(self._pos_embed(x, None))
+            x = HF.TimeTokensFn.apply(x, None, None, temb, _cd(self))
         return self.norm(self.blocks(x))
 
     def forward_head(self, x):
         x = self.pool(x)
         if not self.linear_decoder:
             x = self.decoder_embed(x)
-            x = x + self.decoder_pos_embed.to(x.dtype)
+            if x.dim() != 3 or x.shape[1] != self.decoder_pos_embed.shape[1]:
+                raise ValueError(f"DiffusionVIT: the decoder adds decoder_pos_embed {tuple(self.decoder_pos_embed.shape)} to the pooled tokens "
+                                 f"{tuple(x.shape)}: construct the model with class_token=False, as the training script does")
+            x = HF.TokensFn.apply(x, None, self.decoder_pos_embed, _cd(self))
             x = self.decoder_norm(self.decoder_blocks(x))
         return self.decoder_pred(x)
 
     def forward(self, x, t, variables):
-        return self.forward_head(self.forward_features(x, t.to('cpu'), variables))
+        return self.forward_head(self.forward_features(x, t, variables))

@@ -424,17 +424,22 @@ class MyUnetBlock(nn.Module):
 
 
 class EmbeddingDenseLayer(nn.Module):
-    """time-embedding MLP of DiffusionVIT (reference :286-299): linear -> ReLU -> dropout -> linear"""
+    """time-embedding MLP of DiffusionVIT (reference :286-299): linear -> ReLU -> dropout -> linear.  The two Linears are HIP GEMMs, ReLU
+    and dropout one pass (HF.ReluDropoutFn); `dropout` holds the rate and draws the seed (HipDropout), `relu` is kept for the module
+    list.  In eval() no mask is generated."""
 
     def __init__(self, c_in: int, c_out: int, dropout_prob: float):
         super().__init__()
-        self.linear1 = nn.Linear(c_in, c_out)
-        self.linear2 = nn.Linear(c_out, c_out)
+        if not 0.0 <= dropout_prob < 1.0:
+            raise ValueError(f"EmbeddingDenseLayer: dropout_prob={dropout_prob} is not inside [0, 1)")
+        self.linear1 = Linear(c_in, c_out)
+        self.linear2 = Linear(c_out, c_out)
         self.relu = nn.ReLU()
-        self.dropout = nn.Dropout(p=dropout_prob)
+        self.dropout = HipDropout(p=dropout_prob)
 
     def forward(self, x):
-        return self.linear2(self.dropout(self.relu(self.linear1(x))))
+        site = _draw_dropout(self.dropout) or (0.0, 0)
+        return self.linear2(HF.ReluDropoutFn.apply(self.linear1(x), *site))
 
 
 class VariableMapping_Attention(nn.Module):

@@ -3,6 +3,7 @@
 // All memory traffic is 16-byte vectorised where alignment allows; reductions are deterministic (no float atomics).
 #include "common.h"
 #include "adamw_body.h"
+#include "patch_geom.h"
 
 namespace {
 
@@ -69,10 +70,12 @@ __global__ __launch_bounds__(256) void im2col_kernel(const float* __restrict__ i
 
 // ===================================================================================================
 // token assembly: out[b][t] = (t < pre ? cls : patches[b][t-pre]) + pos[t]
+// TIME (ucfvit_time_tokens_fwd, the DiffusionVIT): + temb[b], the time row of sample b, added in fp32 behind the position:
+// out = (a + pos[t]) + temb[b], one rounding to T.  Without TIME the code is what it was: temb is not touched.
 // ===================================================================================================
-template <typename T>
+template <typename T, bool TIME>
 __global__ void tokens_fwd_kernel(const T* __restrict__ patches, const T* __restrict__ cls, const T* __restrict__ pos,
-                                  T* __restrict__ out, int64_t B, int L, int D, int pre) {
+                                  const T* __restrict__ temb, T* __restrict__ out, int64_t B, int L, int D, int pre) {
     constexpr int EPV = Vec16<T>::N;
     const int nvec = D / EPV, N = L + pre;
     const int64_t total = B * N * nvec;
@@ -86,7 +89,19 @@ __global__ void tokens_fwd_kernel(const T* __restrict__ patches, const T* __rest
             a = *reinterpret_cast<const Vec16<T>*>(cls + v * EPV);
         else
             a = *reinterpret_cast<const Vec16<T>*>(patches + ((b * L + (t - pre)) * D) + v * EPV);
-        if (pos) {
+        if (TIME) {
+            const Vec16<T> tv = *reinterpret_cast<const Vec16<T>*>(temb + b * D + v * EPV);
+            Vec16<T> o;
+            if (pos) {
+                const Vec16<T> pv = *reinterpret_cast<const Vec16<T>*>(pos + (int64_t)t * D + v * EPV);
+#pragma unroll
+                for (int e = 0; e < EPV; ++e) o.set(e, (a.get(e) + pv.get(e)) + tv.get(e));
+            } else {
+#pragma unroll
+                for (int e = 0; e < EPV; ++e) o.set(e, a.get(e) + tv.get(e));
+            }
+            a = o;
+        } else if (pos) {
             const Vec16<T> pv = *reinterpret_cast<const Vec16<T>*>(pos + (int64_t)t * D + v * EPV);
             Vec16<T> o;
 #pragma unroll
@@ -98,24 +113,70 @@ __global__ void tokens_fwd_kernel(const T* __restrict__ patches, const T* __rest
 }
 
 // dpatches = dout[:, pre:], dpos[t] (+)= sum_b dout[b][t], dcls (+)= sum_b dout[b][0]
-template <typename T>
-__global__ void tokens_bwd_kernel(const T* __restrict__ dout, T* __restrict__ dpatches, float* __restrict__ dpos,
-                                  float* __restrict__ dcls, int64_t B, int L, int D, int pre, int accumulate) {
+// A thread owns one 16-byte column pack of one token row and walks the batch in order, so dpos and dcls are the sums b = 0, 1, ... in
+// every instantiation.
+// TIME (ucfvit_time_tokens_bwd): the same pass also gives, per sample, the sum over the token rows.  A wave then covers a chunk of
+// TOKENS_TIME_RC = 8 rows x 8 packs (lane = row * 8 + pack: 128 contiguous bytes of each row); for every sample its 8 rows are added by a
+// fixed butterfly over the lanes (xor 8, 16, 32) and the row-0 lanes write the chunk's sum to tpart[chunk][b][:] (fp32); the ordered fold over
+// the chunks (ucfvit_reduce_rows) is dtemb[b] = sum_t dout[b][t].  Lanes past N or D take part with zeros.  The partials are
+// 4 / (8 * sizeof(T)) of dout's bytes.  (A first version gave a thread all 8 rows of a chunk: an eighth of the threads, 24 workgroups at
+// [256 x 256, 768], 0.92 ms against the 0.10 ms of ucfvit_tokens_bwd: profiles/diffusion.md.)
+constexpr int TOKENS_TIME_RC = 8;
+template <typename T, bool TIME>
+__global__ __launch_bounds__(128) void tokens_bwd_kernel(const T* __restrict__ dout, T* __restrict__ dpatches, float* __restrict__ dpos,
+                                                         float* __restrict__ dcls, float* __restrict__ tpart, int64_t B, int L, int D, int pre,
+                                                         int accumulate) {
     constexpr int EPV = Vec16<T>::N;
     const int nvec = D / EPV, N = L + pre;
-    const int64_t total = (int64_t)N * nvec;
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const int v = i % nvec, t = i / nvec;
+    int v, t, chunk = 0;
+    bool live = true, writer = false;
+    if (TIME) {
+        const int ng = (nvec + 7) / 8, lane = threadIdx.x & 63;
+        const int64_t w = i >> 6;
+        chunk = (int)(w / ng);
+        v = (int)(w % ng) * 8 + (lane & 7);
+        t = chunk * TOKENS_TIME_RC + (lane >> 3);
+        live = t < N && v < nvec;
+        writer = (lane >> 3) == 0 && live;                                 // row 0 of a chunk that exists
+    } else {
+        if (i >= (int64_t)N * nvec) return;
+        v = i % nvec, t = i / nvec;
+    }
     float acc[EPV];
 #pragma unroll
     for (int e = 0; e < EPV; ++e) acc[e] = 0.f;
+    // TIME asks for four samples per trip so that their loads could overlap (the sums stay in order); measured without effect, the
+    // stores between the loads keep the compiler from hoisting them (profiles/diffusion.md).  The old instantiation keeps its loop
+#pragma unroll(TIME ? 4 : 1)
     for (int64_t b = 0; b < B; ++b) {
-        const Vec16<T> d = *reinterpret_cast<const Vec16<T>*>(dout + ((b * N + t) * D) + v * EPV);
+        float dv[EPV];
+        if (live) {
+            const Vec16<T> d = *reinterpret_cast<const Vec16<T>*>(dout + ((b * N + t) * D) + v * EPV);
 #pragma unroll
-        for (int e = 0; e < EPV; ++e) acc[e] += d.get(e);
-        if (t >= pre && dpatches) *reinterpret_cast<Vec16<T>*>(dpatches + ((b * L + (t - pre)) * D) + v * EPV) = d;
+            for (int e = 0; e < EPV; ++e) acc[e] += (dv[e] = d.get(e));
+            if (t >= pre && dpatches) *reinterpret_cast<Vec16<T>*>(dpatches + ((b * L + (t - pre)) * D) + v * EPV) = d;
+        } else {
+#pragma unroll
+            for (int e = 0; e < EPV; ++e) dv[e] = 0.f;
+        }
+        if (TIME) {                                                          // uniform over the wave: every lane takes part
+#pragma unroll
+            for (int e = 0; e < EPV; ++e) {
+                float s = dv[e];
+                s += __shfl_xor(s, 8);
+                s += __shfl_xor(s, 16);
+                s += __shfl_xor(s, 32);
+                dv[e] = s;
+            }
+            if (writer) {
+                float* o = tpart + ((int64_t)chunk * B + b) * D + v * EPV;
+#pragma unroll
+                for (int e = 0; e < EPV; ++e) o[e] = dv[e];
+            }
+        }
     }
+    if (!live) return;
     if (dpos) {
 #pragma unroll
         for (int e = 0; e < EPV; ++e) {
@@ -312,27 +373,9 @@ __global__ void batch_sum_kernel(const T* __restrict__ dout, float* __restrict__
 // patchify-MSE.  pred[b][l][e], e = ((ph*p + pw)[*p + pd])*C + c ; target = img[b][c][h*p+ph][w*p+pw][..]
 // phase 1: per-workgroup partial sums of weighted squared error (and of the mask) ; phase 2: finalize ; phase 3: dpred
 // ===================================================================================================
-struct PatchGeom {
-    int C, H, W, Z, p, nd, gh, gw, gz, L, P;
-};
+// PatchGeom, patch_pixel_index: csrc/patch_geom.h (shared with the DDPM reverse step)
 __device__ __forceinline__ float patch_target(const float* __restrict__ img, const PatchGeom& g, int64_t b, int l, int e) {
-    const int c = e % g.C;
-    int s = e / g.C;
-    if (g.nd == 1) {  // pre-cut token sequence x[B][C][S][P]: target row l = 'b c s p -> b s (p c)' (train_masked_simple.py:29)
-        return img[((b * g.C + c) * (int64_t)g.L + l) * g.p + s];
-    } else if (g.nd == 2) {
-        const int pw = s % g.p, ph = s / g.p;
-        const int w = l % g.gw, h = l / g.gw;
-        return img[((b * g.C + c) * g.H + (h * g.p + ph)) * (int64_t)g.W + (w * g.p + pw)];
-    } else {
-        const int pd = s % g.p;
-        s /= g.p;
-        const int pw = s % g.p, ph = s / g.p;
-        const int z = l % g.gz;
-        int t = l / g.gz;
-        const int w = t % g.gw, h = t / g.gw;
-        return img[(((b * g.C + c) * g.H + (h * g.p + ph)) * (int64_t)g.W + (w * g.p + pw)) * g.Z + (z * g.p + pd)];
-    }
+    return img[patch_pixel_index(g, b, l, e)];
 }
 
 template <typename T>
@@ -479,11 +522,11 @@ extern "C" int ucfvit_tokens_fwd(const void* patches, const void* cls, const voi
     const int64_t work = B * (L + pre) * (D / epv);
     hipStream_t s = (hipStream_t)stream;
     if (dtype == UCFVIT_F32)
-        hipLaunchKernelGGL(tokens_fwd_kernel<float>, dim3(ew_grid(work)), dim3(256), 0, s, (const float*)patches, (const float*)cls,
-                           (const float*)pos, (float*)out, B, (int)L, (int)D, pre);
+        hipLaunchKernelGGL((tokens_fwd_kernel<float, false>), dim3(ew_grid(work)), dim3(256), 0, s, (const float*)patches, (const float*)cls,
+                           (const float*)pos, (const float*)nullptr, (float*)out, B, (int)L, (int)D, pre);
     else
-        hipLaunchKernelGGL(tokens_fwd_kernel<bf16>, dim3(ew_grid(work)), dim3(256), 0, s, (const bf16*)patches, (const bf16*)cls,
-                           (const bf16*)pos, (bf16*)out, B, (int)L, (int)D, pre);
+        hipLaunchKernelGGL((tokens_fwd_kernel<bf16, false>), dim3(ew_grid(work)), dim3(256), 0, s, (const bf16*)patches, (const bf16*)cls,
+                           (const bf16*)pos, (const bf16*)nullptr, (bf16*)out, B, (int)L, (int)D, pre);
     UCF_LAUNCH_CHECK("ucfvit_tokens_fwd");
     return UCFVIT_OK;
 }
@@ -501,13 +544,72 @@ extern "C" int ucfvit_tokens_bwd(const void* dout, void* dpatches, float* dpos, 
     const unsigned grid = (unsigned)((work + 127) / 128);
     hipStream_t s = (hipStream_t)stream;
     if (dtype == UCFVIT_F32)
-        hipLaunchKernelGGL(tokens_bwd_kernel<float>, dim3(grid), dim3(128), 0, s, (const float*)dout, (float*)dpatches, dpos, dcls, B,
-                           (int)L, (int)D, pre, accumulate);
+        hipLaunchKernelGGL((tokens_bwd_kernel<float, false>), dim3(grid), dim3(128), 0, s, (const float*)dout, (float*)dpatches, dpos, dcls,
+                           (float*)nullptr, B, (int)L, (int)D, pre, accumulate);
     else
-        hipLaunchKernelGGL(tokens_bwd_kernel<bf16>, dim3(grid), dim3(128), 0, s, (const bf16*)dout, (bf16*)dpatches, dpos, dcls, B,
-                           (int)L, (int)D, pre, accumulate);
+        hipLaunchKernelGGL((tokens_bwd_kernel<bf16, false>), dim3(grid), dim3(128), 0, s, (const bf16*)dout, (bf16*)dpatches, dpos, dcls,
+                           (float*)nullptr, B, (int)L, (int)D, pre, accumulate);
     UCF_LAUNCH_CHECK("ucfvit_tokens_bwd");
     return UCFVIT_OK;
+}
+
+// token assembly with the per-sample time row (DiffusionVIT): the kernels above with TIME
+extern "C" int ucfvit_time_tokens_fwd(const void* patches, const void* cls, const void* pos, const void* temb, void* out, int64_t B, int64_t L,
+                                      int64_t D, int has_cls, int dtype, void* stream) {
+    UCF_CHECK_ARG(B >= 0 && L >= 0 && D > 0 && B < (1ll << 31) && L < (1ll << 30) && D < (1ll << 30), "ucfvit_time_tokens_fwd: bad sizes");
+    if (B == 0) return UCFVIT_OK;                      // empty batch (pointers may be NULL)
+    UCF_CHECK_ARG(patches && temb && out, "ucfvit_time_tokens_fwd: null pointer");
+    UCF_CHECK_ARG(!has_cls || cls, "ucfvit_time_tokens_fwd: has_cls without cls pointer");
+    UCF_CHECK_ARG(DTYPE_OK(dtype), "ucfvit_time_tokens_fwd: bad dtype %d", dtype);
+    const int epv = dtype == UCFVIT_F32 ? 4 : 8;
+    UCF_CHECK_ARG(D % epv == 0, "ucfvit_time_tokens_fwd: D=%lld must be a multiple of %d", (long long)D, epv);
+    UCF_CHECK_ARG(ucf_is_aligned16(patches) && ucf_is_aligned16(out) && ucf_is_aligned16(cls) && ucf_is_aligned16(pos) && ucf_is_aligned16(temb),
+                  "ucfvit_time_tokens_fwd: pointers must be 16-byte aligned");
+    const int pre = has_cls ? 1 : 0;
+    const int64_t work = B * (L + pre) * (D / epv);
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == UCFVIT_F32)
+        hipLaunchKernelGGL((tokens_fwd_kernel<float, true>), dim3(ew_grid(work)), dim3(256), 0, s, (const float*)patches, (const float*)cls,
+                           (const float*)pos, (const float*)temb, (float*)out, B, (int)L, (int)D, pre);
+    else
+        hipLaunchKernelGGL((tokens_fwd_kernel<bf16, true>), dim3(ew_grid(work)), dim3(256), 0, s, (const bf16*)patches, (const bf16*)cls,
+                           (const bf16*)pos, (const bf16*)temb, (bf16*)out, B, (int)L, (int)D, pre);
+    UCF_LAUNCH_CHECK("ucfvit_time_tokens_fwd");
+    return UCFVIT_OK;
+}
+
+// bytes of the per-chunk partial sums of dtemb: fp32 [ceil((L + pre) / TOKENS_TIME_RC)][B][D]; 0 for sizes the kernel refuses
+extern "C" int64_t ucfvit_time_tokens_bwd_workspace(int64_t B, int64_t L, int64_t D, int has_cls) {
+    if (B <= 0 || L < 0 || D <= 0 || B >= (1ll << 31) || L >= (1ll << 30) || D >= (1ll << 30)) return 0;
+    const int64_t N = L + (has_cls ? 1 : 0);
+    if (N == 0 || B * D >= (1ll << 31)) return 0;
+    return (N + TOKENS_TIME_RC - 1) / TOKENS_TIME_RC * B * D * (int64_t)sizeof(float);
+}
+
+extern "C" int ucfvit_time_tokens_bwd(const void* dout, void* dpatches, float* dpos, float* dcls, float* dtemb, int64_t B, int64_t L,
+                                      int64_t D, int has_cls, int accumulate, float* workspace, int dtype, void* stream) {
+    UCF_CHECK_ARG(B >= 0 && L >= 0 && D > 0 && B < (1ll << 31) && L < (1ll << 30) && D < (1ll << 30), "ucfvit_time_tokens_bwd: bad sizes");
+    if (B == 0) return UCFVIT_OK;
+    UCF_CHECK_ARG(dout && dtemb && workspace, "ucfvit_time_tokens_bwd: null pointer");
+    UCF_CHECK_ARG(DTYPE_OK(dtype), "ucfvit_time_tokens_bwd: bad dtype %d", dtype);
+    const int epv = dtype == UCFVIT_F32 ? 4 : 8;
+    UCF_CHECK_ARG(D % epv == 0, "ucfvit_time_tokens_bwd: D=%lld must be a multiple of %d", (long long)D, epv);
+    UCF_CHECK_ARG(ucf_is_aligned16(dout) && ucf_is_aligned16(dpatches), "ucfvit_time_tokens_bwd: pointers must be 16-byte aligned");
+    const int pre = has_cls ? 1 : 0;
+    UCF_CHECK_ARG(L + pre > 0 && B * D < (1ll << 31), "ucfvit_time_tokens_bwd: no token rows, or B*D >= 2^31");
+    const int64_t chunks = (L + pre + TOKENS_TIME_RC - 1) / TOKENS_TIME_RC;
+    const int64_t waves = chunks * ((D / epv + 7) / 8);                      // a wave: 8 rows x 8 packs
+    UCF_CHECK_ARG(waves < (1ll << 31), "ucfvit_time_tokens_bwd: too many tiles");
+    const unsigned grid = (unsigned)((waves + 1) / 2);                       // 128 threads: two waves
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == UCFVIT_F32)
+        hipLaunchKernelGGL((tokens_bwd_kernel<float, true>), dim3(grid), dim3(128), 0, s, (const float*)dout, (float*)dpatches, dpos,
+                           dcls, workspace, B, (int)L, (int)D, pre, accumulate);
+    else
+        hipLaunchKernelGGL((tokens_bwd_kernel<bf16, true>), dim3(grid), dim3(128), 0, s, (const bf16*)dout, (bf16*)dpatches, dpos,
+                           dcls, workspace, B, (int)L, (int)D, pre, accumulate);
+    UCF_LAUNCH_CHECK("ucfvit_time_tokens_bwd");
+    return ucfvit_reduce_rows(workspace, dtemb, chunks, B * D, 0, s);     // dtemb[b][:] = the chunks' partials, in chunk order
 }
 
 extern "C" int ucfvit_cross_entropy(const void* logits, const int64_t* labels, float* loss, float* row_loss, void* dlogits,
@@ -666,23 +768,7 @@ extern "C" int ucfvit_patch_mse(const void* pred, const float* img, const float*
         UCF_CHECK_ARG(dims[0] > 0 && dims[0] < (1ll << 31) && C * p < (1ll << 31), "ucfvit_patch_mse: bad sequence length");
     else
         for (int i = 0; i < nd; ++i) UCF_CHECK_ARG(dims[i] > 0 && dims[i] % p == 0, "ucfvit_patch_mse: image dim %d not a multiple of p", i);
-    PatchGeom g;
-    g.C = (int)C;
-    g.H = (int)dims[0];
-    g.W = (int)dims[1];
-    g.Z = nd == 3 ? (int)dims[2] : 1;
-    g.p = (int)p;
-    g.nd = nd;
-    g.gh = g.H / g.p;
-    g.gw = g.W / g.p;
-    g.gz = nd == 3 ? g.Z / g.p : 1;
-    g.L = g.gh * g.gw * g.gz;
-    g.P = (int)(C * p * p * (nd == 3 ? p : 1));
-    if (nd == 1) {  // dims = {S}, p = pixels per token and channel
-        g.H = g.W = g.Z = g.gh = g.gw = g.gz = 1;
-        g.L = (int)dims[0];
-        g.P = (int)(C * p);
-    }
+    const PatchGeom g = patch_geom_make(C, dims, nd, p);
     const int64_t total = B * g.L * g.P;
     hipStream_t s = (hipStream_t)stream;
     int nb = (int)((total + 256 * 64 - 1) / (256 * 64));
