@@ -5,7 +5,8 @@ Reference semantics: src/UCF_VIT/simple/building_blocks.py (PatchEmbed:78-92, Ml
 Block:236-239) and src/UCF_VIT/simple/arch.py (_pos_embed:367-393, random_masking:663-681, mask_head:683-702).
 
 Parameter gradients are written by the kernels straight into the flat fp32 gradient buffer of the model's
-HipParamStore when there is one (see params.py); the view is handed to autograd so hooks (e.g. a DDP reducer) still fire.
+HipParamStore when there is one (see params.py); the view is handed to autograd so post-accumulate hooks (e.g. a DDP reducer) still
+fire.  The gradient of a parameter with tensor hooks (register_hook) is not written there: it goes through autograd like any tensor's.
 """
 import os
 import weakref
@@ -50,7 +51,9 @@ class WgradQueue:
 
     Deferral across Blocks is only used for gradients that land in the flat gradient buffer (params.grad_target gives a view):
     autograd receives that view before the kernel has run, which is safe because AccumulateGrad adopts it without reading it and
-    every reader of the buffer (optimizer, HipDataParallel bucket launch, grad clipping) comes after flush_wgrads()."""
+    every reader of the buffer (optimizer, HipDataParallel bucket launch, grad clipping) comes after flush_wgrads().  A tensor hook on
+    the weight would read it: grad_target gives a hooked parameter no target, so its gradient is a tensor of its own, the queue stops
+    deferring (deferrable) and end_block issues the launch before the Block's backward returns."""
 
     MAX_PROBLEMS = 32       # GROUP_MAX of csrc/gemm2.hip
     CUS = 256

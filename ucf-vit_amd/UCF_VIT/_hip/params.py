@@ -166,9 +166,13 @@ def grad_target(p):
 
     returns (out, accumulate): out = fp32 tensor to write into (None: allocate a fresh one and hand it to autograd),
     accumulate = True when `out` already holds this step's partial gradient (then nothing is returned to autograd).
+
+    A parameter with tensor hooks (p.register_hook) has no target: a hook reads the gradient autograd is handed and may replace it, so
+    the gradient must be complete when backward returns it (a queued weight gradient written into the flat buffer is not) and must pass
+    through autograd on every pass (one accumulated by the kernel does not).
     """
     slot = getattr(p, "_ucf_slot", None)
-    if slot is None:
+    if slot is None or p._backward_hooks:
         return None, False
     st, o, n = slot
     if not st.owns(p, o):
