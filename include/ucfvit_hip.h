@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define UCFVIT_ABI_VERSION 24 /* still 24 with the dropout, LayerScale, QK-norm and DDPM entry points (ucfvit_dropout*, ucfvit_layer_scale_*, ucfvit_qk_norm_*, ucfvit_ddpm_*, ucfvit_time_tokens_*, ucfvit_relu_dropout*): symbols were only added */
+#define UCFVIT_ABI_VERSION 24 /* still 24 with the dropout, LayerScale, QK-norm, DDPM, EMA and DDIM entry points (ucfvit_dropout*, ucfvit_layer_scale_*, ucfvit_qk_norm_*, ucfvit_ddpm_*, ucfvit_time_tokens_*, ucfvit_relu_dropout*, ucfvit_adamw_ema, ucfvit_adamw_scaled_ema, ucfvit_ddim_step): symbols were only added */
 
 #define UCFVIT_OK 0
 #define UCFVIT_ERR_INVALID_ARGUMENT (-1)
@@ -420,6 +420,14 @@ int ucfvit_patch_mse(const void* pred, const float* img, const float* mask, floa
 int ucfvit_adamw(float* p, const void* g, float* m, float* v, void* shadow_bf16, int64_t n, float lr, float beta1,
                  float beta2, float eps, float weight_decay, float bias_corr1, float bias_corr2, float grad_scale,
                  int grad_dtype, void* stream);
+/* ucfvit_adamw_ema: ucfvit_adamw, and in the same pass an exponential moving average of the weights, fp32 [n]:
+ *   ema[i] = ema[i] + ema_rate * (p_new[i] - ema[i]),  p_new the fp32 value just stored to p[i],  ema_rate = 1 - decay.
+ * p, m, v and the shadow get the bits ucfvit_adamw gives them.  ema_rate is formed by the caller in double and rounded once (a float 0.9999
+ * carries a relative error of 6e-4 in 1 - decay); it must be inside (0, 1] (1: ema = p_new; NaN is refused).  ema must be non-null and 16-byte
+ * aligned.  ucfvit_adamw_scaled_ema (below) is the same for ucfvit_adamw_scaled: a skipped step leaves ema alone too. */
+int ucfvit_adamw_ema(float* p, const void* g, float* m, float* v, void* shadow_bf16, float* ema, int64_t n, float lr, float beta1,
+                     float beta2, float eps, float weight_decay, float bias_corr1, float bias_corr2, float grad_scale, float ema_rate,
+                     int grad_dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Dynamic loss scaling with on-device skipping of non-finite steps (the reference's bf16 policy: ShardedGradScaler(init_scale=8192,
@@ -455,6 +463,9 @@ int ucfvit_grad_nonfinite(const void* g, int64_t n, int dtype, float mult, float
 int ucfvit_adamw_scaled(float* p, const void* g, float* m, float* v, void* shadow_bf16, int64_t n, float lr, double beta1,
                         double beta2, float eps, float weight_decay, float grad_scale, int grad_dtype, const float* state,
                         void* stream);
+int ucfvit_adamw_scaled_ema(float* p, const void* g, float* m, float* v, void* shadow_bf16, float* ema, int64_t n, float lr, double beta1,
+                            double beta2, float eps, float weight_decay, float grad_scale, float ema_rate, int grad_dtype,
+                            const float* state, void* stream);
 int ucfvit_grad_scaler_update(float* state, void* stream);
 
 /* dtype conversion / scaling helpers (fp32 master → bf16 shadow cast; bf16 gradient transport for the DP all-reduce) */
@@ -867,6 +878,18 @@ int ucfvit_qk_norm_bwd(void* dqkv, const void* saved_qk, const float* gamma_q, c
  *   ucfvit_patch_mse documents, (ph, pw[, pd], c): the reference's unpatchify.  x, z, out are fp32 NCHW(D); dims = {H, W[, Dz]}, nd = 2 | 3.
  *   z may be NULL (step 0; sigma must then be 0, and out = fl(c1 * fl(x - fl(c2 * e)))).  out may be x.  Checked: null pointers, nd, dtype,
  *   sizes (every dim a multiple of p, C pixels < 2^31 per sample), sigma != 0 without z, pointers not aligned to their element.
+ *
+ * ucfvit_ddim_step: one generalised reverse step (DDIM; eta = 1 on every step is the ancestral sampler in its x0 form), with the geometry,
+ *   checks and aliasing rule (out may be x) of ucfvit_ddpm_step.  Per element, every product and sum rounded on its own, in this order:
+ *     e  = (float)pred[i]
+ *     x0 = (x - s_1mab * e) * r_ab
+ *     if clip > 0:  x0 = x0 < -clip ? -clip : (x0 > clip ? clip : x0)      (two selects: a NaN stays a NaN)
+ *                   e  = (x - s_ab * x0) * r_1mab
+ *     o  = c_x0 * x0 + c_eps * e
+ *     out = z ? o + sigma * z : o
+ *   s_ab = sqrt(abar_i), s_1mab = sqrt(1 - abar_i), r_ab and r_1mab their reciprocals, c_x0 = sqrt(abar_prev), c_eps =
+ *   sqrt(1 - abar_prev - sigma^2): DDPM_Scheduler.ddim_coefficients.  clip == 0: no clamp; a negative or NaN clip is refused.  z == NULL
+ *   needs sigma == 0.
  * ------------------------------------------------------------------------------------------------------ */
 int ucfvit_ddpm_q_sample(const float* x0, const float* eps, const int64_t* t, const float* sqrt_ab, const float* sqrt_1mab, float* out,
                          int64_t B, int64_t n_per_sample, int64_t T, void* stream);
@@ -879,6 +902,9 @@ int ucfvit_relu_dropout(const void* x, void* out, int64_t rows, int64_t D, doubl
 int ucfvit_relu_dropout_bwd(const void* x, const void* dy, void* dx, int64_t rows, int64_t D, double p, uint64_t seed, int dtype, void* stream);
 int ucfvit_ddpm_step(const float* x, const void* pred, const float* z, float* out, int64_t B, int64_t C, const int64_t* dims, int nd, int64_t p,
                      float c1, float c2, float sigma, int dtype, void* stream);
+int ucfvit_ddim_step(const float* x, const void* pred, const float* z, float* out, int64_t B, int64_t C, const int64_t* dims, int nd, int64_t p,
+                     float s_ab, float s_1mab, float r_ab, float r_1mab, float c_x0, float c_eps, float sigma, float clip, int dtype,
+                     void* stream);
 
 #ifdef __cplusplus
 }

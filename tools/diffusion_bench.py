@@ -5,11 +5,13 @@ DiffusionVIT training step and sampler at the reference's imagenet/diffusion sha
 
   python tools/diffusion_bench.py kernels [reps=50] [rounds=5]
   python tools/diffusion_bench.py step [batch=32] [reps=10] [rounds=5] [--tree DIR]
-  python tools/diffusion_bench.py sample [batch=8] [steps=20]
+  python tools/diffusion_bench.py sample [batch=8] [steps=20] [--sampler ddim --steps S]
+  python tools/diffusion_bench.py ema [n=304000000] [reps=20] [rounds=5]
 
 Must-move bytes:
   q_sample         reads x0 and eps, writes x_t (fp32)                                           = 3 images
   ddpm_step        reads x, z and pred (bf16, half an image's bytes), writes x (fp32)            = 3.5 images
+  ddim_step        the same (without z at eta = 0: 2.5 images)
   tokens_fwd       reads and writes the token matrix (bf16)                                      = 2 matrices (+ pos, L2-resident)
   time_tokens_fwd  the same + the [B, D] time rows
   tokens_bwd       reads dout, writes dpatches                                                   = 2 matrices (+ dpos)
@@ -21,7 +23,14 @@ with (min ... max); the bandwidth is must-move bytes over the median, as a fract
 (profiles/layer_scale.md).  HIP-event times after a warm-up of every case.  One JSON line per case on stdout.
 
 step: forward + backward + HipAdamW step of the model wrapped in the same noising and loss, `--tree DIR` takes the package from another
-checkout (the parent commit, whose DiffusionVIT runs its glue on torch: the noising is then torch's, the loss HF.patch_mse in both)."""
+checkout (the parent commit, whose DiffusionVIT runs its glue on torch: the noising is then torch's, the loss HF.patch_mse in both).
+
+sample: the ancestral sampler over a `steps`-step schedule, or with `--sampler ddim --steps S` the strided sampler, S steps of the 1000-step
+schedule (eta 0, no clamp).
+
+ema: the optimiser pass over n fp32 parameters with fp32 gradients and the bf16 shadow written: adamw (reads p, g, m, v, writes p, m, v and
+the shadow: 30 B per parameter), adamw_ema (+ the average read and written: 38 B), and adamw followed by ema.lerp_(p, rate) as a pass of its
+own (+ p and the average read, the average written: 42 B)."""
 import json
 import os
 import statistics
@@ -31,7 +40,8 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TREE = sys.argv[sys.argv.index("--tree") + 1] if "--tree" in sys.argv else ROOT
-ARGS = [a for i, a in enumerate(sys.argv[1:], 1) if a != "--tree" and sys.argv[i - 1] != "--tree"]
+OPTS = ("--tree", "--sampler", "--steps")
+ARGS = [a for i, a in enumerate(sys.argv[1:], 1) if a not in OPTS and sys.argv[i - 1] not in OPTS]
 sys.path.insert(0, os.path.join(TREE, "ucf-vit_amd"))
 from UCF_VIT._hip import functional as HF  # noqa: E402
 from UCF_VIT._hip import ops  # noqa: E402
@@ -81,7 +91,13 @@ def kernels(reps, rounds):
         pred = torch.randn((B, 256, 768), device=DEV, generator=g).to(torch.bfloat16)
         img = x0.numel() * 4
         compare({f"q_sample B={B}": (lambda: ops.ddpm_q_sample(x0, eps, t, sa, sb, out=out), 3 * img),
-                 f"ddpm_step B={B}": (lambda: ops.ddpm_step(x0, pred, z, 16, 1.01, 0.09, 0.14, out=out), 3 * img + pred.numel() * 2)}, reps, rounds)
+                 f"ddpm_step B={B}": (lambda: ops.ddpm_step(x0, pred, z, 16, 1.01, 0.09, 0.14, out=out), 3 * img + pred.numel() * 2),
+                 f"ddim_step B={B}": (lambda: ops.ddim_step(x0, pred, z, 16, 0.8, 0.6, 1.25, 1.0 / 0.6, 0.85, 0.5, 0.14, out=out),
+                                      3 * img + pred.numel() * 2),
+                 f"ddim_step clip B={B}": (lambda: ops.ddim_step(x0, pred, z, 16, 0.8, 0.6, 1.25, 1.0 / 0.6, 0.85, 0.5, 0.14, clip=1.0, out=out),
+                                           3 * img + pred.numel() * 2),
+                 f"ddim_step no z B={B}": (lambda: ops.ddim_step(x0, pred, None, 16, 0.8, 0.6, 1.25, 1.0 / 0.6, 0.85, 0.5, 0.0, out=out),
+                                           2 * img + pred.numel() * 2)}, reps, rounds)
         del x0, eps, z, out, pred
     B, L, D = 256, 256, 768
     patches = torch.randn((B * L, D), device=DEV, generator=g).to(torch.bfloat16)
@@ -146,21 +162,44 @@ def step(batch, reps, rounds):
                           peak_GB=round(torch.cuda.max_memory_allocated() / 2 ** 30, 1))), flush=True)
 
 
-def sample(batch, steps):
+def sample(batch, steps, ddim_steps=None):
     from UCF_VIT.ddpm.ddpm import DDPM_Scheduler
     m, _ = _model()
-    sched = DDPM_Scheduler(steps).to(DEV)
+    sched = DDPM_Scheduler(1000 if ddim_steps else steps).to(DEV)
     g = torch.Generator(device=DEV).manual_seed(2)
-    sched.sample(m, (batch, 3, 256, 256), None, generator=g)
+    shape = (batch, 3, 256, 256)
+    run = (lambda: sched.sample_ddim(m, shape, None, num_steps=ddim_steps, generator=g)) if ddim_steps else (lambda: sched.sample(m, shape, None, generator=g))
+    run()
     torch.cuda.synchronize()
     s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     s.record()
-    sched.sample(m, (batch, 3, 256, 256), None, generator=g)
+    run()
     e.record()
     torch.cuda.synchronize()
     ms = s.elapsed_time(e)
+    if ddim_steps:
+        print(json.dumps(dict(case="sample ddim", batch=batch, steps=ddim_steps, ms_per_step=round(ms / ddim_steps, 3),
+                              s_per_image=round(ms / batch / 1e3, 4))), flush=True)
+        return
     print(json.dumps(dict(case="sample", batch=batch, steps=steps, ms_per_step=round(ms / steps, 3),
                           s_per_image_at_1000_steps=round(ms / steps * 1000 / batch / 1e3, 3))), flush=True)
+
+
+def ema(n, reps, rounds):
+    g = torch.Generator(device=DEV).manual_seed(3)
+    p, gr = torch.randn(n, device=DEV, generator=g), torch.randn(n, device=DEV, generator=g) * 1e-3
+    m, v, avg = torch.zeros(n, device=DEV), torch.zeros(n, device=DEV), p.clone()
+    sh = torch.empty(n, device=DEV, dtype=torch.bfloat16)
+    hp = (1e-4, 0.9, 0.95, 1e-8, 1e-5)
+    rate = ops.ema_rate(0.9999)
+
+    def pair():
+        ops.adamw(p, gr, m, v, sh, *hp, 10)
+        avg.lerp_(p, rate)
+
+    compare({f"adamw n={n}": (lambda: ops.adamw(p, gr, m, v, sh, *hp, 10), 30 * n),
+             f"adamw_ema n={n}": (lambda: ops.adamw_ema(p, gr, m, v, sh, avg, *hp, 10, rate), 38 * n),
+             f"adamw + lerp_ n={n}": (pair, 42 * n)}, reps, rounds)
 
 
 if __name__ == "__main__":
@@ -171,6 +210,12 @@ if __name__ == "__main__":
     elif mode == "step":
         step(*(nums + [32, 10, 5][len(nums):]))
     elif mode == "sample":
-        sample(*(nums + [8, 20][len(nums):]))
+        sampler = sys.argv[sys.argv.index("--sampler") + 1] if "--sampler" in sys.argv else "ddpm"
+        if sampler not in ("ddpm", "ddim"):
+            raise SystemExit(__doc__)
+        ddim_steps = (int(sys.argv[sys.argv.index("--steps") + 1]) if "--steps" in sys.argv else 50) if sampler == "ddim" else None
+        sample(*(nums + [8, 20][len(nums):]), ddim_steps=ddim_steps)
+    elif mode == "ema":
+        ema(*(nums + [304_000_000, 20, 5][len(nums):]))
     else:
         raise SystemExit(__doc__)

@@ -1437,3 +1437,11 @@ def ddpm_step(x, pred, z, patch_size, c1, c2, sigma, out=None):
     with torch.no_grad():
         pred = pred if pred.is_contiguous() else pred.contiguous()
         return ops.ddpm_step(x, pred, z, int(patch_size), c1, c2, sigma, out=out)
+
+
+def ddim_step(x, pred, z, patch_size, coef, clip=None, out=None):
+    """one generalised reverse step (DDIM) on the image (no gradient); coef = (s_ab, s_1mab, r_ab, r_1mab, c_x0, c_eps, sigma) of
+    DDPM_Scheduler.ddim_coefficients; clip: clamp the predicted x0 to [-clip, clip] (None: no clamp)"""
+    with torch.no_grad():
+        pred = pred if pred.is_contiguous() else pred.contiguous()
+        return ops.ddim_step(x, pred, z, int(patch_size), *coef, clip=clip, out=out)

@@ -148,8 +148,10 @@ SIGNATURES = {
     "ucfvit_unshuffle_bwd": (c_int, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _P, _I, _P]),
     "ucfvit_patch_mse": (c_int, [_P, _P, _P, _P, _P, _I64, _I64, POINTER(c_int64), _I, _I64, _F, _P, _I, _P]),
     "ucfvit_adamw": (c_int, [_P, _P, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _F, _F, _F, _I, _P]),
+    "ucfvit_adamw_ema": (c_int, [_P, _P, _P, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _F, _F, _F, _F, _I, _P]),
     "ucfvit_grad_nonfinite": (c_int, [_P, _I64, _I, _F, _P, _P]),
     "ucfvit_adamw_scaled": (c_int, [_P, _P, _P, _P, _P, _I64, _F, _D, _D, _F, _F, _F, _I, _P, _P]),
+    "ucfvit_adamw_scaled_ema": (c_int, [_P, _P, _P, _P, _P, _P, _I64, _F, _D, _D, _F, _F, _F, _F, _I, _P, _P]),
     "ucfvit_grad_scaler_update": (c_int, [_P, _P]),
     "ucfvit_cast": (c_int, [_P, _P, _I64, _I, _I, _F, _P]),
     "ucfvit_transpose_batched": (c_int, [_P, _P, _P, _I64, _I64, _P]),
@@ -170,6 +172,7 @@ SIGNATURES = {
     "ucfvit_relu_dropout": (c_int, [_P, _P, _I64, _I64, _D, c_uint64, _I, _P]),
     "ucfvit_relu_dropout_bwd": (c_int, [_P, _P, _P, _I64, _I64, _D, c_uint64, _I, _P]),
     "ucfvit_ddpm_step": (c_int, [_P, _P, _P, _P, _I64, _I64, POINTER(c_int64), _I, _I64, _F, _F, _F, _I, _P]),
+    "ucfvit_ddim_step": (c_int, [_P, _P, _P, _P, _I64, _I64, POINTER(c_int64), _I, _I64, _F, _F, _F, _F, _F, _F, _F, _F, _I, _P]),
 }
 
 _lib = None

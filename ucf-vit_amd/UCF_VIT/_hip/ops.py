@@ -1533,6 +1533,31 @@ def adamw(p, g, m, v, shadow, lr, beta1, beta2, eps, weight_decay, step, grad_sc
                             weight_decay, bc1, bc2, grad_scale, dt(g), _stream()), "ucfvit_adamw")
 
 
+def ema_rate(decay):
+    """1 - decay, formed in double (the kernel's argument is rounded from it once); decay inside [0, 1)"""
+    decay = float(decay)
+    if not 0.0 <= decay < 1.0:
+        raise ValueError(f"ema_decay must be inside [0, 1), got {decay}")
+    return 1.0 - decay
+
+
+def _chk_ema(ema, p):
+    _chk(p, "adamw_ema.p")
+    if ema.dtype != torch.float32 or ema.numel() != p.numel() or not ema.is_contiguous():
+        raise ValueError("adamw_ema: ema must be a contiguous float32 tensor of p's size")
+    return _chk(ema, "adamw_ema.ema")
+
+
+def adamw_ema(p, g, m, v, shadow, ema, lr, beta1, beta2, eps, weight_decay, step, rate, grad_scale=1.0):
+    """adamw, and in the same pass ema += rate * (p_new - ema); rate = ema_rate(decay), a double inside (0, 1]"""
+    L = _l.load()
+    _chk_ema(ema, p)
+    bc1 = 1.0 - beta1 ** step
+    bc2 = 1.0 - beta2 ** step
+    _l.check(L.ucfvit_adamw_ema(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _p(shadow), ema.data_ptr(), p.numel(), lr,
+                                beta1, beta2, eps, weight_decay, bc1, bc2, grad_scale, rate, dt(g), _stream()), "ucfvit_adamw_ema")
+
+
 def _gs_state(state):
     if state.dtype != torch.float32 or state.numel() < _l.GS_STATE_FLOATS or not state.is_contiguous():
         raise ValueError(f"loss-scaler state must be a contiguous float32 tensor of {_l.GS_STATE_FLOATS} elements")
@@ -1552,6 +1577,15 @@ def adamw_scaled(p, g, m, v, shadow, lr, beta1, beta2, eps, weight_decay, state,
     L = _l.load()
     _l.check(L.ucfvit_adamw_scaled(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _p(shadow), p.numel(), lr, beta1, beta2, eps,
                                    weight_decay, grad_scale, dt(g), _gs_state(state).data_ptr(), _stream()), "ucfvit_adamw_scaled")
+
+
+def adamw_scaled_ema(p, g, m, v, shadow, ema, lr, beta1, beta2, eps, weight_decay, state, rate, grad_scale=1.0):
+    """adamw_scaled with the moving average of adamw_ema; a skipped step leaves ema alone"""
+    L = _l.load()
+    _chk_ema(ema, p)
+    _l.check(L.ucfvit_adamw_scaled_ema(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _p(shadow), ema.data_ptr(), p.numel(),
+                                       lr, beta1, beta2, eps, weight_decay, grad_scale, rate, dt(g), _gs_state(state).data_ptr(), _stream()),
+             "ucfvit_adamw_scaled_ema")
 
 
 def grad_scaler_update(state):
@@ -1940,29 +1974,48 @@ def relu_dropout_bwd(x, dy, p=0.0, seed=0, out=None):
     return out
 
 
-def ddpm_step(x, pred, z, patch, c1, c2, sigma, out=None):
-    """out = c1 * (x - c2 * unpatchify(pred)) + sigma * z without the unpatchified tensor: x, z, out fp32 NCHW(D), pred [B, L, p^nd C] in
-    fp32 or bf16; z None: no noise (sigma must be 0).  out may be x."""
-    L = _l.load()
-    _chk_f32(x, "ddpm_step.x"), _chk(pred, "ddpm_step.pred")
+def _step_args(name, x, pred, z, patch, out):
+    """the tensors of a reverse step, checked: -> (out, B, C, dims, nd)"""
+    _chk_f32(x, name + ".x"), _chk(pred, name + ".pred")
     if z is not None:
-        _chk_f32(z, "ddpm_step.z")
+        _chk_f32(z, name + ".z")
         if z.shape != x.shape:
-            raise ValueError("ddpm_step: z must have x's shape")
+            raise ValueError(f"{name}: z must have x's shape")
     B, C = x.shape[0], x.shape[1]
     sp = list(x.shape[2:])
     nd = len(sp)
     if nd not in (2, 3):
-        raise ValueError(f"ddpm_step: x must be NCHW or NCHWD, got {tuple(x.shape)}")
+        raise ValueError(f"{name}: x must be NCHW or NCHWD, got {tuple(x.shape)}")
     Lp = 1
     for s in sp:
         Lp *= s // patch
     if tuple(pred.shape) != (B, Lp, C * patch ** nd):
-        raise ValueError(f"ddpm_step: pred {tuple(pred.shape)} is not [B, L, p^nd C] = {(B, Lp, C * patch ** nd)} of x {tuple(x.shape)}")
-    out = torch.empty_like(x) if out is None else _chk_f32(out, "ddpm_step.out")
+        raise ValueError(f"{name}: pred {tuple(pred.shape)} is not [B, L, p^nd C] = {(B, Lp, C * patch ** nd)} of x {tuple(x.shape)}")
+    out = torch.empty_like(x) if out is None else _chk_f32(out, name + ".out")
     if out.shape != x.shape:
-        raise ValueError("ddpm_step: out must have x's shape")
-    dims = (ctypes.c_int64 * 3)(*(sp + [1] * (3 - nd)))
+        raise ValueError(f"{name}: out must have x's shape")
+    return out, B, C, (ctypes.c_int64 * 3)(*(sp + [1] * (3 - nd))), nd
+
+
+def ddpm_step(x, pred, z, patch, c1, c2, sigma, out=None):
+    """out = c1 * (x - c2 * unpatchify(pred)) + sigma * z without the unpatchified tensor: x, z, out fp32 NCHW(D), pred [B, L, p^nd C] in
+    fp32 or bf16; z None: no noise (sigma must be 0).  out may be x."""
+    L = _l.load()
+    out, B, C, dims, nd = _step_args("ddpm_step", x, pred, z, patch, out)
     _l.check(L.ucfvit_ddpm_step(x.data_ptr(), pred.data_ptr(), _p(z), out.data_ptr(), B, C, dims, nd, int(patch), float(c1), float(c2),
                                 float(sigma), dt(pred), _stream()), "ucfvit_ddpm_step")
+    return out
+
+
+def ddim_step(x, pred, z, patch, s_ab, s_1mab, r_ab, r_1mab, c_x0, c_eps, sigma, clip=0.0, out=None):
+    """the generalised reverse step of ucfvit_ddim_step, tensors as for ddpm_step: x0 = (x - s_1mab e) r_ab, clamped to [-clip, clip] when
+    clip > 0 (e then re-derived as (x - s_ab x0) r_1mab), out = c_x0 x0 + c_eps e + sigma z.  clip 0 or None: no clamp."""
+    L = _l.load()
+    clip = 0.0 if clip is None else float(clip)
+    if not clip >= 0.0:
+        raise ValueError(f"ddim_step: clip must be None, 0 or positive, got {clip}")
+    out, B, C, dims, nd = _step_args("ddim_step", x, pred, z, patch, out)
+    _l.check(L.ucfvit_ddim_step(x.data_ptr(), pred.data_ptr(), _p(z), out.data_ptr(), B, C, dims, nd, int(patch), float(s_ab), float(s_1mab),
+                                float(r_ab), float(r_1mab), float(c_x0), float(c_eps), float(sigma), clip, dt(pred), _stream()),
+             "ucfvit_ddim_step")
     return out

@@ -8,7 +8,15 @@ same pass); otherwise it falls back to one launch per parameter.
 Under a HipGradScaler (grad_scaler.py) the same two paths run ucfvit_grad_nonfinite over every gradient segment of every group first and
 then ucfvit_adamw_scaled, which skips itself on the device when the check fired (step_scaled below).  The host-side step counters then
 count CALLS; the number of applied steps, which the bias corrections use, lives in the scaler's device state.
+
+With `ema_decay` the same launches (ucfvit_adamw_ema / ucfvit_adamw_scaled_ema) also keep an exponential moving average of the weights,
+ema += (1 - decay) (p_new - ema): one fp32 buffer per flat run, one tensor per parameter on the fallback path, created at the first step as
+a copy of the parameters before that step's update.  The average is not optimizer state in torch's sense and stays out of state_dict(),
+which keeps the torch.optim.AdamW layout; ema_state_dict / load_ema_state_dict carry it as a model state_dict, and ema_weights() swaps it
+into the model for evaluation.
 """
+import contextlib
+
 import torch
 
 from . import ops
@@ -16,10 +24,15 @@ from .lib import GS_APPLIED_STEPS as _GS_APPLIED, GS_SKIPPED_STEPS as _GS_SKIPPE
 
 
 class HipAdamW(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0, ema_decay=None):
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        ema_rate = None if ema_decay is None else ops.ema_rate(ema_decay)      # 1 - decay in double; refuses a decay outside [0, 1)
         super().__init__(params, defaults)
         self.grad_scale = grad_scale  # multiplies gradients inside the kernel (e.g. 1/world_size, or 1/loss_scale)
+        # moving average of the weights (None: not kept).  _ema: parameter -> its average, a tensor of its own or a view into the buffer of
+        # its flat run; _ema_flat: (id(store), lo, hi) -> (store, lo, hi, buffer, params).  Neither is part of state_dict().
+        self.ema_decay, self._ema_rate = ema_decay, ema_rate
+        self._ema, self._ema_flat = {}, {}
         # flat moment buffers of the one-launch path, keyed (id(store), lo, hi).  They live on the optimizer object, NOT in self.state:
         # state_dict() then serialises only the per-parameter {step, exp_avg, exp_avg_sq} entries (views into these buffers) — the
         # torch.optim.AdamW layout the reference's checkpoints hold (train_class_simple.py:364-388) — and nothing keyed by an id()
@@ -112,11 +125,98 @@ class HipAdamW(torch.optim.Optimizer):
                     ops.grad_nonfinite(p.grad if p.grad.is_contiguous() else p.grad.contiguous(), gs, self.grad_scale)
         self._update(gs)
 
-    def _adamw(self, gs, p, g, m, v, shadow, lr, b1, b2, eps, wd, step):
-        if gs is None:
-            ops.adamw(p, g, m, v, shadow, lr, b1, b2, eps, wd, step, self.grad_scale)
+    def _adamw(self, gs, p, g, m, v, shadow, ema, lr, b1, b2, eps, wd, step):
+        if ema is None:
+            if gs is None:
+                ops.adamw(p, g, m, v, shadow, lr, b1, b2, eps, wd, step, self.grad_scale)
+            else:
+                ops.adamw_scaled(p, g, m, v, shadow, lr, b1, b2, eps, wd, gs, self.grad_scale)
+        elif gs is None:
+            ops.adamw_ema(p, g, m, v, shadow, ema, lr, b1, b2, eps, wd, step, self._ema_rate, self.grad_scale)
         else:
-            ops.adamw_scaled(p, g, m, v, shadow, lr, b1, b2, eps, wd, gs, self.grad_scale)
+            ops.adamw_scaled_ema(p, g, m, v, shadow, ema, lr, b1, b2, eps, wd, gs, self._ema_rate, self.grad_scale)
+
+    # ------------------------------------------------------------------------------------------------ moving average of the weights
+    def _ema_of_run(self, group, st, lo, hi):
+        """the average of a flat run: one buffer over [lo, hi), started from the parameters as they are now, or from the per-parameter
+        averages where the fallback path (or load_ema_state_dict) made some before; the parameters' entries become views into it"""
+        key = (id(st), lo, hi)
+        ent = self._ema_flat.get(key)
+        if ent is None or ent[0] is not st:
+            buf = st.flat_p[lo:hi].clone()
+            for p in group["params"]:
+                o, n = p._ucf_slot[1] - lo, p.numel()
+                if p in self._ema:
+                    buf[o:o + n].copy_(self._ema[p].reshape(-1))
+                self._ema[p] = buf[o:o + n].view(p.shape)
+            ent = self._ema_flat[key] = (st, lo, hi, buf, list(group["params"]))
+        return ent[3]
+
+    def _ema_of_param(self, p):
+        e = self._ema.get(p)
+        if e is None:
+            e = self._ema[p] = p.detach().clone(memory_format=torch.contiguous_format)
+        return e
+
+    def _params(self):
+        return [p for group in self.param_groups for p in group["params"]]
+
+    def ema_state_dict(self, module):
+        """module.state_dict() with every entry that is a parameter of this optimizer replaced by a clone of its average (the parameter's
+        own value before the first step).  Entries are matched by identity, so two names of one parameter both get the average."""
+        sd = module.state_dict()
+        for k, v in module.state_dict(keep_vars=True).items():
+            e = self._ema.get(v) if isinstance(v, torch.nn.Parameter) else None
+            if e is not None:
+                sd[k] = e.detach().clone()
+        return sd
+
+    @torch.no_grad()
+    def load_ema_state_dict(self, module, sd):
+        """the inverse of ema_state_dict: every parameter of this optimizer gets the average `sd` holds under its name in `module`"""
+        if self._ema_rate is None:
+            raise RuntimeError("load_ema_state_dict: this optimizer keeps no average (ema_decay=None)")
+        mine = set(self._params())
+        for k, v in module.state_dict(keep_vars=True).items():
+            if not (isinstance(v, torch.nn.Parameter) and v in mine):
+                continue
+            if k not in sd or tuple(sd[k].shape) != tuple(v.shape):
+                raise KeyError(f"load_ema_state_dict: no entry of shape {tuple(v.shape)} for {k}")
+            self._ema_of_param(v).copy_(sd[k].to(v.device, torch.float32))
+
+    @torch.no_grad()
+    def _swap_ema(self):
+        """exchange parameter and average contents in place (copies only: bit-exact), a flat run in three copies; the bf16 shadows and
+        their transposed copies no longer match the weights afterwards and are marked stale"""
+        done = set()
+        for st, lo, hi, buf, params in self._ema_flat.values():
+            if all(getattr(p, "_ucf_slot", None) is not None and p._ucf_slot[0] is st and st.owns(p, p._ucf_slot[1]) and
+                   self._ema[p].data_ptr() == buf.data_ptr() + 4 * (p._ucf_slot[1] - lo) for p in params):
+                tmp = buf.clone()
+                buf.copy_(st.flat_p[lo:hi])
+                st.flat_p[lo:hi].copy_(tmp)
+                done.update(params)
+        for p, e in self._ema.items():
+            if p not in done:
+                tmp = e.clone()
+                e.copy_(p)
+                p.copy_(tmp)
+        for p in self._ema:
+            slot = getattr(p, "_ucf_slot", None)
+            if slot is not None:
+                slot[0]._shadow_sig, slot[0]._t_fresh = None, False
+            if hasattr(p, "_ucf_shadow"):
+                del p._ucf_shadow
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """inside the context the model's parameters hold the averaged weights (and the averages hold the raw iterate); on exit both are
+        back, bit for bit.  Before the first step there is no average yet and nothing moves.  Not for use around step()."""
+        self._swap_ema()
+        try:
+            yield self
+        finally:
+            self._swap_ema()
 
     def _update(self, gs):
         for group in self.param_groups:
@@ -149,12 +249,16 @@ class HipAdamW(torch.optim.Optimizer):
                                              exp_avg_sq=ent["v"][o:o + p.numel()].view(p.shape))
                 ent["step"] += 1
                 shadow = st.flat_s[lo:hi] if st.flat_s is not None else None
-                self._adamw(gs, st.flat_p[lo:hi], st.flat_g[lo:hi], ent["m"], ent["v"], shadow, lr, b1, b2, eps, wd, ent["step"])
+                ema = self._ema_of_run(group, st, lo, hi) if self._ema_rate is not None else None
+                self._adamw(gs, st.flat_p[lo:hi], st.flat_g[lo:hi], ent["m"], ent["v"], shadow, ema, lr, b1, b2, eps, wd, ent["step"])
                 for p in group["params"]:
                     self.state[p]["step"] += 1
                 if shadow is not None:
                     st.note_shadow_fresh()      # (also after a skipped step: the shadow still equals p, neither moved)
                 continue
+            if self._ema_rate is not None:
+                for p in group["params"]:
+                    self._ema_of_param(p)           # also of a parameter without a gradient: its average is the parameter itself
             for p in group["params"]:
                 if p.grad is None:
                     continue
@@ -165,7 +269,7 @@ class HipAdamW(torch.optim.Optimizer):
                     s["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                 s["step"] += 1
                 g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
-                self._adamw(gs, p.data, g, s["exp_avg"], s["exp_avg_sq"], None, lr, b1, b2, eps, wd, int(s["step"]))
+                self._adamw(gs, p.data, g, s["exp_avg"], s["exp_avg_sq"], None, self._ema.get(p), lr, b1, b2, eps, wd, int(s["step"]))
                 p._version  # (kernel wrote p in place; bf16 shadows are re-cast lazily via the store signature)
                 slot = getattr(p, "_ucf_slot", None)
                 if slot is not None:

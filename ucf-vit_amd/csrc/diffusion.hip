@@ -2,6 +2,7 @@
 //   ucfvit_ddpm_q_sample      forward noising            out[b][i] = sqrt_ab[t[b]] x0[b][i] + sqrt_1mab[t[b]] eps[b][i]
 //   ucfvit_relu_dropout[_bwd] hidden layer of the time MLP   y = f m max(x, 0),   dx = f m [x > 0] dy    (mask of csrc/dropout_mask.h)
 //   ucfvit_ddpm_step          one ancestral reverse step     out = c1 (x - c2 eps_hat) + sigma z, eps_hat read in the patch layout of pred
+//   ucfvit_ddim_step          one generalised reverse step   out = c_x0 x0_hat + c_eps eps_hat + sigma z, x0_hat optionally clamped
 // (the token assembly with the time row, ucfvit_time_tokens_fwd / _bwd, lives with the token kernels in csrc/elementwise.hip).
 // All are bound by memory: fp32 arithmetic, one rounding to the output type, 16-byte accesses where sizes and pointers allow and an element
 // path with the same results otherwise, no atomics.  The file is compiled without fma contraction (Makefile): every product and sum below
@@ -119,6 +120,58 @@ __global__ __launch_bounds__(DF_BLOCK) void ddpm_step_kernel(const float* x, con
     }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// generalised reverse step (DDIM, and DDPM through its x0 form): the predicted x0 from eps_hat, optionally clamped to [-clip, clip] with
+// eps_hat then re-derived from the clamped x0, and out = c_x0 x0 + c_eps eps_hat (+ sigma z).  Same work split and scatter as
+// ddpm_step_kernel, so out may be x.  The clamp is two selects: a NaN x0 fails both comparisons and stays a NaN.
+// ---------------------------------------------------------------------------------------------------
+struct DdimCoef {
+    float s_ab, s_1mab, r_ab, r_1mab, c_x0, c_eps, sigma, clip;
+};
+
+template <typename T, bool HAS_Z, bool CLIP>
+__global__ __launch_bounds__(DF_BLOCK) void ddim_step_kernel(const float* x, const T* __restrict__ pred, const float* __restrict__ z,
+                                                             float* out, PatchGeom g, int64_t B, DdimCoef k) {
+    const int64_t total = B * g.L * g.P;
+    for (int64_t i = (int64_t)blockIdx.x * DF_BLOCK + threadIdx.x; i < total; i += (int64_t)gridDim.x * DF_BLOCK) {
+        const int e = i % g.P;
+        const int64_t bl = i / g.P;
+        const int l = bl % g.L;
+        const int64_t b = bl / g.L;
+        const int64_t q = patch_pixel_index(g, b, l, e);
+        const float xv = x[q];
+        float eh = to_f32<T>(pred[i]);
+        float x0 = (xv - k.s_1mab * eh) * k.r_ab;
+        if (CLIP) {
+            x0 = x0 < -k.clip ? -k.clip : (x0 > k.clip ? k.clip : x0);
+            eh = (xv - k.s_ab * x0) * k.r_1mab;
+        }
+        const float o = k.c_x0 * x0 + k.c_eps * eh;
+        out[q] = HAS_Z ? o + k.sigma * z[q] : o;
+    }
+}
+
+// the checks ucfvit_ddpm_step and ucfvit_ddim_step share; *pg is filled when B > 0
+int step_check(const char* name, const float* x, const void* pred, const float* z, float* out, int64_t B, int64_t C, const int64_t* dims,
+               int nd, int64_t p, float sigma, int dtype, PatchGeom* pg) {
+    UCF_CHECK_ARG(x && pred && out && dims, "%s: null pointer", name);
+    UCF_CHECK_ARG(nd == 2 || nd == 3, "%s: nd must be 2 or 3", name);
+    UCF_CHECK_ARG(DTYPE_OK(dtype), "%s: bad dtype %d", name, dtype);
+    UCF_CHECK_ARG(B >= 0 && C > 0 && p > 0 && B < (1ll << 31) && C < (1ll << 16) && p < (1ll << 16), "%s: bad sizes", name);
+    int64_t pixels = 1;
+    for (int i = 0; i < nd; ++i) {
+        UCF_CHECK_ARG(dims[i] > 0 && dims[i] < (1ll << 31) && dims[i] % p == 0, "%s: image dim %d (%lld) not a multiple of p=%lld", name, i,
+                      (long long)dims[i], (long long)p);
+        pixels *= dims[i];
+        UCF_CHECK_ARG(pixels * C < (1ll << 31), "%s: a sample has 2^31 elements or more", name);   // L, P and the products inside
+    }                                                                                                // patch_pixel_index are ints
+    UCF_CHECK_ARG(z || sigma == 0.f, "%s: sigma=%g without noise (z == NULL needs sigma == 0)", name, (double)sigma);
+    UCF_CHECK_ARG((((uintptr_t)x | (uintptr_t)z | (uintptr_t)out) & 3) == 0 && (((uintptr_t)pred) & (dtype == UCFVIT_F32 ? 3 : 1)) == 0,
+                  "%s: misaligned pointer", name);
+    if (B > 0) *pg = patch_geom_make(C, dims, nd, p);
+    return UCFVIT_OK;
+}
+
 }  // namespace
 
 extern "C" int ucfvit_ddpm_q_sample(const float* x0, const float* eps, const int64_t* t, const float* sqrt_ab, const float* sqrt_1mab,
@@ -165,22 +218,10 @@ extern "C" int ucfvit_relu_dropout_bwd(const void* x, const void* dy, void* dx, 
 
 extern "C" int ucfvit_ddpm_step(const float* x, const void* pred, const float* z, float* out, int64_t B, int64_t C, const int64_t* dims, int nd,
                                 int64_t p, float c1, float c2, float sigma, int dtype, void* stream) {
-    UCF_CHECK_ARG(x && pred && out && dims, "ucfvit_ddpm_step: null pointer");
-    UCF_CHECK_ARG(nd == 2 || nd == 3, "ucfvit_ddpm_step: nd must be 2 or 3");
-    UCF_CHECK_ARG(DTYPE_OK(dtype), "ucfvit_ddpm_step: bad dtype %d", dtype);
-    UCF_CHECK_ARG(B >= 0 && C > 0 && p > 0 && B < (1ll << 31) && C < (1ll << 16) && p < (1ll << 16), "ucfvit_ddpm_step: bad sizes");
-    int64_t pixels = 1;
-    for (int i = 0; i < nd; ++i) {
-        UCF_CHECK_ARG(dims[i] > 0 && dims[i] < (1ll << 31) && dims[i] % p == 0, "ucfvit_ddpm_step: image dim %d (%lld) not a multiple of p=%lld", i,
-                      (long long)dims[i], (long long)p);
-        pixels *= dims[i];
-        UCF_CHECK_ARG(pixels * C < (1ll << 31), "ucfvit_ddpm_step: a sample has 2^31 elements or more");   // L, P and the products inside
-    }                                                                                                        // patch_pixel_index are ints
-    UCF_CHECK_ARG(z || sigma == 0.f, "ucfvit_ddpm_step: sigma=%g without noise (z == NULL is step 0, whose sigma is 0)", (double)sigma);
-    UCF_CHECK_ARG((((uintptr_t)x | (uintptr_t)z | (uintptr_t)out) & 3) == 0 && (((uintptr_t)pred) & (dtype == UCFVIT_F32 ? 3 : 1)) == 0,
-                  "ucfvit_ddpm_step: misaligned pointer");
+    PatchGeom g;
+    const int rc = step_check("ucfvit_ddpm_step", x, pred, z, out, B, C, dims, nd, p, sigma, dtype, &g);
+    if (rc != UCFVIT_OK) return rc;
     if (B == 0) return UCFVIT_OK;
-    const PatchGeom g = patch_geom_make(C, dims, nd, p);
     const int64_t total = B * g.L * g.P;
     hipStream_t s = (hipStream_t)stream;
 #define ST_GO(T, HZ)                                                                                                                          \
@@ -192,5 +233,33 @@ extern "C" int ucfvit_ddpm_step(const float* x, const void* pred, const float* z
     }
 #undef ST_GO
     UCF_LAUNCH_CHECK("ucfvit_ddpm_step");
+    return UCFVIT_OK;
+}
+
+extern "C" int ucfvit_ddim_step(const float* x, const void* pred, const float* z, float* out, int64_t B, int64_t C, const int64_t* dims, int nd,
+                                int64_t p, float s_ab, float s_1mab, float r_ab, float r_1mab, float c_x0, float c_eps, float sigma, float clip,
+                                int dtype, void* stream) {
+    PatchGeom g;
+    const int rc = step_check("ucfvit_ddim_step", x, pred, z, out, B, C, dims, nd, p, sigma, dtype, &g);
+    if (rc != UCFVIT_OK) return rc;
+    UCF_CHECK_ARG(clip >= 0.f, "ucfvit_ddim_step: clip %g must be 0 (no clamp) or positive", (double)clip);   // false for NaN
+    if (B == 0) return UCFVIT_OK;
+    const int64_t total = B * g.L * g.P;
+    const DdimCoef k{s_ab, s_1mab, r_ab, r_1mab, c_x0, c_eps, sigma, clip};
+    hipStream_t s = (hipStream_t)stream;
+#define DI_GO(T, HZ, CL)                                                                                                                       \
+    hipLaunchKernelGGL((ddim_step_kernel<T, HZ, CL>), dim3(df_grid(total)), dim3(DF_BLOCK), 0, s, x, (const T*)pred, z, out, g, B, k)
+#define DI_Z(T, CL)                                                                                                                            \
+    do {                                                                                                                                       \
+        if (z) DI_GO(T, true, CL); else DI_GO(T, false, CL);                                                                                  \
+    } while (0)
+    if (dtype == UCFVIT_F32) {
+        if (clip > 0.f) DI_Z(float, true); else DI_Z(float, false);
+    } else {
+        if (clip > 0.f) DI_Z(bf16, true); else DI_Z(bf16, false);
+    }
+#undef DI_Z
+#undef DI_GO
+    UCF_LAUNCH_CHECK("ucfvit_ddim_step");
     return UCFVIT_OK;
 }

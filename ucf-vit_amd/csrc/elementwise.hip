@@ -452,7 +452,15 @@ template <typename G>
 __global__ void adamw_kernel(float* __restrict__ p, const G* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                              bf16* __restrict__ shadow, int64_t n, float lr, float b1, float b2, float eps, float wd, float bc1,
                              float bc2_sqrt, float gscale) {
-    adamw_update<G>(p, g, m, v, shadow, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale);
+    adamw_update<G, false>(p, g, m, v, shadow, nullptr, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale, 0.f);
+}
+
+// the same pass with the weights' exponential moving average: ema += rate * (p_new - ema)
+template <typename G>
+__global__ void adamw_ema_kernel(float* __restrict__ p, const G* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                 bf16* __restrict__ shadow, float* __restrict__ ema, int64_t n, float lr, float b1, float b2, float eps,
+                                 float wd, float bc1, float bc2_sqrt, float gscale, float rate) {
+    adamw_update<G, true>(p, g, m, v, shadow, ema, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale, rate);
 }
 
 template <typename S, typename Dd>
@@ -816,6 +824,32 @@ extern "C" int ucfvit_adamw(float* p, const void* g, float* m, float* v, void* s
                            beta2, eps, weight_decay, bias_corr1, bc2s, grad_scale);
     }
     UCF_LAUNCH_CHECK("ucfvit_adamw");
+    return UCFVIT_OK;
+}
+
+extern "C" int ucfvit_adamw_ema(float* p, const void* g, float* m, float* v, void* shadow_bf16, float* ema, int64_t n, float lr, float beta1,
+                                float beta2, float eps, float weight_decay, float bias_corr1, float bias_corr2, float grad_scale,
+                                float ema_rate, int grad_dtype, void* stream) {
+    UCF_CHECK_ARG(p && g && m && v && ema, "ucfvit_adamw_ema: null pointer");
+    UCF_CHECK_ARG(n >= 0, "ucfvit_adamw_ema: negative size");
+    UCF_CHECK_ARG(DTYPE_OK(grad_dtype), "ucfvit_adamw_ema: bad grad dtype %d", grad_dtype);
+    UCF_CHECK_ARG(ema_rate > 0.f && ema_rate <= 1.f, "ucfvit_adamw_ema: ema_rate %g outside (0, 1]", (double)ema_rate);   // false for NaN
+    UCF_CHECK_ARG(ucf_is_aligned16(p) && ucf_is_aligned16(m) && ucf_is_aligned16(v) && ucf_is_aligned16(ema) && (((uintptr_t)g) % 8 == 0) &&
+                      (((uintptr_t)shadow_bf16) % 8 == 0),
+                  "ucfvit_adamw_ema: pointers must be 16-byte aligned (grad/shadow 8)");
+    if (n == 0) return UCFVIT_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned grid = ew_grid((n + 3) / 4);
+    const float bc2s = sqrtf(bias_corr2);
+    if (grad_dtype == UCFVIT_F32) {
+        UCF_CHECK_ARG(ucf_is_aligned16(g), "ucfvit_adamw_ema: fp32 grads must be 16-byte aligned");
+        hipLaunchKernelGGL(adamw_ema_kernel<float>, dim3(grid), dim3(256), 0, s, p, (const float*)g, m, v, (bf16*)shadow_bf16, ema, n, lr,
+                           beta1, beta2, eps, weight_decay, bias_corr1, bc2s, grad_scale, ema_rate);
+    } else {
+        hipLaunchKernelGGL(adamw_ema_kernel<bf16>, dim3(grid), dim3(256), 0, s, p, (const bf16*)g, m, v, (bf16*)shadow_bf16, ema, n, lr,
+                           beta1, beta2, eps, weight_decay, bias_corr1, bc2s, grad_scale, ema_rate);
+    }
+    UCF_LAUNCH_CHECK("ucfvit_adamw_ema");
     return UCFVIT_OK;
 }
 

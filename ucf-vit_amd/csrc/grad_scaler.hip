@@ -61,7 +61,21 @@ __global__ void adamw_scaled_kernel(float* __restrict__ p, const G* __restrict__
     const double t = (double)state[UCFVIT_GS_APPLIED_STEPS] + 1.0;
     const float bc1 = (float)(1.0 - pow(b1, t));                      // formed in double, rounded once: as ops.adamw does on the host
     const float bc2 = (float)(1.0 - pow(b2, t));
-    adamw_update<G>(p, g, m, v, shadow, n, lr, (float)b1, (float)b2, eps, wd, bc1, sqrtf(bc2), gscale * state[UCFVIT_GS_INV_SCALE]);
+    adamw_update<G, false>(p, g, m, v, shadow, nullptr, n, lr, (float)b1, (float)b2, eps, wd, bc1, sqrtf(bc2),
+                           gscale * state[UCFVIT_GS_INV_SCALE], 0.f);
+}
+
+// the same with the weights' exponential moving average, which a skipped step leaves alone as it leaves p, m, v and the shadow
+template <typename G>
+__global__ void adamw_scaled_ema_kernel(float* __restrict__ p, const G* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                        bf16* __restrict__ shadow, float* __restrict__ ema, int64_t n, float lr, double b1, double b2,
+                                        float eps, float wd, float gscale, float rate, const float* __restrict__ state) {
+    if (state[UCFVIT_GS_FOUND_INF] != 0.f) return;
+    const double t = (double)state[UCFVIT_GS_APPLIED_STEPS] + 1.0;
+    const float bc1 = (float)(1.0 - pow(b1, t));
+    const float bc2 = (float)(1.0 - pow(b2, t));
+    adamw_update<G, true>(p, g, m, v, shadow, ema, n, lr, (float)b1, (float)b2, eps, wd, bc1, sqrtf(bc2),
+                          gscale * state[UCFVIT_GS_INV_SCALE], rate);
 }
 
 // torch's _amp_update_scale_ + the reference's floor; one thread
@@ -140,6 +154,32 @@ extern "C" int ucfvit_adamw_scaled(float* p, const void* g, float* m, float* v, 
                            beta1, beta2, eps, weight_decay, grad_scale, state);
     }
     UCF_LAUNCH_CHECK("ucfvit_adamw_scaled");
+    return UCFVIT_OK;
+}
+
+extern "C" int ucfvit_adamw_scaled_ema(float* p, const void* g, float* m, float* v, void* shadow_bf16, float* ema, int64_t n, float lr,
+                                       double beta1, double beta2, float eps, float weight_decay, float grad_scale, float ema_rate,
+                                       int grad_dtype, const float* state, void* stream) {
+    UCF_CHECK_ARG(p && g && m && v && ema, "ucfvit_adamw_scaled_ema: null pointer");
+    UCF_CHECK_ARG(state, "ucfvit_adamw_scaled_ema: null state");
+    UCF_CHECK_ARG(n >= 0, "ucfvit_adamw_scaled_ema: negative size");
+    UCF_CHECK_ARG(DTYPE_OK(grad_dtype), "ucfvit_adamw_scaled_ema: bad grad dtype %d", grad_dtype);
+    UCF_CHECK_ARG(ema_rate > 0.f && ema_rate <= 1.f, "ucfvit_adamw_scaled_ema: ema_rate %g outside (0, 1]", (double)ema_rate);   // false for NaN
+    UCF_CHECK_ARG(ucf_is_aligned16(p) && ucf_is_aligned16(m) && ucf_is_aligned16(v) && ucf_is_aligned16(ema) && (((uintptr_t)g) % 8 == 0) &&
+                      (((uintptr_t)shadow_bf16) % 8 == 0) && (((uintptr_t)state) % 4 == 0),
+                  "ucfvit_adamw_scaled_ema: pointers must be 16-byte aligned (grad/shadow 8, state 4)");
+    if (n == 0) return UCFVIT_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned grid = grid_for((n + 3) / 4, 256, 256 * 8);       // ucfvit_adamw's grid
+    if (grad_dtype == UCFVIT_F32) {
+        UCF_CHECK_ARG(ucf_is_aligned16(g), "ucfvit_adamw_scaled_ema: fp32 grads must be 16-byte aligned");
+        hipLaunchKernelGGL(adamw_scaled_ema_kernel<float>, dim3(grid), dim3(256), 0, s, p, (const float*)g, m, v, (bf16*)shadow_bf16, ema, n,
+                           lr, beta1, beta2, eps, weight_decay, grad_scale, ema_rate, state);
+    } else {
+        hipLaunchKernelGGL(adamw_scaled_ema_kernel<bf16>, dim3(grid), dim3(256), 0, s, p, (const bf16*)g, m, v, (bf16*)shadow_bf16, ema, n,
+                           lr, beta1, beta2, eps, weight_decay, grad_scale, ema_rate, state);
+    }
+    UCF_LAUNCH_CHECK("ucfvit_adamw_scaled_ema");
     return UCFVIT_OK;
 }
 

@@ -4,7 +4,10 @@ training_scripts/train_diffusion_simple.py:  python train_diffusion_simple.py <c
 
 Per batch (reference :322-344): t ~ U{0..T-1} per sample, e ~ N(0, I), x_t = sqrt(abar_t) x + sqrt(1 - abar_t) e, loss =
 MSE(unpatchify(model(x_t, t)), e).  Here t and e are drawn on the device from a per-rank generator, the noising is HF.q_sample, and the loss
-kernel reads e in place (HF.patch_mse without a mask is MSELoss(unpatchify(pred), e)); unpatchify(pred) is never materialised."""
+kernel reads e in place (HF.patch_mse without a mask is MSELoss(unpatchify(pred), e)); unpatchify(pred) is never materialised.
+
+`model: ema_decay` (absent: off) keeps an exponential moving average of the weights inside the AdamW pass; the checkpoint then also holds
+`model_ema_state_dict`, which inference_diffusion_simple.py samples from and a resumed run continues."""
 import sys
 
 import torch
@@ -43,6 +46,16 @@ def training_step(data, variables, t, e, net, ddpm, patch_size, loss_fn):
     return HF.patch_mse(net(x_t, t, variables), e, patch_size)
 
 
+def resume(conf, net, optimizer, scheduler, scaler):
+    """maybe_resume, and under `model: ema_decay` the weights' moving average from the checkpoint's `model_ema_state_dict`; a checkpoint
+    written without one resumes with the average restarted from the loaded weights"""
+    extras = {"model_ema_state_dict": None}
+    epoch_start, loss_list = maybe_resume(conf, net, optimizer, scheduler, scaler, extras=extras)
+    if optimizer.ema_decay is not None and extras["model_ema_state_dict"] is not None:
+        optimizer.load_ema_state_dict(net, extras["model_ema_state_dict"])
+    return epoch_start, loss_list
+
+
 def main(device, local_rank, rank, world):
     conf = load_config(sys.argv[1])
     model, margs, a, d = build_model(conf, device)
@@ -61,10 +74,12 @@ def main(device, local_rank, rank, world):
     # and can be compared.  It is not DDPM training: each image would meet one (t, noise, mask) for the whole run.
     replay = bool(conf["trainer"].get("replay_noise_per_epoch", False))
     net = HipDataParallel(model)
-    optimizer = configure_optimizer(model, float(m["lr"]), float(m["beta_1"]), float(m["beta_2"]), float(m["weight_decay"]))
+    ema_decay = m.get("ema_decay")
+    optimizer = configure_optimizer(model, float(m["lr"]), float(m["beta_1"]), float(m["beta_2"]), float(m["weight_decay"]),
+                                    ema_decay=None if ema_decay is None else float(ema_decay))
     scheduler = configure_scheduler(optimizer, int(m["warmup_steps"]), int(m["max_steps"]), float(m["warmup_start_lr"]), float(m["eta_min"]))
     scaler = configure_grad_scaler(bool(m.get("use_grad_scaler", False)))
-    epoch_start, loss_list = maybe_resume(conf, net, optimizer, scheduler, scaler)
+    epoch_start, loss_list = resume(conf, net, optimizer, scheduler, scaler)
     variables = d["dict_in_variables"][d["dataset"]]
     loss_fn = m.get("loss_fn", "MSE")
     loader = SyntheticLoader(d["batch_size"], margs["in_chans"], margs["img_size"], 0, iters_per_epoch(conf), device, 1234 + rank)
@@ -93,7 +108,8 @@ def main(device, local_rank, rank, world):
         loss_list.append(epoch_loss)
         if rank == 0:
             print(f"epoch: {epoch} epoch_loss {epoch_loss.item():.4f} images/s {timer.rate():.1f}", flush=True)
-        save_checkpoint(conf, epoch, net, optimizer, scheduler, loss_list, rank, scaler)
+        save_checkpoint(conf, epoch, net, optimizer, scheduler, loss_list, rank, scaler,
+                        extra=None if ema_decay is None else {"model_ema_state_dict": optimizer.ema_state_dict(net)})
 
 
 if __name__ == "__main__":
