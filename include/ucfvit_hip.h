@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define UCFVIT_ABI_VERSION 24 /* still 24 with the dropout, LayerScale, QK-norm, DDPM, EMA and DDIM entry points (ucfvit_dropout*, ucfvit_layer_scale_*, ucfvit_qk_norm_*, ucfvit_ddpm_*, ucfvit_time_tokens_*, ucfvit_relu_dropout*, ucfvit_adamw_ema, ucfvit_adamw_scaled_ema, ucfvit_ddim_step): symbols were only added */
+#define UCFVIT_ABI_VERSION 24 /* still 24 with the dropout, LayerScale, QK-norm, DDPM, EMA and DDIM entry points (ucfvit_dropout*, ucfvit_layer_scale_*, ucfvit_qk_norm_*, ucfvit_ddpm_*, ucfvit_time_tokens_*, ucfvit_relu_dropout*, ucfvit_adamw_ema, ucfvit_adamw_scaled_ema, ucfvit_ddim_step, ucfvit_grad_sqnorm*, ucfvit_grad_clip_coef, ucfvit_adamw_clipped): symbols were only added */
 
 #define UCFVIT_OK 0
 #define UCFVIT_ERR_INVALID_ARGUMENT (-1)
@@ -467,6 +467,38 @@ int ucfvit_adamw_scaled_ema(float* p, const void* g, float* m, float* v, void* s
                             double beta2, float eps, float weight_decay, float grad_scale, float ema_rate, int grad_dtype,
                             const float* state, void* stream);
 int ucfvit_grad_scaler_update(float* state, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Gradient clipping by global L2 norm (torch.nn.utils.clip_grad_norm_'s rule) folded into AdamW: gradients are never rewritten and the host
+ * never reads the norm.  The clip state is ONE device array of UCFVIT_GC_STATE_FLOATS fp32 owned by the caller:
+ *   [MAX_NORM] the threshold, written by the host   [NORM] the global norm of the last step before clipping, of the gradients as AdamW
+ *   consumes them (after grad_scale and, under a loss scaler, after the division by the scale)   [COEF] min(1, MAX_NORM / (NORM + 1e-6));
+ *   the rest is spare.
+ *
+ * grad_sqnorm:   one read-only pass over one gradient segment (fp32 or bf16).  Workgroup b writes partials[b] = the sum in double of x^2,
+ *                x = g[i] * k rounded to fp32 as AdamW forms it, k = mult (gs_state NULL) or mult * gs_state[INV_SCALE].  With gs_state the
+ *                same pass sets gs_state[FOUND_INF] under ucfvit_grad_nonfinite's rule and never clears it: it replaces that launch.
+ *                ucfvit_grad_sqnorm_partials(n, dtype) (host only) is the number of partials such a call writes: 0 for n = 0, when g and
+ *                partials may be NULL; -1 for a negative n or an unknown dtype.  Segments are laid side by side in one workspace with it.
+ * grad_clip_coef: one workgroup sums `count` partials in a fixed order and writes NORM = (float)sqrt(sum) and COEF.  An Inf norm gives
+ *                COEF = 0, a NaN norm a NaN COEF, as torch's clamp does.  count = 0: NORM = 0.
+ *                No atomics anywhere: NORM's bits are a function of the gradients and the segment layout alone, so data-parallel ranks
+ *                reach the same COEF from the same all-reduced buffer without a collective.
+ * adamw_clipped: ema NULL, gs_state NULL: ucfvit_adamw with the gradient factor grad_scale * COEF.  ema given: ucfvit_adamw_ema likewise.
+ *                gs_state given: ucfvit_adamw_scaled(_ema) with (grad_scale * INV_SCALE) * COEF; bias_corr1/2 are then ignored, the
+ *                corrections come from APPLIED_STEPS, and a step whose check fired returns before touching anything.  With COEF = 1 every
+ *                output has the bits of the respective entry point without clipping.
+ * ------------------------------------------------------------------------------------------------------ */
+#define UCFVIT_GC_MAX_NORM 0
+#define UCFVIT_GC_NORM 1
+#define UCFVIT_GC_COEF 2
+#define UCFVIT_GC_STATE_FLOATS 8
+int64_t ucfvit_grad_sqnorm_partials(int64_t n, int dtype);
+int ucfvit_grad_sqnorm(const void* g, int64_t n, int dtype, float mult, float* gs_state, double* partials, void* stream);
+int ucfvit_grad_clip_coef(const double* partials, int64_t count, float* clip_state, void* stream);
+int ucfvit_adamw_clipped(float* p, const void* g, float* m, float* v, void* shadow_bf16, float* ema, int64_t n, float lr, double beta1,
+                         double beta2, float eps, float weight_decay, float bias_corr1, float bias_corr2, float grad_scale, float ema_rate,
+                         int grad_dtype, const float* gs_state, const float* clip_state, void* stream);
 
 /* dtype conversion / scaling helpers (fp32 master → bf16 shadow cast; bf16 gradient transport for the DP all-reduce) */
 int ucfvit_cast(const void* src, void* dst, int64_t n, int src_dtype, int dst_dtype, float scale, void* stream);

@@ -96,7 +96,7 @@ class HipGradScaler:
 
     def unscale_(self, optimizer):
         raise NotImplementedError("HipGradScaler.unscale_ is not provided: unscaling is folded into AdamW's read, and nothing here clips "
-                                  "gradients")
+                                  "gradients; clipping by global norm is HipAdamW(max_grad_norm=...), inside the same read")
 
     # ------------------------------------------------------------------ host-side views (these synchronise)
     def get_scale(self):

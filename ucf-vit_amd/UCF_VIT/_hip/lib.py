@@ -14,6 +14,8 @@ GEMM_SCHED_BYTES = 1024
 # loss-scaler state block (UCFVIT_GS_* of include/ucfvit_hip.h)
 GS_SCALE, GS_INV_SCALE, GS_FOUND_INF, GS_GROWTH_TRACKER, GS_APPLIED_STEPS, GS_SKIPPED_STEPS = 0, 1, 2, 3, 4, 5
 GS_GROWTH_FACTOR, GS_BACKOFF_FACTOR, GS_GROWTH_INTERVAL, GS_MIN_SCALE, GS_STATE_FLOATS = 6, 7, 8, 9, 16
+# gradient-clipping state block (UCFVIT_GC_*)
+GC_MAX_NORM, GC_NORM, GC_COEF, GC_STATE_FLOATS = 0, 1, 2, 8
 # label dtypes and resampling modes of the label serializers / tree deserializers (UCFVIT_LABEL_*, UCFVIT_RESAMPLE_*)
 LABEL_U8, LABEL_I64 = 0, 1
 RESAMPLE_SMOOTH, RESAMPLE_NEAREST = 0, 1
@@ -153,6 +155,10 @@ SIGNATURES = {
     "ucfvit_adamw_scaled": (c_int, [_P, _P, _P, _P, _P, _I64, _F, _D, _D, _F, _F, _F, _I, _P, _P]),
     "ucfvit_adamw_scaled_ema": (c_int, [_P, _P, _P, _P, _P, _P, _I64, _F, _D, _D, _F, _F, _F, _F, _I, _P, _P]),
     "ucfvit_grad_scaler_update": (c_int, [_P, _P]),
+    "ucfvit_grad_sqnorm_partials": (c_int64, [_I64, _I]),
+    "ucfvit_grad_sqnorm": (c_int, [_P, _I64, _I, _F, _P, _P, _P]),
+    "ucfvit_grad_clip_coef": (c_int, [_P, _I64, _P, _P]),
+    "ucfvit_adamw_clipped": (c_int, [_P, _P, _P, _P, _P, _P, _I64, _F, _D, _D, _F, _F, _F, _F, _F, _F, _I, _P, _P, _P]),
     "ucfvit_cast": (c_int, [_P, _P, _I64, _I, _I, _F, _P]),
     "ucfvit_transpose_batched": (c_int, [_P, _P, _P, _I64, _I64, _P]),
     "ucfvit_drop_path_colsum_rows": (_I64, [_I64, _I64, _I64]),

@@ -1593,6 +1593,67 @@ def grad_scaler_update(state):
     _l.check(L.ucfvit_grad_scaler_update(_gs_state(state).data_ptr(), _stream()), "ucfvit_grad_scaler_update")
 
 
+def _gc_state(state):
+    if state.dtype != torch.float32 or state.numel() < _l.GC_STATE_FLOATS or not state.is_contiguous():
+        raise ValueError(f"clip state must be a contiguous float32 tensor of {_l.GC_STATE_FLOATS} elements")
+    return _chk(state, "clip state")
+
+
+def _gc_partials(partials, need):
+    if partials.dtype != torch.float64 or not partials.is_contiguous() or partials.numel() < need:
+        raise ValueError(f"partials must be a contiguous float64 tensor of at least {need} elements")
+    return _chk(partials, "partials")
+
+
+def grad_sqnorm_partials(n, dtype):
+    """how many partial sums grad_sqnorm writes for a segment of n elements of `dtype` (0 for an empty one); host only"""
+    L = _l.load()
+    try:
+        code = _DT[dtype]
+    except KeyError:
+        raise TypeError(f"UCF_VIT HIP ops support float32 and bfloat16 tensors, got {dtype}")
+    count = L.ucfvit_grad_sqnorm_partials(n, code)
+    if count < 0:
+        _l.check(-1, "ucfvit_grad_sqnorm_partials")
+    return count
+
+
+def grad_sqnorm(g, partials, mult=1.0, gs_state=None):
+    """partials[:grad_sqnorm_partials(...)] = per-workgroup sums in double of (g * k)^2, k = mult or mult * gs_state[GS_INV_SCALE]; with
+    gs_state the pass also sets gs_state[GS_FOUND_INF] as grad_nonfinite would.  Read-only over g, no host synchronisation.  Returns the
+    number of partials written."""
+    L = _l.load()
+    _chk(g, "grad_sqnorm.g")
+    count = grad_sqnorm_partials(g.numel(), g.dtype)
+    _gc_partials(partials, count)
+    _l.check(L.ucfvit_grad_sqnorm(g.data_ptr(), g.numel(), dt(g), mult, None if gs_state is None else _gs_state(gs_state).data_ptr(),
+                                  partials.data_ptr(), _stream()), "ucfvit_grad_sqnorm")
+    return count
+
+
+def grad_clip_coef(partials, count, clip_state):
+    """clip_state[GC_NORM] = sqrt(sum of partials[:count]), clip_state[GC_COEF] = min(1, clip_state[GC_MAX_NORM] / (norm + 1e-6))"""
+    L = _l.load()
+    _gc_partials(partials, count)
+    _l.check(L.ucfvit_grad_clip_coef(partials.data_ptr(), count, _gc_state(clip_state).data_ptr(), _stream()), "ucfvit_grad_clip_coef")
+
+
+def clipped_adamw(p, g, m, v, shadow, ema, lr, beta1, beta2, eps, weight_decay, step, rate, clip_state, gs_state=None, grad_scale=1.0):
+    """adamw / adamw_ema (gs_state None) or adamw_scaled / adamw_scaled_ema with clip_state[GC_COEF] multiplied into the gradient factor; ema
+    (and rate) may be None.  `step` forms the bias corrections as adamw does and is not used under a loss scaler."""
+    L = _l.load()
+    if ema is not None:
+        _chk_ema(ema, p)
+    bc1 = bc2 = 1.0
+    if gs_state is None:
+        bc1 = 1.0 - beta1 ** step
+        bc2 = 1.0 - beta2 ** step
+    _l.check(L.ucfvit_adamw_clipped(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _p(shadow), _p(ema), p.numel(), lr, beta1, beta2,
+                                    eps, weight_decay, bc1, bc2, grad_scale, 0.0 if ema is None else rate, dt(g),
+                                    None if gs_state is None else _gs_state(gs_state).data_ptr(), _gc_state(clip_state).data_ptr(),
+                                    _stream()), "ucfvit_adamw_clipped")
+
+
 def cast(src, dst, scale=1.0):
     L = _l.load()
     _l.check(L.ucfvit_cast(src.data_ptr(), dst.data_ptr(), src.numel(), dt(src), dt(dst), scale, _stream()), "ucfvit_cast")

@@ -14,18 +14,26 @@ ema += (1 - decay) (p_new - ema): one fp32 buffer per flat run, one tensor per p
 a copy of the parameters before that step's update.  The average is not optimizer state in torch's sense and stays out of state_dict(),
 which keeps the torch.optim.AdamW layout; ema_state_dict / load_ema_state_dict carry it as a model state_dict, and ema_weights() swaps it
 into the model for evaluation.
+
+With `max_grad_norm` the gradients are clipped by their global L2 norm, torch.nn.utils.clip_grad_norm_'s rule, without being rewritten: one
+read-only pass per gradient segment (ucfvit_grad_sqnorm, which under a loss scaler is also the non-finite check and replaces
+ucfvit_grad_nonfinite), one launch that folds the partial sums into the norm and the coefficient (ucfvit_grad_clip_coef), and AdamW launches
+that multiply the coefficient into the factor they already apply to every gradient (ucfvit_adamw_clipped).  Norm and coefficient stay on the
+device (grad_norm(), clip_coef()); neither they nor the threshold are part of state_dict().
 """
 import contextlib
 
 import torch
 
 from . import ops
+from .lib import GC_COEF as _GC_COEF, GC_MAX_NORM as _GC_MAX_NORM, GC_NORM as _GC_NORM, GC_STATE_FLOATS as _GC_FLOATS
 from .lib import GS_APPLIED_STEPS as _GS_APPLIED, GS_SKIPPED_STEPS as _GS_SKIPPED
 
 
 class HipAdamW(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0, ema_decay=None):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0, ema_decay=None, max_grad_norm=None):
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        max_grad_norm = self._checked_max_norm(max_grad_norm)
         ema_rate = None if ema_decay is None else ops.ema_rate(ema_decay)      # 1 - decay in double; refuses a decay outside [0, 1)
         super().__init__(params, defaults)
         self.grad_scale = grad_scale  # multiplies gradients inside the kernel (e.g. 1/world_size, or 1/loss_scale)
@@ -40,6 +48,80 @@ class HipAdamW(torch.optim.Optimizer):
         # loss-scaler binding (step_scaled): the scaler's device state, and its skipped-step count when the host counters were last equal
         # to the applied-step count (construction or load_state_dict)
         self._gs, self._gs_skip_base, self._gs_bound = None, None, False
+        # clipping by global norm (None: off).  _gc: the device state block (UCFVIT_GC_*), _gc_ws: the partial sums of all gradient segments;
+        # both are allocated at the first clipped step and stay out of state_dict()
+        self._max_grad_norm, self._gc, self._gc_ws = max_grad_norm, None, None
+
+    # ------------------------------------------------------------------------------------------------ clipping by global norm
+    @staticmethod
+    def _checked_max_norm(value):
+        if value is None:
+            return None
+        if isinstance(value, bool) or not isinstance(value, float) or not 0.0 < value < float("inf"):       # (NaN fails the comparison)
+            raise ValueError(f"max_grad_norm must be None or a positive finite float, got {value!r}")
+        return value
+
+    @property
+    def max_grad_norm(self):
+        return self._max_grad_norm
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, value):
+        """None switches clipping off; a new threshold reaches the device by a device-side write (no synchronisation)"""
+        self._max_grad_norm = self._checked_max_norm(value)
+        if self._gc is not None and self._max_grad_norm is not None:
+            self._gc[_GC_MAX_NORM:_GC_MAX_NORM + 1].fill_(self._max_grad_norm)
+
+    def _clip_state(self):
+        """the fp32 state block on the device (UCFVIT_GC_* layout), created on first use by device-side writes"""
+        if self._max_grad_norm is None:
+            raise RuntimeError("this optimizer does not clip gradients (max_grad_norm=None)")
+        if self._gc is None:
+            gc = torch.zeros(_GC_FLOATS, dtype=torch.float32, device=self._params()[0].device)
+            gc[_GC_MAX_NORM:_GC_MAX_NORM + 1].fill_(self._max_grad_norm)
+            gc[_GC_COEF:_GC_COEF + 1].fill_(1.0)
+            self._gc = gc
+        return self._gc
+
+    def grad_norm(self):
+        """0-d device tensor (a view of the state): the global L2 norm of the last step's gradients before clipping, as AdamW consumed them
+        (times grad_scale, and under a loss scaler divided by the scale; Inf or NaN at a skipped step).  0 before the first step."""
+        return self._clip_state()[_GC_NORM]
+
+    def clip_coef(self):
+        """0-d device tensor (a view of the state): the factor min(1, max_grad_norm / (norm + 1e-6)) the last step applied"""
+        return self._clip_state()[_GC_COEF]
+
+    def _clip_pass(self, gs):
+        """sums of squares over ALL gradient segments of ALL groups (one flat run per group, or one launch per parameter that has a gradient),
+        then the coefficient: no group updates before it is final.  Under a loss scaler (gs) the same pass is the non-finite check."""
+        for group in self.param_groups:
+            for p in group["params"]:
+                if getattr(p, "_ucf_sharded", None):
+                    raise NotImplementedError(
+                        f"HipAdamW(max_grad_norm=...): a parameter is {p._ucf_sharded}-parallel: ranks hold different shards, so the global "
+                        "norm would need a sum over the group; not supported")
+        segs = []
+        for group in self.param_groups:
+            if not group["params"]:
+                continue
+            self._adopt_foreign_grads(group)
+            run = self._flat_run(group)
+            if run is not None:
+                segs.append(run[0].flat_g[run[1]:run[2]])
+                continue
+            segs.extend(p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in group["params"] if p.grad is not None)
+        counts = [ops.grad_sqnorm_partials(g.numel(), g.dtype) for g in segs]
+        total = sum(counts)
+        gc = self._clip_state()
+        if self._gc_ws is None or self._gc_ws.numel() < total:
+            self._gc_ws = torch.empty(max(total, 1), dtype=torch.float64, device=gc.device)
+        off = 0
+        for g, c in zip(segs, counts):
+            if c:
+                ops.grad_sqnorm(g, self._gc_ws[off:off + c], self.grad_scale, gs)
+            off += c
+        ops.grad_clip_coef(self._gc_ws, total, gc)
 
     def load_state_dict(self, state_dict):
         """accepts a torch.optim.AdamW / HipAdamW state_dict; the flat buffers are rebuilt from the per-parameter entries on the next
@@ -103,15 +185,21 @@ class HipAdamW(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        if self._max_grad_norm is not None:
+            self._clip_pass(None)
         self._update(None)
         return loss
 
     @torch.no_grad()
     def step_scaled(self, gs):
         """one step under a loss scaler whose device state is `gs` (HipGradScaler.step calls this): the non-finite check over ALL gradient
-        segments of ALL groups first, then the AdamW launches, so no group updates before the flag is final.  No host synchronisation."""
+        segments of ALL groups first, then the AdamW launches, so no group updates before the flag is final.  No host synchronisation.
+        With max_grad_norm the clip pass is that check (ucfvit_grad_sqnorm sets the flag): ucfvit_grad_nonfinite is not launched."""
         if self._gs is not gs or not self._gs_bound:
             self._bind_scaler(gs)
+        if self._max_grad_norm is not None:
+            self._clip_pass(gs)
+            return self._update(gs)
         for group in self.param_groups:
             if not group["params"]:
                 continue
@@ -126,7 +214,9 @@ class HipAdamW(torch.optim.Optimizer):
         self._update(gs)
 
     def _adamw(self, gs, p, g, m, v, shadow, ema, lr, b1, b2, eps, wd, step):
-        if ema is None:
+        if self._max_grad_norm is not None:
+            ops.clipped_adamw(p, g, m, v, shadow, ema, lr, b1, b2, eps, wd, step, self._ema_rate, self._gc, gs, self.grad_scale)
+        elif ema is None:
             if gs is None:
                 ops.adamw(p, g, m, v, shadow, lr, b1, b2, eps, wd, step, self.grad_scale)
             else:

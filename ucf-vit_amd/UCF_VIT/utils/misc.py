@@ -36,16 +36,17 @@ def unpatchify(patchified_pixel_values, data, patch_size, twoD):
     return x.reshape(B, C, gh * p, gw * p, gz * p)
 
 
-def configure_optimizer(model, lr, beta_1, beta_2, weight_decay, ema_decay=None):
+def configure_optimizer(model, lr, beta_1, beta_2, weight_decay, ema_decay=None, max_grad_norm=None):
     """AdamW with the reference's two groups: everything weight-decayed except names containing
     var_embed / pos_embed / time_pos_embed.  Returns the fused HIP AdamW (a torch.optim.Optimizer).  ema_decay (None: off): the update
-    pass also keeps an exponential moving average of the weights (HipAdamW.ema_state_dict / ema_weights)."""
+    pass also keeps an exponential moving average of the weights (HipAdamW.ema_state_dict / ema_weights).  max_grad_norm (None: off): the
+    gradients of both groups together are clipped by their global L2 norm inside the update (HipAdamW.grad_norm / clip_coef)."""
     decay, no_decay = [], []
     for name, p in model.named_parameters():
         (no_decay if is_no_decay(name) else decay).append(p)
     return HipAdamW(
         [dict(params=decay, lr=lr, betas=(beta_1, beta_2), weight_decay=weight_decay),
-         dict(params=no_decay, lr=lr, betas=(beta_1, beta_2), weight_decay=0)], ema_decay=ema_decay)
+         dict(params=no_decay, lr=lr, betas=(beta_1, beta_2), weight_decay=0)], ema_decay=ema_decay, max_grad_norm=max_grad_norm)
 
 
 def configure_scheduler(optimizer, warmup_steps, max_steps, warmup_start_lr, eta_min):

@@ -278,3 +278,32 @@ class StepTimer:
     def rate(self):
         torch.cuda.synchronize()
         return self.n / (time.perf_counter() - self.t0)
+
+
+def clip_grad_norm_of(conf):
+    """`model: clip_grad_norm` (absent: off): the threshold of HipAdamW's clipping by global gradient norm (PyYAML reads "1e-1" as str)"""
+    v = conf["model"].get("clip_grad_norm")
+    return None if v is None else float(v)
+
+
+class GradNormMeter:
+    """epoch mean of optimizer.grad_norm(), accumulated on the device (no synchronisation per step).  A step the loss scaler skipped has
+    a non-finite norm and is left out.  Without clipping the meter does nothing and suffix() is empty: the epoch line stays as it was."""
+
+    def __init__(self, optimizer, device):
+        self.opt = optimizer if optimizer.max_grad_norm is not None else None
+        self.sum, self.cnt = torch.zeros((), device=device), torch.zeros((), device=device)
+
+    def update(self):
+        if self.opt is not None:
+            g = self.opt.grad_norm()
+            ok = torch.isfinite(g)
+            self.sum += torch.where(ok, g, torch.zeros_like(g))
+            self.cnt += ok
+
+    def suffix(self):
+        if self.opt is None:
+            return ""
+        mean = (self.sum / self.cnt.clamp_min(1.0)).item()
+        self.sum.zero_(), self.cnt.zero_()
+        return f" grad_norm {mean:.4f}"

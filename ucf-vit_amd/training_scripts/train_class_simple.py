@@ -6,8 +6,8 @@ import sys
 
 import torch
 
-from _common import (SyntheticLoader, SyntheticSeqLoader, StepTimer, init_distributed, iters_per_epoch, load_config, maybe_resume, model_args,
-                     save_checkpoint, seed_drop_path, seed_dropout)
+from _common import (GradNormMeter, SyntheticLoader, SyntheticSeqLoader, StepTimer, init_distributed, iters_per_epoch, load_config, maybe_resume, model_args,
+                     clip_grad_norm_of, save_checkpoint, seed_drop_path, seed_dropout)
 from UCF_VIT.simple.arch import VIT
 from UCF_VIT.utils.fused_attn import FusedAttn
 from UCF_VIT.utils.metrics import cross_entropy_loss
@@ -29,7 +29,8 @@ def main(device, local_rank, rank, world):
     seed_drop_path(model, device, rank)                                      # stochastic depth: ranks must not share a draw
     seed_dropout(model, device, rank)                                        # dropout: neither ranks nor modules share a seed
     net = HipDataParallel(model)                                             # reference: DDP(model, find_unused_parameters=True)
-    optimizer = configure_optimizer(model, float(m["lr"]), float(m["beta_1"]), float(m["beta_2"]), float(m["weight_decay"]))   # PyYAML reads "1e-5" as str
+    optimizer = configure_optimizer(model, float(m["lr"]), float(m["beta_1"]), float(m["beta_2"]), float(m["weight_decay"]),
+                                    max_grad_norm=clip_grad_norm_of(conf))   # PyYAML reads "1e-5" as str
     scheduler = configure_scheduler(optimizer, int(m["warmup_steps"]), int(m["max_steps"]), float(m["warmup_start_lr"]), float(m["eta_min"]))
     epoch_start, loss_list = maybe_resume(conf, net, optimizer, scheduler)
     variables = d["dict_in_variables"][d["dataset"]]
@@ -45,18 +46,20 @@ def main(device, local_rank, rank, world):
         epoch_loss = torch.zeros((), device=device)
         epoch_acc = torch.zeros((), device=device)
         timer = StepTimer()
+        gnorm = GradNormMeter(optimizer, device)                              # `model: clip_grad_norm` only
         for batch_idx, (data, label, seq_ps) in enumerate(loader()):
             loss, output = training_step(data, variables, label, net, seq_ps)
             epoch_acc += (output.argmax(dim=1) == label).float().mean()
             epoch_loss += loss.detach()
             loss.backward()
             optimizer.step()
+            gnorm.update()
             optimizer.zero_grad()
             scheduler.step()
             timer.tick(data.shape[0] * world)
         loss_list.append(epoch_loss)
         if rank == 0:   # one host sync per epoch (the reference prints every iteration, a sync per step)
-            print(f"epoch: {epoch} epoch_loss {epoch_loss.item():.4f} epoch_accuracy {epoch_acc.item():.4f} images/s {timer.rate():.1f}", flush=True)
+            print(f"epoch: {epoch} epoch_loss {epoch_loss.item():.4f} epoch_accuracy {epoch_acc.item():.4f} images/s {timer.rate():.1f}{gnorm.suffix()}", flush=True)
         save_checkpoint(conf, epoch, net, optimizer, scheduler, loss_list, rank)
 
 

@@ -12,8 +12,8 @@ import sys
 
 import torch
 
-from _common import (SyntheticLoader, StepTimer, init_distributed, iters_per_epoch, load_config, maybe_resume, model_args, save_checkpoint,
-                     seed_drop_path, seed_dropout)
+from _common import (GradNormMeter, SyntheticLoader, StepTimer, init_distributed, iters_per_epoch, load_config, maybe_resume, model_args, save_checkpoint,
+                     clip_grad_norm_of, seed_drop_path, seed_dropout)
 from UCF_VIT.simple.arch import DiffusionVIT
 from UCF_VIT.ddpm.ddpm import DDPM_Scheduler
 from UCF_VIT.utils.fused_attn import FusedAttn
@@ -76,7 +76,7 @@ def main(device, local_rank, rank, world):
     net = HipDataParallel(model)
     ema_decay = m.get("ema_decay")
     optimizer = configure_optimizer(model, float(m["lr"]), float(m["beta_1"]), float(m["beta_2"]), float(m["weight_decay"]),
-                                    ema_decay=None if ema_decay is None else float(ema_decay))
+                                    ema_decay=None if ema_decay is None else float(ema_decay), max_grad_norm=clip_grad_norm_of(conf))
     scheduler = configure_scheduler(optimizer, int(m["warmup_steps"]), int(m["max_steps"]), float(m["warmup_start_lr"]), float(m["eta_min"]))
     scaler = configure_grad_scaler(bool(m.get("use_grad_scaler", False)))
     epoch_start, loss_list = resume(conf, net, optimizer, scheduler, scaler)
@@ -89,6 +89,7 @@ def main(device, local_rank, rank, world):
             reseed()
         epoch_loss = torch.zeros((), device=device)
         timer = StepTimer()
+        gnorm = GradNormMeter(optimizer, device)                              # `model: clip_grad_norm` only
         for data, _ in loader:
             data = data / 255.0
             t = torch.randint(0, margs["time_steps"], (data.shape[0],), device=device, generator=gen)
@@ -102,12 +103,13 @@ def main(device, local_rank, rank, world):
             else:
                 loss.backward()
                 optimizer.step()
+            gnorm.update()
             optimizer.zero_grad()
             scheduler.step()
             timer.tick(data.shape[0] * world)
         loss_list.append(epoch_loss)
         if rank == 0:
-            print(f"epoch: {epoch} epoch_loss {epoch_loss.item():.4f} images/s {timer.rate():.1f}", flush=True)
+            print(f"epoch: {epoch} epoch_loss {epoch_loss.item():.4f} images/s {timer.rate():.1f}{gnorm.suffix()}", flush=True)
         save_checkpoint(conf, epoch, net, optimizer, scheduler, loss_list, rank, scaler,
                         extra=None if ema_decay is None else {"model_ema_state_dict": optimizer.ema_state_dict(net)})
 

@@ -5,8 +5,8 @@ import sys
 
 import torch
 
-from _common import (SyntheticLoader, SyntheticSeqLoader, StepTimer, init_distributed, iters_per_epoch, load_config, maybe_resume, model_args,
-                     save_checkpoint, seed_drop_path, seed_dropout)
+from _common import (GradNormMeter, SyntheticLoader, SyntheticSeqLoader, StepTimer, init_distributed, iters_per_epoch, load_config, maybe_resume, model_args,
+                     clip_grad_norm_of, save_checkpoint, seed_drop_path, seed_dropout)
 from UCF_VIT.simple.arch import MAE
 from UCF_VIT.utils.fused_attn import FusedAttn
 from UCF_VIT.utils.metrics import patch_mse_loss, seq_mse_loss
@@ -37,7 +37,8 @@ def main(device, local_rank, rank, world):
     seed_drop_path(model, device, rank)                                      # stochastic depth: ranks must not share a draw
     seed_dropout(model, device, rank)                                        # dropout: neither ranks nor modules share a seed
     net = HipDataParallel(model)
-    optimizer = configure_optimizer(model, float(m["lr"]), float(m["beta_1"]), float(m["beta_2"]), float(m["weight_decay"]))   # PyYAML reads "1e-5" as str
+    optimizer = configure_optimizer(model, float(m["lr"]), float(m["beta_1"]), float(m["beta_2"]), float(m["weight_decay"]),
+                                    max_grad_norm=clip_grad_norm_of(conf))   # PyYAML reads "1e-5" as str
     scheduler = configure_scheduler(optimizer, int(m["warmup_steps"]), int(m["max_steps"]), float(m["warmup_start_lr"]), float(m["eta_min"]))
     # dynamic loss scaling of the reference's bf16 policy (train_masked_fsdp.py:417-419,601-606), folded into this entry point like the
     # rest of that script's bf16 semantics; off unless the config says `model: use_grad_scaler: True`
@@ -56,6 +57,7 @@ def main(device, local_rank, rank, world):
         model.train()
         epoch_loss = torch.zeros((), device=device)
         timer = StepTimer()
+        gnorm = GradNormMeter(optimizer, device)                              # `model: clip_grad_norm` only
         for data, seq_ps in loader():
             if margs["adaptive_patching"]:
                 loss, _, _ = training_step_adaptive(data, variables, net, loss_fn, seq_ps)
@@ -69,12 +71,13 @@ def main(device, local_rank, rank, world):
             else:
                 loss.backward()
                 optimizer.step()
+            gnorm.update()
             optimizer.zero_grad()
             scheduler.step()
             timer.tick(data.shape[0] * world)
         loss_list.append(epoch_loss)
         if rank == 0:
-            print(f"epoch: {epoch} epoch_loss {epoch_loss.item():.4f} images/s {timer.rate():.1f}", flush=True)
+            print(f"epoch: {epoch} epoch_loss {epoch_loss.item():.4f} images/s {timer.rate():.1f}{gnorm.suffix()}", flush=True)
         save_checkpoint(conf, epoch, net, optimizer, scheduler, loss_list, rank, scaler)
 
 

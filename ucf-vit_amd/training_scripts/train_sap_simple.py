@@ -8,8 +8,8 @@ import sys
 
 import torch
 
-from _common import (SyntheticSeqLoader, StepTimer, init_distributed, iters_per_epoch, load_config, maybe_resume, model_args, save_checkpoint,
-                     seed_drop_path, seed_dropout, sqrt_len_of)
+from _common import (GradNormMeter, SyntheticSeqLoader, StepTimer, clip_grad_norm_of, init_distributed, iters_per_epoch, load_config,
+                     maybe_resume, model_args, save_checkpoint, seed_drop_path, seed_dropout, sqrt_len_of)
 from UCF_VIT.simple.arch import SAP
 from UCF_VIT.utils.fused_attn import FusedAttn
 from UCF_VIT.utils.metrics import DiceBLoss
@@ -73,7 +73,8 @@ def main(device, local_rank, rank, world):
     seed_drop_path(model, device, rank)                                      # stochastic depth: ranks must not share a draw
     seed_dropout(model, device, rank)                                        # dropout: neither ranks nor modules share a seed
     net = HipDataParallel(model)
-    optimizer = configure_optimizer(model, float(m["lr"]), float(m["beta_1"]), float(m["beta_2"]), float(m["weight_decay"]))
+    optimizer = configure_optimizer(model, float(m["lr"]), float(m["beta_1"]), float(m["beta_2"]), float(m["weight_decay"]),
+                                    max_grad_norm=clip_grad_norm_of(conf))
     scheduler = configure_scheduler(optimizer, int(m["warmup_steps"]), int(m["max_steps"]), float(m["warmup_start_lr"]), float(m["eta_min"]))
     epoch_start, loss_list = maybe_resume(conf, net, optimizer, scheduler)
     variables = d["dict_in_variables"][d["dataset"]]
@@ -90,6 +91,7 @@ def main(device, local_rank, rank, world):
         model.train()
         epoch_loss = torch.zeros((), device=device)
         timer = StepTimer()
+        gnorm = GradNormMeter(optimizer, device)                              # `model: clip_grad_norm` only
         for seq, seq_ps, extra in loader:
             if from_image:
                 seq_label, label_map, nodes, count = extra
@@ -106,6 +108,7 @@ def main(device, local_rank, rank, world):
             epoch_loss += loss.detach()
             loss.backward()
             optimizer.step()
+            gnorm.update()
             optimizer.zero_grad()
             scheduler.step()
             timer.tick(seq.shape[0] * world)
@@ -115,7 +118,7 @@ def main(device, local_rank, rank, world):
             mean, _ = full_resolution_dice(output, label_map, nodes, count, margs["patch_size"], nc, margs["fixed_length"], margs["twoD"])
             dice = f" dice {mean.item():.4f}"
         if rank == 0:
-            print(f"epoch: {epoch} epoch_loss {epoch_loss.item():.4f} images/s {timer.rate():.1f}{dice}", flush=True)
+            print(f"epoch: {epoch} epoch_loss {epoch_loss.item():.4f} images/s {timer.rate():.1f}{dice}{gnorm.suffix()}", flush=True)
         save_checkpoint(conf, epoch, net, optimizer, scheduler, loss_list, rank)
 
 

@@ -17,8 +17,8 @@ import sys
 import torch
 import torch.nn.functional as F
 
-from _common import (SyntheticLoader, SyntheticSeqLoader, StepTimer, init_distributed, iters_per_epoch, load_config, maybe_resume, model_args,
-                     save_checkpoint, seed_drop_path, seed_dropout, seq_to_pseudo_image, sqrt_len_of)
+from _common import (GradNormMeter, SyntheticLoader, SyntheticSeqLoader, StepTimer, clip_grad_norm_of, init_distributed, iters_per_epoch,
+                     load_config, maybe_resume, model_args, save_checkpoint, seed_drop_path, seed_dropout, seq_to_pseudo_image, sqrt_len_of)
 from UCF_VIT.simple.arch import UNETR
 from UCF_VIT.utils.fused_attn import FusedAttn
 from UCF_VIT.utils.metrics import DiceMetric
@@ -63,7 +63,8 @@ def main(device, local_rank, rank, world):
     seed_drop_path(model, device, rank)                                      # stochastic depth: ranks must not share a draw
     seed_dropout(model, device, rank)                                        # dropout: neither ranks nor modules share a seed
     net = HipDataParallel(model)
-    optimizer = configure_optimizer(model, float(m["lr"]), float(m["beta_1"]), float(m["beta_2"]), float(m["weight_decay"]))   # PyYAML reads "1e-5" as str
+    optimizer = configure_optimizer(model, float(m["lr"]), float(m["beta_1"]), float(m["beta_2"]), float(m["weight_decay"]),
+                                    max_grad_norm=clip_grad_norm_of(conf))   # PyYAML reads "1e-5" as str
     scheduler = configure_scheduler(optimizer, int(m["warmup_steps"]), int(m["max_steps"]), float(m["warmup_start_lr"]), float(m["eta_min"]))
     extras = {"dice_list": []}
     epoch_start, loss_list = maybe_resume(conf, net, optimizer, scheduler, extras=extras)
@@ -79,6 +80,7 @@ def main(device, local_rank, rank, world):
         epoch_loss = torch.zeros((), device=device)
         dice_acc.reset()
         timer = StepTimer()
+        gnorm = GradNormMeter(optimizer, device)                              # `model: clip_grad_norm` only
         seqs = iter(seq_loader) if adaptive else None
         for data, label in loader:
             if adaptive:
@@ -92,13 +94,14 @@ def main(device, local_rank, rank, world):
             del output                                           # (backward needs the gradient the loss kept, not the logits)
             loss.backward()
             optimizer.step()
+            gnorm.update()
             optimizer.zero_grad()
             scheduler.step()
             timer.tick(data.shape[0] * world)
         loss_list.append(epoch_loss)
         dice_list.append(dice_acc.aggregate()[0])
         if rank == 0:
-            print(f"epoch: {epoch} epoch_loss {epoch_loss.item():.4f} volumes/s {timer.rate():.2f} dice {dice_list[-1].item():.4f}", flush=True)
+            print(f"epoch: {epoch} epoch_loss {epoch_loss.item():.4f} volumes/s {timer.rate():.2f} dice {dice_list[-1].item():.4f}{gnorm.suffix()}", flush=True)
         save_checkpoint(conf, epoch, net, optimizer, scheduler, loss_list, rank, extra={"dice_list": dice_list})
 
 
